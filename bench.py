@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: MH steps/sec (all chains) + ESS/sec.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype f64|f32]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dtype f64|f32] [--full] [--dump-outputs DIR]
 
 Default: BASELINE.json configs[1] (C2) -- RWMH on the isotropic 100-dim Gaussian, 65 536 chains per GPU -- in fp64, the
-arithmetic the reference computes in (Distributions' Float64 rand / logpdf).  The same run also reports the fp32 engine
+arithmetic the reference computes in (Distributions' Float64 rand / logpdf).  A --full run also reports the fp32 engine
 as a second figure (`f32`), never as `value`.
 
 One "step" = one pass of the hot path over one batch = ONE mhx_run_sample call that advances all chains of this rank by
@@ -31,13 +31,18 @@ runs launcher, rendezvous, ladder and the host-side combining with no device and
 Prints ONE JSON line on rank 0, < 8 KB (the driver keeps an 8 KB tail): numbers only -- what each field means, the byte
 models and the workload texts are DESIGN.md section 7.  `roofline` prices the dominant kernel (bound "hbm": algorithmic bytes
 of DESIGN.md section 7 over the HIP-event launch time measured here; bound "valu": PMC wave-instructions per launch over the
-same time against the issue peak); `cpu_baseline` is the CPU oracle (a port of the reference algorithm, oracle/, rebuilt -O3
--march=native on the host that times it) on a bounded sample -- rank 0, N=1 only.  At N=1 the default (c2) run also carries,
-all measured after the timed region:
+same time against the issue peak).
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `value` (MH steps/s of the headline config),
+`ms_per_step`, `acceptance_rate`, `roofline`.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs).
+Everything else is --full (a --no-* option drops one part of it again).  At N=1 a --full run also carries `cpu_baseline`, the
+CPU oracle (a port of the reference algorithm, oracle/, rebuilt -O3 -march=native on the host that times it) on a bounded
+sample, `f32` the fp32 engine on the same workload, and c5's `rhat`; the c2 run on top of that, all measured after the timed region:
   `e2e_host`  the rate THROUGH the boundary -- samples back on the host (mhx_run_sample_to_host), save-all and thinned;
   `configs`   the other BASELINE.json configs and their SURVEY 8(d) variants (c1, c2_literal, c3, c3_rotated, c4,
               c4_moving, c4_fixed, c4_deferred, c5, c5_banana): {value, ms_per_step, acc, bound, frac, traffic_ratio, gen, cpu, ...} each;
-  `ess`       the ESS/sec window;  `f32` the fp32 engine on the same workload.
+  `ess`       the ESS/sec window;  `rhat_last_launch`.
+A run of several ranks or members carries the all-reduced R-hat (`rhat`, `rhat_last_launch`) with or without --full.
 """
 import argparse
 import json
@@ -752,6 +757,56 @@ def timed(wl, steps, warmup, barrier, spin=30):
     return time.perf_counter() - t0, kernel_ms, accepted, transitions, st
 
 
+DUMP_BYTES = 48 << 20                # under 64 MB whichever way a megabyte is counted, .npy headers included
+
+
+def dump_outputs(wl, out_dir, seed=0x5EED):
+    """--dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy.  A config that keeps a record (c1, c2,
+    c3) writes `samples` [N][d+1][k] and `accepted` [N][k]; every config writes the chains' last state `state_x` [d][k] and
+    `state_lp` [k], and c5 the moment sums of its R-hat reduction (`sum_m`, `sum_m2`, `sum_v`, [d+1] each).  k chains of the
+    run, picked by a fixed seed (and, should one chain's record alone take half the budget, a seeded subset of its N rows), so that
+    the files stay within DUMP_BYTES and two runs with the same arguments write the same entries.  Reals in the run's width, the
+    accept flags as float32 0 / 1."""
+    import numpy as np
+    run = wl.run
+    real = np.dtype(run.real)
+    n, d = run.n, run.dim
+    keep = wl.sched()[4]
+    rng = np.random.default_rng(seed)
+    out = {}
+    x, lp, _ = run.state()
+    if keep is True:
+        samples, acc = run.samples()
+        N = samples.shape[0]
+        rows = np.arange(N)
+        row_bytes = (d + 1) * real.itemsize + 4
+        if N * row_bytes + (d + 1) * real.itemsize > DUMP_BYTES // 2:
+            rows = np.sort(rng.choice(N, min(N, (DUMP_BYTES // 2) // row_bytes), replace=False))
+        per_chain = len(rows) * row_bytes + (d + 1) * real.itemsize
+        k = max(1, min(n, DUMP_BYTES // per_chain))
+        idx = np.sort(rng.choice(n, k, replace=False))
+        out["samples"] = samples[:, :, idx] if len(rows) == N else samples[np.ix_(rows, np.arange(d + 1), idx)]
+        out["accepted"] = (acc[:, idx] if len(rows) == N else acc[np.ix_(rows, idx)]).astype(np.float32)
+        del samples, acc
+    else:
+        k = max(1, min(n, DUMP_BYTES // 2 // ((d + 1) * real.itemsize)))
+        idx = np.sort(rng.choice(n, k, replace=False))
+    out["state_x"] = np.ascontiguousarray(x[:, idx])
+    out["state_lp"] = lp[idx]
+    if keep == "moments":
+        dg = run.diagnostics(max_lag=0)
+        for key in ("sum_m", "sum_m2", "sum_v"):
+            out[key] = np.asarray(dg[key], dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in out.items():
+        np.save(os.path.join(out_dir, key + ".npy"), np.ascontiguousarray(a))
+    sys.stderr.write("bench.py --dump-outputs: %s (%d of %d chains, %.1f MB) in %s\n" % (
+        ", ".join("%s%s" % (key, list(a.shape)) for key, a in out.items()), len(idx), n, total / 1e6, out_dir))
+
+
 def ess_window(mhx, wl, world):
     """ESS/sec of SURVEY 8(d): rank-normalised bulk ESS (split chains, Geyer truncation; mhx_run_ess_bulk_tail) of a THINNED
     window long enough for the autocorrelations to die out -- 256 draws `thin` transitions apart, thin chosen so that the window
@@ -1232,14 +1287,21 @@ def main():
     ap.add_argument("--tools-lib", action="store_true", help="bind libmhx_tools.so (timing probes, fault injection: --opt EMCEE_PROBE=3 ...); "
                     "a run with a probe option is tainted and the line says so")
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous + ladder + host-side combining only: no device, no engine")
-    ap.add_argument("--no-other-configs", action="store_true", help="c2 at N=1: skip the C3 / C4 / C4-moving / C5 lines under `configs`")
-    ap.add_argument("--no-e2e", action="store_true", help="c2 at N=1: skip the rate through the boundary (samples back on the host)")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the line can carry: the ESS window, "
+                    "e2e_host, the fp32 figure, the CPU baseline, the other configs and the R-hat of a one-rank run (a --no-* option "
+                    "drops one of them again).  Without it: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(a fixed, seeded sample of its chains) as DIR/<name>.npy, float32 / float64, 48 MiB at most")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, c2 at N=1: skip the C3 / C4 / C4-moving / C5 lines under `configs`")
+    ap.add_argument("--no-e2e", action="store_true", help="--full, c2 at N=1: skip the rate through the boundary (samples back on the host)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="size of the CPU-baseline sample of the headline config")
-    ap.add_argument("--no-second-dtype", action="store_true", help="skip the fp32 figure")
-    ap.add_argument("--no-ess", action="store_true")
+    ap.add_argument("--no-second-dtype", action="store_true", help="--full: skip the fp32 figure")
+    ap.add_argument("--no-ess", action="store_true", help="--full: skip the ESS window")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     args.opt = [tuple(o.split("=", 1)) if "=" in o else (o, "1") for o in args.opt]
 
     single = args.single_process and args.gpus > 1
@@ -1327,11 +1389,15 @@ def main():
             ctx.set_option("TOTAL_CHAINS", wl.C * world)
         wl.build(mhx, ctx, rank)
     dt, kernel_ms, accepted, transitions, st = timed(wl, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.first if single else wl, args.dump_outputs)
 
-    # outside the timed region: diagnostics, the ESS window, the fp32 figure, the CPU baseline
+    # outside the timed region, --full only for one rank: diagnostics, the ESS window, the fp32 figure, the CPU baseline
+    lone = world == 1 and not single
+    full = args.full
     ess, diag = None, None
     chains_all = None
-    if args.config in ("c2", "c5"):
+    if args.config in ("c2", "c5") and (full or not lone):
         if single:
             diag = wl.g.diagnostics(max_lag=0)                   # the members' sums added on the host
             chains_all = diag["n_chains"]
@@ -1350,8 +1416,7 @@ def main():
             acc_rate = v[0] / v[1]
     else:
         acc_rate = accepted / float(transitions)
-    lone = world == 1 and not single
-    if args.config == "c2" and not args.no_ess and not args.c2_literal and not args.c2_user and rank == 0 and lone:
+    if full and args.config == "c2" and not args.no_ess and not args.c2_literal and not args.c2_user and rank == 0 and lone:
         try:
             ess = ess_window(mhx, wl, world)
         except Exception as e:                                   # never let a diagnostic break the bench line
@@ -1405,12 +1470,12 @@ def main():
             # the all-reduced between / within statistic of the LAST timed launch only (consecutive transitions, shorter than one
             # autocorrelation time at d = 100): it exercises the collective, it is not a convergence claim -- see ess.rhat_max_split
             out["rhat_last_launch"] = sig(float(np.nanmax(diag["rhat"][:wl.d])))
-        if lone and args.config == "c2" and not args.no_e2e and not args.c2_literal and not args.c2_user:
+        if full and lone and args.config == "c2" and not args.no_e2e and not args.c2_literal and not args.c2_user:
             try:
                 out["e2e_host"] = e2e_host(mhx, wl)
             except Exception as e:
                 out["e2e_host"] = {"error": str(e)[:160]}
-        if lone and not args.no_second_dtype and args.dtype == "f64":
+        if full and lone and not args.no_second_dtype and args.dtype == "f64":
             try:                                                  # the same workload on the fp32 engine: a second figure, never `value`
                 ctx32 = mhx.Context(device, "f32")
                 for k, v in args.opt:
@@ -1429,9 +1494,9 @@ def main():
                 wl32.run.close()
             except Exception as e:
                 out["f32"] = {"error": str(e)[:160]}
-        if lone and not args.no_cpu_baseline:
+        if full and lone and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, args.dtype, args.cpu_seconds)
-        if lone and args.config == "c2" and not args.no_other_configs and not args.c2_literal and not args.c2_user:
+        if full and lone and args.config == "c2" and not args.no_other_configs and not args.c2_literal and not args.c2_user:
             wl.run.close()                                        # 13.4 GB of samples: C4 needs the room
             out["configs"] = other_configs(mhx, ctx, args, barrier)
         try:                                                      # run-time kernels of the whole run: built here / by clang++ / from the disk cache

@@ -349,6 +349,57 @@ def test_bench_refuses_to_claim_ranks_or_gpus_it_does_not_have():
         assert rc != 0 and line is None
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs (bench.dump_outputs) on a stand-in run: float32 / float64 files only, 64 MB at most in all even for the
+    headline's 13 GB record, the same chains on every call, and each dumped chain's columns taken from that chain."""
+    import bench
+
+    class Run:
+        def __init__(self, n, d, N, real):
+            self.n, self.dim, self.real = n, d, real
+            self.rec = np.broadcast_to(np.arange(n, dtype=real), (N, d + 1, n))     # every entry of chain c is c
+            self.acc = np.broadcast_to((np.arange(n) % 2).astype(np.uint8), (N, n))
+
+        def state(self):
+            return np.array(self.rec[-1, :self.dim]), np.array(self.rec[-1, self.dim]), np.zeros(self.n, np.uint32)
+
+        def samples(self):
+            return self.rec, self.acc
+
+        def diagnostics(self, max_lag=0):
+            return {k: np.ones(self.dim + 1) for k in ("sum_m", "sum_m2", "sum_v")}
+
+    class Workload:
+        def __init__(self, run, keep):
+            self.run, self.keep = run, keep
+
+        def sched(self):
+            return (1, 1, 1, 0, self.keep)
+
+    cases = [(65536, 100, 250, np.float64, True, {"samples", "accepted", "state_x", "state_lp"}),
+             (300, 10, 5, np.float32, True, {"samples", "accepted", "state_x", "state_lp"}),
+             (1, 2, 10 ** 7, np.float64, True, {"samples", "accepted", "state_x", "state_lp"}),
+             (8192, 1000, 1, np.float64, "moments", {"state_x", "state_lp", "sum_m", "sum_m2", "sum_v"}),
+             (8192, 200, 1, np.float32, False, {"state_x", "state_lp"})]
+    for i, (n, d, N, real, keep, names) in enumerate(cases):
+        dirs = [tmp_path / ("%d_%d" % (i, rep)) for rep in (0, 1)]
+        for dr in dirs:
+            bench.dump_outputs(Workload(Run(n, d, N, real), keep), str(dr))
+        files = sorted(os.listdir(dirs[0]))
+        assert files == sorted(k + ".npy" for k in names) == sorted(os.listdir(dirs[1]))
+        assert sum(os.path.getsize(dirs[0] / f) for f in files) <= 64e6
+        got = {f[:-4]: np.load(dirs[0] / f) for f in files}
+        for f in files:
+            assert got[f[:-4]].dtype in (np.float32, np.float64)
+            assert np.array_equal(got[f[:-4]], np.load(dirs[1] / f))
+        chains = got["state_lp"]
+        assert got["state_x"].dtype == real and np.array_equal(got["state_x"], np.broadcast_to(chains, got["state_x"].shape))
+        assert np.all(np.diff(chains) > 0) and 0 < chains.size <= n
+        if "samples" in got:
+            assert np.array_equal(got["samples"], np.broadcast_to(chains, got["samples"].shape))
+            assert np.array_equal(got["accepted"], np.broadcast_to((chains % 2).astype(np.float32), got["accepted"].shape))
+
+
 def test_bench_line_fits_the_drivers_tail():
     """The driver keeps an 8 KB tail of stdout: the whole line has to fit.  Checked on the last full line a GPU box printed
     (profiles/r0[456]*_bench_full.json, committed) and on the worst case the compact blocks can reach."""

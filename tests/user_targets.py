@@ -156,8 +156,9 @@ class _UserData(C.Structure):
     _fields_ = [("p", C.c_void_p), ("n", C.c_int)]
 
 
-def host_target(oracle, source, dim, data=None, cache_dir="/tmp/mhx_user_targets"):
-    """Compile `source` with g++ (same -ffp-contract=off discipline) and wrap it as an oracle Target."""
+def host_target(oracle, source, dim, data=None, cache_dir=os.path.join(ROOT, "oracle", "_user_targets")):
+    """Compile `source` with g++ (same -ffp-contract=off discipline) and wrap it as an oracle Target.  The objects are cached
+    inside this checkout (git-ignored): each one links against this checkout's oracle by rpath."""
     import numpy as np
     oracle.build()
     os.makedirs(cache_dir, exist_ok=True)
@@ -170,9 +171,11 @@ def host_target(oracle, source, dim, data=None, cache_dir="/tmp/mhx_user_targets
         cpp = os.path.join(cache_dir, "user_%s.cpp" % tag)
         open(cpp, "w").write(_PRELUDE + source + epilogue)
         odir = os.path.join(ROOT, "oracle")
+        tmp = "%s.%d.tmp" % (so, os.getpid())         # renamed into place when complete: an interrupted compile leaves no .so
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-mfma", "-mavx2", "-DMHX_REAL64=%d" % (1 if f64 else 0), "-o", so, cpp, "-L" + odir,
+                               "-mfma", "-mavx2", "-DMHX_REAL64=%d" % (1 if f64 else 0), "-o", tmp, cpp, "-L" + odir,
                                "-lmhx_oracle64" if f64 else "-lmhx_oracle", "-Wl,-rpath," + odir])
+        os.replace(tmp, so)
     lib = C.CDLL(so)
     addr = C.cast(lib.user_logdensity, C.c_void_p).value
     ud = None

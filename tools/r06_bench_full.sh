@@ -1,10 +1,12 @@
 #!/bin/bash
-mkdir -p gpurun_out/r06b
-timeout 1500 python bench.py > gpurun_out/r06b/bench_full.json 2> gpurun_out/r06b/bench_full.err; echo "rc $?" >> gpurun_out/r06b/bench_full.err
-tail -3 gpurun_out/r06b/bench_full.err
+# the whole line (--full) and its blocks; OUT = a directory for the results
+: "${OUT:?set OUT to a results directory}"; OUT=$(realpath -m "$OUT"); export OUT
+mkdir -p $OUT
+timeout 1500 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc $?" >> $OUT/bench_full.err
+tail -3 $OUT/bench_full.err
 python - <<'PY'
-import json
-line = open("gpurun_out/r06b/bench_full.json").read().strip().splitlines()[-1]
+import json, os
+line = open(os.path.join(os.environ["OUT"], "bench_full.json")).read().strip().splitlines()[-1]
 print("line length", len(line))
 d = json.loads(line)
 print("value", d["value"], "frac", d["roofline"]["frac"])

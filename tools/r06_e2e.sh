@@ -1,8 +1,9 @@
-mkdir -p gpurun_out/r06a
-timeout 900 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-second-dtype --no-ess > gpurun_out/r06a/bench.json 2> gpurun_out/r06a/bench.err; echo "bench rc $?" >> gpurun_out/r06a/bench.err
-tail -3 gpurun_out/r06a/bench.err
+: "${OUT:?set OUT to a results directory}"; OUT=$(realpath -m "$OUT"); export OUT
+mkdir -p $OUT
+timeout 900 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-second-dtype --no-ess > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?" >> $OUT/bench.err
+tail -3 $OUT/bench.err
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r06a/bench.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["OUT"], "bench.json")).read().strip().splitlines()[-1])
 print(json.dumps(d.get("e2e_host"), indent=1))
 PY

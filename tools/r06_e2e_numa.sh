@@ -1,12 +1,13 @@
 #!/bin/bash
-mkdir -p gpurun_out/r06a
-for f in /sys/bus/pci/devices/*/numa_node; do d=$(dirname $f); if [ "$(cat $d/vendor 2>/dev/null)" = "0x1002" ]; then echo "$d class $(cat $d/class) numa $(cat $f)"; fi; done > gpurun_out/r06a/gpu_numa.txt
+: "${OUT:?set OUT to a results directory}"; OUT=$(realpath -m "$OUT"); export OUT
+mkdir -p $OUT
+for f in /sys/bus/pci/devices/*/numa_node; do d=$(dirname $f); if [ "$(cat $d/vendor 2>/dev/null)" = "0x1002" ]; then echo "$d class $(cat $d/class) numa $(cat $f)"; fi; done > $OUT/gpu_numa.txt
 run() { # label, taskset-list
   if [ -n "$2" ]; then pre="taskset -c $2"; else pre=""; fi
-  $pre timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-second-dtype --no-ess > gpurun_out/r06a/bench_$1.json 2> gpurun_out/r06a/bench_$1.err
+  $pre timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-second-dtype --no-ess > $OUT/bench_$1.json 2> $OUT/bench_$1.err
   python - "$1" <<'PY'
-import json, sys
-d = json.loads(open("gpurun_out/r06a/bench_%s.json" % sys.argv[1]).read().strip().splitlines()[-1])
+import json, os, sys
+d = json.loads(open(os.path.join(os.environ["OUT"], "bench_%s.json" % sys.argv[1])).read().strip().splitlines()[-1])
 e = d.get("e2e_host", {})
 for k in ("save_all", "save_all_pageable", "save_all_plain"):
     b = e.get(k, {})
@@ -16,4 +17,4 @@ PY
 run free ""
 run node0 "0-63,128-191"
 run node1 "64-127,192-255"
-cat gpurun_out/r06a/gpu_numa.txt
+cat $OUT/gpu_numa.txt
