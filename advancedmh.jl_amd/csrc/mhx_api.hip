@@ -285,6 +285,13 @@ static const char* opt(const mhx_ctx* ctx, const char* name)
     auto it = ctx->options.find(name);
     return it == ctx->options.end() ? nullptr : it->second.c_str();
 }
+// ... as a number (`unset_value` when the option is not set), and as a switch (set and not 0)
+static int opt_int(const mhx_ctx* ctx, const char* name, int unset_value)
+{
+    const char* v = opt(ctx, name);
+    return v ? atoi(v) : unset_value;
+}
+static bool opt_on(const mhx_ctx* ctx, const char* name) { return opt_int(ctx, name, 0) != 0; }
 // The chains of the WHOLE run a shard belongs to (option TOTAL_CHAINS; mhx_group_shard sets it on the member's context, a process
 // of a multi-process run sets it itself): the kernel form -- and with it the summation order of the log-density -- is chosen for
 // that count, so that a shard takes the form the unsharded run takes and stays bit for bit its part of it (the
@@ -429,8 +436,8 @@ static void jit_cache_write(const std::string& dir, const std::string& name, con
 }
 
 // compile `source` (which #includes the embedded device headers) with hiprtc for gfx950
-static int jit_compile(mhx_ctx* ctx, const std::string& key_in, const std::string& source,
-                       const std::vector<std::string>& defines, jit_module** out, const std::vector<std::string>& extra_opts = {})
+static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vector<std::string>& defines, jit_module** out,
+                       const std::vector<std::string>& extra_opts = {})
 {
     // tools build, option JIT_DEFS = "NAME=VALUE NAME=VALUE": extra defines for every hiprtc compile of the context -- how the A/B
     // scripts reach the kernels' compile-time knobs; part of both cache keys.  It taints the context (a define can change a
@@ -438,9 +445,6 @@ static int jit_compile(mhx_ctx* ctx, const std::string& key_in, const std::strin
     const char* xdefs = MHX_PROBE_OPT(ctx, "JIT_DEFS");
     struct jit_guard { jit_guard() { mhx_jit_lock(); } ~jit_guard() { mhx_jit_unlock(); } } one_at_a_time;
     const char* xflags = MHX_PROBE_OPT(ctx, "JIT_FLAGS");      // (tools build: raw compiler options, blank-separated, for A/B of code generation)
-    const std::string key = ((xdefs && *xdefs) ? key_in + "/xd=" + xdefs : key_in) + ((xflags && *xflags) ? std::string("/xf=") + xflags : std::string());
-    auto it = ctx->jit.find(key);
-    if (it != ctx->jit.end()) { *out = it->second.get(); return MHX_OK; }
     const char* hdr_src[] = {k_src_mhx_zig_table_h, k_src_mhx_device_math_h, k_src_mhx_targets_h, k_src_mhx_rwmh_kernels_h,
                              k_src_mhx_emcee_kernels_h, k_src_mhx_ram_kernels_h, k_src_mhx_mala_kernels_h,
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
@@ -453,24 +457,26 @@ static int jit_compile(mhx_ctx* ctx, const std::string& key_in, const std::strin
 #ifdef MHX_TOOLS_BUILD
     opts.push_back("-DMHX_TOOLS_BUILD=1");              // the embedded headers of this build carry the probes
 #endif
+    // the blank-separated words of `list`, each behind `prefix`
+    auto push_words = [&opts](const char* list, const char* prefix) {
+        for (const char* p = list; p && *p;) {
+            while (*p == ' ') ++p;
+            const char* e = p;
+            while (*e && *e != ' ') ++e;
+            if (e > p) opts.push_back(prefix + std::string(p, e));
+            p = e;
+        }
+    };
     for (auto& d : defines) opts.push_back("-D" + d);
-    if (xdefs)
-        for (const char* p = xdefs; *p;) {
-            while (*p == ' ') ++p;
-            const char* e = p;
-            while (*e && *e != ' ') ++e;
-            if (e > p) opts.push_back("-D" + std::string(p, e));
-            p = e;
-        }
+    push_words(xdefs, "-D");
     for (auto& o : extra_opts) opts.push_back(o);
-    if (xflags)
-        for (const char* p = xflags; *p;) {
-            while (*p == ' ') ++p;
-            const char* e = p;
-            while (*e && *e != ' ') ++e;
-            if (e > p) opts.push_back(std::string(p, e));
-            p = e;
-        }
+    push_words(xflags, "");
+    // the context's modules are keyed by what is compiled: the source and every option ('\0' occurs in neither).  Not by the
+    // compiler: a module the context holds is reused whichever one the option names now
+    std::string key = source;
+    for (auto& o : opts) { key += '\0'; key += o; }
+    auto it = ctx->jit.find(key);
+    if (it != ctx->jit.end()) { *out = it->second.get(); return MHX_OK; }
     // Which compiler: the installation's clang++ where there is one (mhx_jit_ext.h: hiprtc is whichever copy the process loaded first,
     // a PyTorch wheel's older one inside Python), hiprtc otherwise or when option JIT_COMPILER says "hiprtc"; "clang" = no fall-back
     const char* jc = opt(ctx, "JIT_COMPILER");
@@ -515,8 +521,11 @@ static int jit_compile(mhx_ctx* ctx, const std::string& key_in, const std::strin
             return mhx_fail(MHX_EJIT, "JIT_COMPILER=clang: %s", xlog.c_str());
         }
         // (a source that does not compile fails here too: hiprtc's log is the one the caller gets; MHX_JIT_VERBOSE=1 shows this one)
-        if (const char* v = getenv("MHX_JIT_VERBOSE")) if (*v && *v != '0')
-            fprintf(stderr, "mhx: the offline compiler failed on %s, hiprtc takes over: %.1500s\n", key.c_str(), xlog.c_str());
+        if (const char* v = getenv("MHX_JIT_VERBOSE")) if (*v && *v != '0') {
+            std::string what;
+            for (auto& d : defines) what += " " + d;
+            fprintf(stderr, "mhx: the offline compiler failed on%s, hiprtc takes over: %.1500s\n", what.c_str(), xlog.c_str());
+        }
     }
     hiprtcProgram prog = nullptr;
     hiprtcResult r = hiprtcCreateProgram(&prog, source.c_str(), "mhx_jit.hip", 11, hdr_src, hdr_name);
@@ -557,6 +566,19 @@ static int jit_function(jit_module* m, const char* name, hipFunction_t* fn)
     m->fns[name] = *fn;
     return MHX_OK;
 }
+// let a kernel (pre-built, or a hipFunction_t of a run-time module) use `lds_bytes` of dynamic LDS; what a refusal means is the caller's
+static int kernel_lds_limit(const void* fn, size_t lds_bytes, const char* what)
+{
+    if (lds_bytes && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+        return mhx_fail(MHX_EHIP, "%s: %zu bytes of LDS refused", what, lds_bytes);
+    return MHX_OK;
+}
+// the kernel `name` of a run-time module, allowed `lds_bytes` of dynamic LDS
+static int jit_kernel(jit_module* m, const char* name, hipFunction_t* fn, size_t lds_bytes, const char* what)
+{
+    const int rc = jit_function(m, name, fn);
+    return rc ? rc : kernel_lds_limit((const void*)*fn, lds_bytes, what);
+}
 
 // ---------------------------------------------------------------------------------------------
 // targets
@@ -566,7 +588,6 @@ struct mhx_target : mhx_handle_hdr {
     mhx_real cst = MHX_R(0.0);
     mhx_real* dparams = nullptr;
     std::string user_src;        // MHX_TARGET_USER
-    std::string user_key;        // hash of the source, for the JIT cache
     int bandwidth = -1;          // CORR_GAUSS: largest r - c with A_rc != 0 (exact zeros only), -1 otherwise: a banded precision
                                  // factor (Markov / autoregressive model) lets the row products skip the zeros
     ~mhx_target() { if (dparams) (void)hipFree(dparams); }
@@ -654,15 +675,6 @@ int api_target_builtin(mhx_ctx* ctx, int kind, int dim, const mhx_real* params, 
     return MHX_OK;
 }
 
-static std::string fnv_hex(const std::string& s)
-{
-    unsigned long long h = 1469598103934665603ull;
-    for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; }
-    char b[32];
-    snprintf(b, sizeof b, "%016llx", h);
-    return b;
-}
-
 static std::string jit_source(const mhx_target* t, const char* family_header)
 {
     std::string s = "#include \"mhx_device_math.h\"\n";
@@ -679,8 +691,7 @@ static std::string jit_source(const mhx_target* t, const char* family_header)
 
 static int jit_generic_rwmh(const mhx_target* t, jit_module** m)
 {
-    const std::string key = "rwmh_generic/tk=" + std::to_string(t->kind) + "/" + t->user_key;
-    return jit_compile(t->ctx, key, jit_source(t, "mhx_rwmh_kernels.h"),
+    return jit_compile(t->ctx, jit_source(t, "mhx_rwmh_kernels.h"),
                        {"MHX_JIT_RWMH_GENERIC=1", "MHX_JIT_TK=" + std::to_string(t->kind)}, m);
 }
 
@@ -698,7 +709,6 @@ int api_target_from_hip_source(mhx_ctx* ctx, const char* src, int dim, const mhx
     t->dim = dim;
     t->cst = MHX_R(0.0);
     t->user_src = src;
-    t->user_key = fnv_hex(t->user_src);
     int rc = target_upload(t.get(), data, ndata);
     if (rc) return rc;
     // compile now so that a bad source is reported at model construction, like a MethodError would be
@@ -759,6 +769,23 @@ int api_target_eval(mhx_ctx* ctx, const mhx_target* t, const mhx_real* x, int n,
 // ---------------------------------------------------------------------------------------------
 // runs
 enum run_kind { RUN_RWMH = 0, RUN_EMCEE = 1, RUN_RAM = 2, RUN_MALA = 3 };
+// The kernel form of a run.  The numbers are frozen: they travel as mhx_stats.kernel_variant (described at include/mhx.h:403), in
+// ckpt_header.variant, and the host mirrors and bench.py read them.
+enum kernel_form {
+    KF_GENERIC = 0,         // run-time dimension, state in HBM
+    KF_REG = 1,             // pre-built register kernel
+    KF_REG_JIT = 2,         // run-time specialised register kernel
+    KF_COOP = 3,            // pre-built cooperative kernel
+    KF_COOP_JIT = 4,        // run-time specialised cooperative kernel
+    KF_DENSE_COOP = 5,      // cooperative RWMH kernel with dense factor images in LDS
+    KF_EMCEE_PERSIST = 6,   // a small ensemble as one persistent block
+    KF_EMCEE_SEQ = 7,       // the reference's sequential ensemble sweep
+    KF_MFMA = 8,            // matrix-core RWMH / MALA
+    KF_EMCEE_SCAL = 9,      // scalar-factor form of the stretch move
+    KF_EMCEE_MFMA = 10,     // matrix-core form of the stretch move
+    KF_WAVE = 11,           // a wave per chain
+    KF_RAM_DEFER = 12,      // RAM with a deferred factor
+};
 
 struct mhx_run : mhx_handle_hdr {
     mhx_ctx* ctx = nullptr;
@@ -825,8 +852,7 @@ struct mhx_run : mhx_handle_hdr {
     bool moments_mode = false;
     void (*reg_fn_mom)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;
     hipFunction_t jit_step_mom = nullptr;
-    std::string coop_key;                // JIT key / defines of the cooperative kernel (for its moments twin)
-    std::vector<std::string> coop_defs;
+    std::vector<std::string> coop_defs;  // defines of the cooperative kernel (its moments twin differs in MHX_JIT_MOM)
     // kernel choice
     int normal_gen = MHX_GEN_BOX_MULLER; // how stream bits become standard normals (MHX_FLAG_ZIGGURAT: the table ziggurat, fp64)
     size_t reg_lds = 0;                  // dynamic LDS of the register kernel: the tail of a state that does not fit beside the candidate
@@ -843,12 +869,10 @@ struct mhx_run : mhx_handle_hdr {
     mhx_real *d_xw2 = nullptr, *d_lp2 = nullptr;   // ... the buffers the next sweep writes (swapped with d_xw / d_lp after every launch)
     size_t sweep_lds = 0;
     bool emcee_preload = false;          // the half-step kernel takes its hot arguments as preloaded scalars (MHX_JIT_PRELOAD)
-    bool emcee_mfma = false;             // the matrix-core form of the stretch move (variant 10): 4 lanes per walker, operand image in d_mfma_img
-    bool emcee_scal = false;             // the scalar-factor form of the cooperative stretch move (variant 9): coop_L waves per block, 64 walkers
-    int variant = 0;
+    int variant = KF_GENERIC;            // kernel_form
     void (*reg_fn)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;
-    void (*reg_fn8)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;   // variant 11: the K = 8 build of the wave-per-chain kernel
-    int wave_k = 4;                      // variant 11: candidates per round of the next call (8 after a call that accepted < 1 step in 8)
+    void (*reg_fn8)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;   // KF_WAVE: the K = 8 build of the wave-per-chain kernel
+    int wave_k = 4;                      // KF_WAVE: candidates per round of the next call (8 after a call that accepted < 1 step in 8)
     hipFunction_t jit_step = nullptr, jit_init = nullptr;
     mhx_stats stats{};
     mhx_host_stats host_stats{};         // what the last mhx_run_sample_to_host moved
@@ -948,8 +972,8 @@ static size_t mfma_image_reals(int d)
 static size_t mfma_image_reals_T(int d) { const int NT = (d + 15) / 16; return (size_t)(NT * (NT + 1) / 2) * 256; }   // the image of A^T
 static bool mfma_fits(const mhx_ctx* ctx, int d, int reduce_lanes, int nimages)
 {
-    const char* no_mfma = opt(ctx, "NO_MFMA");                      // tuning knob: the vector kernel instead
-    return (reduce_lanes == 0 || reduce_lanes == 4) && d >= 16 && (d + 3) / 4 <= MHX_MFMA_MAX_NS && !(no_mfma && atoi(no_mfma)) &&
+    // (NO_MFMA, tuning knob: the vector kernel instead)
+    return (reduce_lanes == 0 || reduce_lanes == 4) && d >= 16 && (d + 3) / 4 <= MHX_MFMA_MAX_NS && !opt_on(ctx, "NO_MFMA") &&
            nimages * mfma_image_reals(d) * sizeof(mhx_real) <= MHX_LDS_PER_BLOCK;
 }
 // streamed images (larger than a block's LDS): two ring buffers of whole 256-thread rounds of 16-byte pieces of the largest chunk
@@ -970,8 +994,7 @@ static size_t mfma_ring_bytes(int d, bool pair = true)
 // 0 = no, 1 = tile pairs + state in registers, 2 = single tiles + state in HBM
 static int mfma_stream_mode(const mhx_ctx* ctx, int d, int reduce_lanes)
 {
-    const char* no_mfma = opt(ctx, "NO_MFMA");
-    if (!((reduce_lanes == 0 || reduce_lanes == 4) && d >= 16) || (no_mfma && atoi(no_mfma))) return 0;
+    if (!((reduce_lanes == 0 || reduce_lanes == 4) && d >= 16) || opt_on(ctx, "NO_MFMA")) return 0;
     const int NS = (d + 3) / 4;
     if (NS <= MHX_MFMA_STREAM_MAX_NS && mfma_ring_bytes(d, true) <= MHX_LDS_PER_BLOCK) return 1;
     if (NS <= MHX_MFMA_XMEM_MAX_NS && mfma_ring_bytes(d, false) <= MHX_LDS_PER_BLOCK) return 2;
@@ -1048,19 +1071,18 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     // the register / cooperative kernels address a [dim+1][nchains] slab with 32-bit byte offsets
     if (((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) >= (1ull << 32)) r->flags |= MHX_FLAG_GENERIC;
     // ---- kernel choice
-    r->variant = 0;
+    r->variant = KF_GENERIC;
     const int tk = t->kind, pk = r->prop_kind;
     // (fp32, round 6: 256 layers, one Philox word per normal -- on the cooperative kernel, the register kernel and MALA's register kernel
     // like fp64; the check at the end of this function refuses a run whose kernel has no ziggurat form)
     if ((cfg->flags & MHX_FLAG_ZIGGURAT) && d >= (1 << 20))      // the retry blocks are numbered (normal index << 8 | attempt) in 28 bits
         return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: dim must be below 2^20");
-    int regmax = pk == MHX_PROP_DENSE ? MHX_REG_MAX_DIM_DENSE : MHX_REG_MAX_DIM;
-    if (const char* rm = opt(ctx, "REG_MAX_DIM")) regmax = atoi(rm);      // tuning knob
+    int regmax = opt_int(ctx, "REG_MAX_DIM", pk == MHX_PROP_DENSE ? MHX_REG_MAX_DIM_DENSE : MHX_REG_MAX_DIM);      // tuning knob
     const int nblk = (d + 3) / 4;
     const bool separable = tk == MHX_TARGET_ISO_GAUSS || tk == MHX_TARGET_BANANA || tk == MHX_TARGET_FUNNEL;
     // lanes per chain: cfg->reduce_lanes, or (auto) the smallest power of two that (a) keeps a lane's
     // blocks in registers (<= 13 blocks = 104 VGPRs of state) and (b) gives the chip >= 2 waves per SIMD
-    // A wave per chain (variant 11): the data-sum target of the README example with FEW chains -- the lanes split the likelihood's
+    // A wave per chain (KF_WAVE): the data-sum target of the README example with FEW chains -- the lanes split the likelihood's
     // terms (reduction shape 64).  Asked for (reduce_lanes = 64), or by default while every chain can have a wave to itself (<= 2 per
     // SIMD) and there are terms to split; the plain random walk, ISO / DIAG proposal, Box-Muller normals.
     if (tk == MHX_TARGET_IID_NORMAL && d == 2 && pk != MHX_PROP_DENSE && walk == MHX_WALK_PLAIN &&
@@ -1068,7 +1090,7 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         (cfg->reduce_lanes == 64 || (cfg->reduce_lanes == 0 && t->nparams >= 8 && chains_of_whole_run(ctx, r->n) <= 2048))) {
         r->reg_fn = pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 4> : k_rwmh_wave<MHX_PROP_DIAG, 4>;
         r->reg_fn8 = pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 8> : k_rwmh_wave<MHX_PROP_DIAG, 8>;
-        r->variant = 11;
+        r->variant = KF_WAVE;
         r->coop_L = 64;
     } else if (tk == MHX_TARGET_IID_NORMAL && cfg->reduce_lanes > 1) {
         return mhx_fail(MHX_EINVAL, "mhx_rwmh_create: the data-sum target knows reduce_lanes 0, 1 and 64 (a wave per chain: plain walk, "
@@ -1110,41 +1132,29 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         if (mfma_fits(ctx, d, cfg->reduce_lanes, nimg)) {
             jit_module* m = nullptr;
             const int waves = mfma_waves(ctx, d);
-            const std::string key = "rwmh_mfma/d=" + std::to_string(d) + "/pk=" + std::to_string(pk) + "/tk=" + std::to_string(tk) +
-                                    "/w=" + std::to_string(waves);
-            rc = jit_compile(ctx, key, jit_source(t, "mhx_rwmh_mfma_kernels.h"),
+            rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_mfma_kernels.h"),
                              {"MHX_JIT_RWMH_MFMA=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_PK=" + std::to_string(pk),
                               "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_rwmh_mfma", &r->jit_step);
-            if (rc == MHX_OK) {
-                r->dense_lds = nimg * mfma_image_reals(d) * sizeof(mhx_real);
-                if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->dense_lds) != hipSuccess)
-                    rc = mhx_fail(MHX_EHIP, "matrix-core kernel: %zu bytes of LDS refused", r->dense_lds);
-            }
-            if (rc == MHX_OK) { r->variant = 8; r->coop_L = 4; }
+            r->dense_lds = nimg * mfma_image_reals(d) * sizeof(mhx_real);
+            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_mfma", &r->jit_step, r->dense_lds, "matrix-core kernel");
+            if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; }
         }
-        if (!r->variant && mfma_stream_fits(ctx, d, cfg->reduce_lanes)) {
+        if (r->variant == KF_GENERIC && mfma_stream_fits(ctx, d, cfg->reduce_lanes)) {
             // the images do not fit a block's LDS: they stay in global memory (built once, here) and every block walks them
             // through an LDS ring, one tile pair at a time
             jit_module* m = nullptr;
             const int smode = mfma_stream_mode(ctx, d, cfg->reduce_lanes);
-            const std::string key = "rwmh_mfma_stream/d=" + std::to_string(d) + "/pk=" + std::to_string(pk) + "/tk=" + std::to_string(tk) +
-                                    "/mode=" + std::to_string(smode);
             // the kernel is fully unrolled over its tiles: lift hipcc's size limit for `#pragma unroll` (past it the candidate
             // would be indexed dynamically, i.e. live in scratch)
-            rc = jit_compile(ctx, key, jit_source(t, "mhx_rwmh_mfma_kernels.h"),
+            rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_mfma_kernels.h"),
                              {"MHX_JIT_RWMH_MFMA_STREAM=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_PK=" + std::to_string(pk),
                               "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_WAVES=1", std::string("MHX_JIT_PAIR=") + (smode == 1 ? "1" : "0"),
                               std::string("MHX_JIT_XMEM=") + (smode == 2 ? "1" : "0")}, &m,
                              {"-mllvm", "-pragma-unroll-threshold=4000000"});
             hipFunction_t fimg = nullptr;
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_rwmh_mfma_stream", &r->jit_step);
+            r->dense_lds = mfma_ring_bytes(d, smode == 1);
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image", &fimg);
-            if (rc == MHX_OK) {
-                r->dense_lds = mfma_ring_bytes(d, smode == 1);
-                if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->dense_lds) != hipSuccess)
-                    rc = mhx_fail(MHX_EHIP, "streamed matrix-core kernel: %zu bytes of LDS refused", r->dense_lds);
-            }
+            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_mfma_stream", &r->jit_step, r->dense_lds, "streamed matrix-core kernel");
             if (rc == MHX_OK) {
                 const size_t reals = mfma_image_reals(d);
                 HIP_TRY(hipMalloc(&r->d_mfma_img, 2 * reals * sizeof(mhx_real)));
@@ -1158,34 +1168,28 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
                 }
                 if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(ctx->stream));
             }
-            if (rc == MHX_OK) { r->variant = 8; r->coop_L = 4; r->mfma_stream = true; }
+            if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->mfma_stream = true; }
             else { r->jit_step = nullptr; }
         }
         // reduce_lanes = 4 asked for explicitly and a matrix-core kernel was tried but did not come up: the error is the
         // caller's, like every other explicit reduce_lanes (no silent change of the summation shape)
-        if (!r->variant && rc != MHX_OK && cfg->reduce_lanes == 4) return rc;
+        if (r->variant == KF_GENERIC && rc != MHX_OK && cfg->reduce_lanes == 4) return rc;
         L = cfg->reduce_lanes > 1 ? cfg->reduce_lanes : dense_coop_lanes(d);
-        if (r->variant == 8 || !dense_coop_fits(d, L, nimg)) {
+        if (r->variant == KF_MFMA || !dense_coop_fits(d, L, nimg)) {
             L = 1;
         } else {
         if (L > 64 || (L & (L - 1)) || L > d) return mhx_fail(MHX_EINVAL, "reduce_lanes must be a power of two <= min(64, dim), got %d", L);
         jit_module* m = nullptr;
-        const std::string key = "rwmh_dense/d=" + std::to_string(d) + "/l=" + std::to_string(L) + "/pk=" + std::to_string(pk) +
-                                "/tk=" + std::to_string(tk);
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_rwmh_dense_kernels.h"),
+        rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_dense_kernels.h"),
                          {"MHX_JIT_RWMH_DENSE=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_L=" + std::to_string(L),
                           "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_TK=" + std::to_string(tk)}, &m);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_rwmh_dense", &r->jit_step);
-        if (rc == MHX_OK) {
-            r->dense_lds = dense_coop_lds_bytes(d, L, (tk == MHX_TARGET_CORR_GAUSS ? 1 : 0) + (pk == MHX_PROP_DENSE ? 1 : 0));
-            if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->dense_lds) != hipSuccess)
-                rc = mhx_fail(MHX_EHIP, "dense cooperative kernel: %zu bytes of LDS refused", r->dense_lds);
-        }
-        if (rc == MHX_OK) { r->variant = 5; r->coop_L = L; }
+        r->dense_lds = dense_coop_lds_bytes(d, L, nimg);
+        if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_dense", &r->jit_step, r->dense_lds, "dense cooperative kernel");
+        if (rc == MHX_OK) { r->variant = KF_DENSE_COOP; r->coop_L = L; }
         else if (cfg->reduce_lanes > 1) return rc;
         L = 1;                                                        // not the separable cooperative path below
         }
-    } else if (cfg->reduce_lanes > 1 && r->variant != 11) {
+    } else if (cfg->reduce_lanes > 1 && r->variant != KF_WAVE) {
         return mhx_fail(MHX_EINVAL, "reduce_lanes > 1 needs a separable catalogue target or the dense Gaussian target "
                                 "(dim <= 128, JIT), and an ISO/DIAG proposal");
     }
@@ -1194,57 +1198,41 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         if (NBL > MHX_COOP_NBL_MAX) return mhx_fail(MHX_EINVAL, "reduce_lanes=%d leaves %d blocks per lane (max %d)", L, NBL, MHX_COOP_NBL_MAX);
         // tuning knobs: MHX_NO_PREBUILT=1 specialises with hiprtc even where a pre-built kernel exists; MHX_COOP_WAVES=w
         // overrides the waves-per-SIMD launch bound of the hiprtc kernel (register budget 512 / w)
-        const char* no_prebuilt = opt(ctx, "NO_PREBUILT");
-        const char* waves_env = opt(ctx, "COOP_WAVES");
-        const int waves_override = waves_env ? atoi(waves_env) : 0;
+        const int waves_override = opt_int(ctx, "COOP_WAVES", 0);
         const bool zig = (cfg->flags & MHX_FLAG_ZIGGURAT) != 0;
         if (zig && MHX_ZIG_LDS_BYTES(NBL) > MHX_LDS_PER_BLOCK)
             return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: %d blocks per lane need %d bytes of LDS per block (limit %d); use more lanes per chain",
                             NBL, (int)MHX_ZIG_LDS_BYTES(NBL), (int)MHX_LDS_PER_BLOCK);
-        if (!(no_prebuilt && atoi(no_prebuilt)) && !waves_override && !walk)
+        if (zig) r->coop_lds = MHX_ZIG_LDS_BYTES(NBL);
+        if (!opt_on(ctx, "NO_PREBUILT") && !waves_override && !walk)
             for (const auto& pb : k_prebuilt_coop)
                 if (pb.L == L && pb.NBL == NBL && pb.TK == tk && pb.PK == pk && pb.gen == (zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER)) {
-                    r->reg_fn = pb.fn; r->reg_fn_mom = pb.fn_mom; r->variant = 3; r->normal_gen = pb.gen;
-                    if (zig) {
-                        r->coop_lds = MHX_ZIG_LDS_BYTES(NBL);
-                        for (auto f : {pb.fn, pb.fn_mom})
-                            if (f && hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->coop_lds) != hipSuccess)
-                                return mhx_fail(MHX_EHIP, "cooperative kernel (ziggurat): %zu bytes of LDS refused", r->coop_lds);
-                    }
+                    r->reg_fn = pb.fn; r->reg_fn_mom = pb.fn_mom; r->variant = KF_COOP; r->normal_gen = pb.gen;
+                    for (auto f : {pb.fn, pb.fn_mom})
+                        if (f && (rc = kernel_lds_limit((const void*)f, r->coop_lds, "cooperative kernel (ziggurat)"))) return rc;
                 }
-        if (!r->variant && !(r->flags & MHX_FLAG_NO_JIT)) {
+        // the kernel's defines; its running-moments twin (mhx_run_sample, MHX_SAVE_MOMENTS) is built from this list with MHX_JIT_MOM=1
+        r->coop_defs = {"MHX_JIT_RWMH_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
+                        "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_MOM=0",
+                        "MHX_JIT_WALK=" + std::to_string(walk), std::string("MHX_JIT_GEN=") + (zig ? "1" : "0")};
+        if (r->variant == KF_GENERIC && !(r->flags & MHX_FLAG_NO_JIT)) {
             jit_module* m = nullptr;
-            const std::string key = "rwmh_coop/l=" + std::to_string(L) + "/nbl=" + std::to_string(NBL) + "/tk=" +
-                                    std::to_string(tk) + "/pk=" + std::to_string(pk) + "/w=" + std::to_string(waves_override) +
-                                    "/walk=" + std::to_string(walk) + "/gen=" + std::to_string(zig ? 1 : 0)
-#ifdef MHX_TOOLS_BUILD
-                                    + (opt(ctx, "ZIG_PROBE") ? std::string("/zp=") + opt(ctx, "ZIG_PROBE") : std::string()) +
-                                    (opt(ctx, "ZIG_FORCE_FAIL") ? std::string("/zff=") + opt(ctx, "ZIG_FORCE_FAIL") : std::string())
-#endif
-                                    ;
-            std::vector<std::string> defs = {"MHX_JIT_RWMH_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
-                                             "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_MOM=0",
-                                             "MHX_JIT_WALK=" + std::to_string(walk), std::string("MHX_JIT_GEN=") + (zig ? "1" : "0")};
+            std::vector<std::string> defs = r->coop_defs;
             if (waves_override > 0) defs.push_back("MHX_JIT_WAVES=" + std::to_string(waves_override));
 #ifdef MHX_TOOLS_BUILD
-            if (const char* zf = opt(ctx, "ZIG_FORCE_FAIL"))                       // test hook: see mhx_rwmh_kernels.h (the chains stay valid)
-                if (atoi(zf) > 0) defs.push_back(std::string("MHX_ZIG_FORCE_FAIL=") + std::to_string(atoi(zf)));
+            if (const int zf = opt_int(ctx, "ZIG_FORCE_FAIL", 0); zf > 0)          // test hook: see mhx_rwmh_kernels.h (the chains stay valid)
+                defs.push_back("MHX_ZIG_FORCE_FAIL=" + std::to_string(zf));
             if (const char* zp = opt(ctx, "ZIG_PROBE")) {                          // timing probe: the chains of such a run are NOT valid
                 defs.push_back(std::string("MHX_ZIG_PROBE=") + zp);
                 fprintf(stderr, "mhx (tools build): ZIG_PROBE=%s -- timing probe, this run's chains are NOT valid (stats.tainted = 1)\n", zp);
             }
 #endif
-            rc = jit_compile(ctx, key + "/mom=0", jit_source(t, "mhx_rwmh_kernels.h"), defs, &m);
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_rwmh_coop", &r->jit_step);
-            if (rc == MHX_OK && zig) {
-                r->coop_lds = MHX_ZIG_LDS_BYTES(NBL);
-                if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->coop_lds) != hipSuccess)
-                    rc = mhx_fail(MHX_EHIP, "cooperative kernel (ziggurat): %zu bytes of LDS refused", r->coop_lds);
-            }
-            if (rc == MHX_OK) { r->variant = 4; r->normal_gen = zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER; }
+            rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_kernels.h"), defs, &m);
+            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_coop", &r->jit_step, r->coop_lds, "cooperative kernel (ziggurat)");
+            if (rc == MHX_OK) { r->variant = KF_COOP_JIT; r->normal_gen = zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER; }
             else if (cfg->reduce_lanes > 1 || zig) return rc;      // the caller asked for this shape explicitly
         }
-        if (r->variant) {
+        if (r->variant != KF_GENERIC) {
             // one or two chains per wave: rows of the [dim][chains] arrays move through LDS, CB = 4 * (64 / L) chains at a time
             // (mhx_rwmh_coop_body); the ziggurat's slab holds that buffer, the Box-Muller kernels get one of their own
             if (L >= 32) {
@@ -1253,22 +1241,17 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
                 else if (need <= 65536) { r->coop_lds = (need + 15) & ~(size_t)15; r->coop_tr = 1; }
             }
             r->coop_L = L;
-            r->coop_key = "rwmh_coop/l=" + std::to_string(L) + "/nbl=" + std::to_string(NBL) + "/tk=" + std::to_string(tk) +
-                          "/pk=" + std::to_string(pk) + "/walk=" + std::to_string(walk) + "/gen=" + std::to_string(zig ? 1 : 0);
-            r->coop_defs = {"MHX_JIT_RWMH_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
-                            "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_MOM=1",
-                            "MHX_JIT_WALK=" + std::to_string(walk), std::string("MHX_JIT_GEN=") + (zig ? "1" : "0")};
         } else if (cfg->reduce_lanes > 1) return mhx_fail(MHX_EINVAL, "reduce_lanes=%d: no pre-built kernel and JIT disabled", L);
     }
-    if (!r->variant && walk) {
+    if (r->variant == KF_GENERIC && walk) {
         // no cooperative kernel for this target / proposal family: the state-in-HBM kernel evaluates the ratio
         if (cfg->reduce_lanes > 1) return mhx_fail(MHX_EINVAL, "reduce_lanes > 1 with a drifting / static proposal needs a separable catalogue target and an ISO / DIAG proposal");
         r->flags |= MHX_FLAG_GENERIC;
     }
-    if (!r->variant && !(r->flags & MHX_FLAG_GENERIC)) {
+    if (r->variant == KF_GENERIC && !(r->flags & MHX_FLAG_GENERIC)) {
         if (tk != MHX_TARGET_USER && !(cfg->flags & MHX_FLAG_ZIGGURAT))
             for (const auto& pb : k_prebuilt_reg)
-                if (pb.D == d && pb.TK == tk && pb.PK == pk) { r->reg_fn = pb.fn; r->variant = 1; }
+                if (pb.D == d && pb.TK == tk && pb.PK == pk) { r->reg_fn = pb.fn; r->variant = KF_REG; }
         // The candidate must be whole in a lane's registers (an arbitrary log-density reads all of it); the state need not be: above
         // MHX_REG_XR_ALL dimensions only its first MHX_REG_XR_CAP coordinates stay in registers, the tail lives in LDS
         // (mhx_rwmh_reg_body<..., XR>).  That carries the kernel to twice its old dimension limit -- an fp64 user log-density at
@@ -1279,7 +1262,7 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         // the kernel runs 3 x slower (the cliff between d = 96 and d = 100 of the first measurement).
         const bool split = d > MHX_REG_XR_ALL && d <= 2 * MHX_REG_MAX_DIM && pk != MHX_PROP_DENSE;
         if (!opt(ctx, "REG_MAX_DIM") && split) regmax = 2 * MHX_REG_MAX_DIM;
-        if (!r->variant && !(r->flags & MHX_FLAG_NO_JIT) && d <= regmax &&
+        if (r->variant == KF_GENERIC && !(r->flags & MHX_FLAG_NO_JIT) && d <= regmax &&
             !(tk == MHX_TARGET_CORR_GAUSS && d > (MHX_REAL64 ? 32 : 64)) && !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096)) {
             jit_module* m = nullptr;
             int xr = split ? MHX_REG_XR_CAP : d;
@@ -1297,23 +1280,16 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             // (option REG_ZSLAB = 0 / 1 overrides)
             bool zslab = !MHX_REAL64 && zig_reg && 4 * (MHX_REG_ZIG_LDS_BYTES(d, xr) + MHX_REG_ZIG_SLAB_BYTES(d)) <= 163840;
             if (const char* ze = opt(ctx, "REG_ZSLAB")) zslab = !MHX_REAL64 && zig_reg && atoi(ze) != 0;
-            const std::string key = "rwmh_reg/d=" + std::to_string(d) + "/tk=" + std::to_string(tk) + "/pk=" +
-                                    std::to_string(pk) + "/xr=" + std::to_string(xr) + (ut ? std::string("/ut=") + ut : std::string()) +
-                                    (zig_reg ? "/gen=1" : "") + (zslab ? "/slab" : "") + (rwaves > 1 ? "/w=" + std::to_string(rwaves) : std::string()) +
-                                    "/" + t->user_key;
             std::vector<std::string> rdefs = {"MHX_JIT_RWMH_REG=1", "MHX_JIT_DIM=" + std::to_string(d),
                                               "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_XR=" + std::to_string(xr)};
             if (zig_reg) rdefs.push_back("MHX_JIT_GEN=1");
             if (zslab) rdefs.push_back("MHX_JIT_ZSLAB=1");
             if (rwaves > 1) rdefs.push_back("MHX_JIT_REG_WAVES=" + std::to_string(rwaves));
-            rc = jit_compile(ctx, key, jit_source(t, "mhx_rwmh_kernels.h"), rdefs, &m, xo);
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_rwmh_reg", &r->jit_step);
+            rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_kernels.h"), rdefs, &m, xo);
             r->reg_lds = (size_t)(d - xr) * 64 * sizeof(mhx_real);
             if (zig_reg) r->reg_lds = MHX_REG_ZIG_LDS_BYTES(d, xr) + (zslab ? MHX_REG_ZIG_SLAB_BYTES(d) : 0);
-            if (rc == MHX_OK && r->reg_lds > 65536 &&
-                hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->reg_lds) != hipSuccess)
-                rc = mhx_fail(MHX_EHIP, "register kernel: %zu bytes of LDS refused", r->reg_lds);
-            if (rc == MHX_OK) { r->variant = 2; if (zig_reg) r->normal_gen = MHX_GEN_ZIGGURAT; }
+            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_reg", &r->jit_step, r->reg_lds, "register kernel");
+            if (rc == MHX_OK) { r->variant = KF_REG_JIT; if (zig_reg) r->normal_gen = MHX_GEN_ZIGGURAT; }
             else if (tk == MHX_TARGET_USER) return rc;      // no pre-built kernel can run a user source
             // built-in target: the generic kernel below computes the same chain; keep the message
         }
@@ -1322,14 +1298,14 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         jit_module* m = nullptr;
         if ((rc = jit_generic_rwmh(t, &m))) return rc;
         if ((rc = jit_function(m, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
-        if (r->variant == 0 && (rc = jit_function(m, "mhx_jit_rwmh_generic", &r->jit_step))) return rc;
+        if (r->variant == KF_GENERIC && (rc = jit_function(m, "mhx_jit_rwmh_generic", &r->jit_step))) return rc;
     }
     if ((cfg->flags & MHX_FLAG_ZIGGURAT) && r->normal_gen != MHX_GEN_ZIGGURAT)
         return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: this run's kernel (variant %d) has no ziggurat form -- it exists on the cooperative "
                                     "kernel (separable catalogue target) and on the register kernel (any target within its "
                                     "dimension limit), ISO / DIAG proposal, JIT allowed", r->variant);
     // candidate scratch of the state-in-HBM kernel; a static proposal whitens the state into it whatever kernel steps the chain
-    if (r->variant == 0 || r->d_qx) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
+    if (r->variant == KF_GENERIC || r->d_qx) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
     *out = r.release();
     return MHX_OK;
 }
@@ -1406,7 +1382,7 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->variant == 3 || r->variant == 4) {
+        if (r->variant == KF_COOP || r->variant == KF_COOP_JIT) {
             const long threads = (((long)r->n + (64 / r->coop_L) - 1) / (64 / r->coop_L)) * 64;   // whole waves
             unsigned grid = (unsigned)((threads + 255) / 256);
             if (r->coop_L >= 32) grid = (grid + 7u) & ~7u;          // the kernel's XCD-aware block -> chain map wants whole rounds of 8
@@ -1415,38 +1391,37 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
             } else if (r->moments_mode) {
                 void* params[] = {&a, &tp, &pv};
                 HIP_TRY(hipModuleLaunchKernel(r->jit_step_mom, grid, 1, 1, 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
-            } else if (r->variant == 3) {
+            } else if (r->variant == KF_COOP) {
                 hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(256), r->coop_lds, ctx->stream, a, tp, pv);
             } else {
                 void* params[] = {&a, &tp, &pv};
                 HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
             }
-        } else if (r->variant == 8 && r->mfma_stream) {
+        } else if (r->variant == KF_MFMA && r->mfma_stream) {
             const unsigned grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
             mhx_real* gA = r->d_mfma_img;
             mhx_real* gL = r->d_mfma_img + mfma_image_reals(r->dim);
             void* params[] = {&a, &tp, &pv, &gA, &gL};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds,
                                           ctx->stream, params, nullptr));
-        } else if (r->variant == 8) {
+        } else if (r->variant == KF_MFMA) {
             const unsigned grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
             void* params[] = {&a, &tp, &pv};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds,
                                           ctx->stream, params, nullptr));
-        } else if (r->variant == 5) {
+        } else if (r->variant == KF_DENSE_COOP) {
             const long per_block = (64 / r->coop_L) * MHX_EMCEE_COOP_WAVES;          // chains per block
             const unsigned grid = (unsigned)(((long)r->n + per_block - 1) / per_block);
             void* params[] = {&a, &tp, &pv};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_EMCEE_COOP_WAVES, 1, 1, (unsigned)r->dense_lds,
                                           ctx->stream, params, nullptr));
-        } else if (r->variant == 11) {                           // a wave per chain; candidates per round: by the last call's acceptance
-            const char* wk = opt(r->ctx, "WAVE_K");
-            const int k = wk ? atoi(wk) : r->wave_k;
+        } else if (r->variant == KF_WAVE) {                      // a wave per chain; candidates per round: by the last call's acceptance
+            const int k = opt_int(r->ctx, "WAVE_K", r->wave_k);
             hipLaunchKernelGGL(k == 8 ? r->reg_fn8 : r->reg_fn, dim3((unsigned)r->n), dim3(64), 0, ctx->stream, a, tp, pv);
-        } else if (r->variant == 1) {
+        } else if (r->variant == KF_REG) {
             const unsigned grid = (unsigned)((r->n + 63) / 64);
             hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(64), 0, ctx->stream, a, tp, pv);
-        } else if (r->variant == 2) {
+        } else if (r->variant == KF_REG_JIT) {
             const unsigned grid = (unsigned)((r->n + 63) / 64);
             void* params[] = {&a, &tp, &pv};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64, 1, 1, (unsigned)r->reg_lds, ctx->stream, params, nullptr));
@@ -1562,16 +1537,15 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->rec_loga_view = nullptr;
     if (save_samples == MHX_SAVE_MOMENTS) {
         // running moments instead of a sample tensor
-        if (r->kind != RUN_RWMH || (r->variant != 0 && r->variant != 3 && r->variant != 4))
+        if (r->kind != RUN_RWMH || (r->variant != KF_GENERIC && r->variant != KF_COOP && r->variant != KF_COOP_JIT))
             return mhx_fail(MHX_EINVAL, "running moments need an RWMH run on the cooperative or the generic kernel "
                                     "(separable target, or MHX_FLAG_GENERIC); this run uses kernel variant %d", r->variant);
-        if (((r->variant == 3 && !r->reg_fn_mom) || r->variant == 4) && !r->jit_step_mom) {
+        if (((r->variant == KF_COOP && !r->reg_fn_mom) || r->variant == KF_COOP_JIT) && !r->jit_step_mom) {
             jit_module* m = nullptr;
-            int rcj = jit_compile(ctx, r->coop_key + "/mom=1", jit_source(r->target, "mhx_rwmh_kernels.h"), r->coop_defs, &m);
-            if (rcj == MHX_OK) rcj = jit_function(m, "mhx_jit_rwmh_coop", &r->jit_step_mom);
-            if (rcj == MHX_OK && r->coop_lds &&
-                hipFuncSetAttribute((const void*)r->jit_step_mom, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->coop_lds) != hipSuccess)
-                rcj = mhx_fail(MHX_EHIP, "cooperative kernel (ziggurat, moments): %zu bytes of LDS refused", r->coop_lds);
+            std::vector<std::string> defs = r->coop_defs;
+            for (auto& df : defs) if (df == "MHX_JIT_MOM=0") df = "MHX_JIT_MOM=1";
+            int rcj = jit_compile(ctx, jit_source(r->target, "mhx_rwmh_kernels.h"), defs, &m);
+            if (rcj == MHX_OK) rcj = jit_kernel(m, "mhx_jit_rwmh_coop", &r->jit_step_mom, r->coop_lds, "cooperative kernel (moments)");
             if (rcj) return rcj;
         }
         const size_t bytes = ((size_t)r->dim + 1) * (size_t)r->n * sizeof(mhx_real);
@@ -1636,7 +1610,7 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->stats.transitions = nT * (uint64_t)r->n;
     r->stats.accepted = acc_after - acc_before;
     r->stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (r->variant == 11 && r->stats.transitions >= 64)          // (the same chain for either K: only the speed depends on it)
+    if (r->variant == KF_WAVE && r->stats.transitions >= 64)        // (the same chain for either K: only the speed depends on it)
         r->wave_k = 8.0 * (double)r->stats.accepted < (double)r->stats.transitions ? 8 : 4;
     return MHX_OK;
 }

@@ -68,7 +68,7 @@ static mhx_emcee_args emcee_args(const mhx_run* r)
     a.seed = r->seed; a.ensemble_id = r->first_id;
     a.nwalkers = r->ens_w; a.dim = r->dim;
     a.ld = r->n;                                          // E ensembles side by side: columns of [..][E W] arrays
-    a.ybuf_ens = r->variant == 7 ? r->dim : r->ens_w;
+    a.ybuf_ens = r->variant == KF_EMCEE_SEQ ? r->dim : r->ens_w;
     a.target_kind = r->target->kind; a.ntparams = r->target->nparams; a.tconst = r->target->cst;
     a.stretch = r->stretch;
     a.save_slot = -1;
@@ -109,28 +109,21 @@ static int emcee_create_mfma(mhx_run* r, const mhx_target* t, const int d)
     jit_module* m = nullptr;
     const char* wv = opt(r->ctx, "EMCEE_MFMA_WAVES");                      // tuning knob
     r->coop_waves = wv ? std::max(1, std::min(8, atoi(wv))) : 1;
-    const std::string key = "emcee_mfma/d=" + std::to_string(d) + "/w=" + std::to_string(r->coop_waves) +
-                            (opt(r->ctx, "EMCEE_REC_STORE") ? std::string("/rs=") + opt(r->ctx, "EMCEE_REC_STORE") : std::string());
     std::vector<std::string> defs = {"MHX_JIT_EMCEE_MFMA=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_EMCEE_MFMA_WAVES=" + std::to_string(r->coop_waves)};
     if (const char* rs = opt(r->ctx, "EMCEE_REC_STORE")) defs.push_back(std::string("MHX_EMCEE_REC_STORE=") + rs);
-    int rc = jit_compile(ctx, key, "#include \"mhx_emcee_mfma_kernels.h\"\n", defs, &m);
+    int rc = jit_compile(ctx, "#include \"mhx_emcee_mfma_kernels.h\"\n", defs, &m);
     if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_mfma_half", &r->jit_step);
     if (rc) { (void)hipFree(r->d_mfma_img); r->d_mfma_img = nullptr; r->jit_step = nullptr; return rc; }
-    const char* fz = opt(r->ctx, "EMCEE_FUSED");
     // (this form's sweep kernel pays up to 20 480 walkers at d = 50: 16 384 1.18 -> 1.48e9 moves/s, 20 480 1.31 -> 1.48e9, 24 576 1.53 ->
     // 1.48e9; further out for smaller dimensions -- d = 24: +16 % at 49 152, d = 10: +13 % at 65 536; d = 64: +11 % at 16 384, -9 % at 24 576)
-    if (fz ? atoi(fz) != 0 : (MHX_EMCEE_FUSED_DEFAULT != 0 && (long)r->n <= std::max(16384L, std::min(61440L, 21000L * 50 / std::max(d, 16)))))
+    if (opt_int(ctx, "EMCEE_FUSED", MHX_EMCEE_FUSED_DEFAULT != 0 && (long)r->n <= std::max(16384L, std::min(61440L, 21000L * 50 / std::max(d, 16)))) != 0)
         if (jit_function(m, "mhx_jit_emcee_mfma_sweep", &r->jit_sweep) != MHX_OK) r->jit_sweep = nullptr;
     // more than one wave per block: the waves share ONE fetch of the operand image through LDS (mhx_emcee_mfma_kernels.h)
     r->sweep_lds = r->coop_waves > 1 ? img.size() * sizeof(mhx_real) : 0;
-    if (r->sweep_lds > 65536) {
-        if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->sweep_lds) != hipSuccess ||
-            (r->jit_sweep && hipFuncSetAttribute((const void*)r->jit_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->sweep_lds) != hipSuccess))
-            return mhx_fail(MHX_EHIP, "matrix-core stretch move: %zu bytes of LDS refused", r->sweep_lds);
-    }
-    r->emcee_mfma = true;
+    for (hipFunction_t f : {r->jit_step, r->jit_sweep})
+        if (f && (rc = kernel_lds_limit((const void*)f, r->sweep_lds, "matrix-core stretch move"))) return rc;
     r->emcee_band = -1;
-    r->variant = 10;
+    r->variant = KF_EMCEE_MFMA;
     r->coop_L = 4;
     return MHX_OK;
 }
@@ -185,12 +178,11 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
     if (sequential) {
         // the reference's Gauss-Seidel sweep: one wavefront, run-time dimension, state in the ABI layout
         if (cfg->reduce_lanes > 1) return mhx_fail(MHX_EINVAL, "mhx_emcee_create: the sequential sweep runs on one lane group (reduce_lanes must be 0 or 1)");
-        r->variant = 7;
+        r->variant = KF_EMCEE_SEQ;
         r->coop_L = 1;
         if (t->kind == MHX_TARGET_USER) {
             jit_module* m = nullptr;
-            const std::string key = "emcee/d=0/tk=" + std::to_string(t->kind) + "/l=1/" + t->user_key;
-            rc = jit_compile(ctx, key, jit_source(t, "mhx_emcee_kernels.h"),
+            rc = jit_compile(ctx, jit_source(t, "mhx_emcee_kernels.h"),
                              {"MHX_JIT_EMCEE=1", "MHX_JIT_DIM=0", "MHX_JIT_TK=" + std::to_string(t->kind), "MHX_JIT_L=1"}, &m);
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_seq", &r->jit_step);
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_init", &r->jit_init);
@@ -203,7 +195,7 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
     const bool user = tk == MHX_TARGET_USER;
     const bool want_reg = !(r->flags & MHX_FLAG_GENERIC) && d <= MHX_EMCEE_REG_MAX_DIM &&
                           !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096);
-    r->variant = 0;
+    r->variant = KF_GENERIC;
     // lanes per walker: the cooperative kernel exists for the dense-Gaussian target with a compile-time dimension
     int L = 1;
     const bool can_coop = tk == MHX_TARGET_CORR_GAUSS && !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && d >= 2 && d <= MHX_DENSE_COOP_MAX_DIM;
@@ -226,38 +218,34 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
     // form, =NW (4, 8, 16) forces the scalar form with NW waves wherever a cooperative kernel would run (tuning / tests).
     const int band_bw = (tk == MHX_TARGET_CORR_GAUSS && !(r->flags & MHX_FLAG_DENSE_FACTOR) && t->bandwidth >= 0 &&
                          t->bandwidth <= MHX_EMCEE_MAX_BAND && t->bandwidth < d - 1) ? t->bandwidth : -1;
-    // ... or, while its operands fit a lane's registers, the matrix-core form (mhx_emcee_mfma_kernels.h, variant 10): 4 lanes per
+    // ... or, while its operands fit a lane's registers, the matrix-core form (mhx_emcee_mfma_kernels.h, KF_EMCEE_MFMA): 4 lanes per
     // walker, the candidate formed in the MFMA's B-operand layout, every lane's A operands fetched once per launch from an image
     // built here, once per run -- no LDS, no barrier.  Reduction shape 4.  MHX_EMCEE_MFMA=0 keeps the scalar-factor form (tuning).
     {
-        const char* mv = opt(ctx, "EMCEE_MFMA");
         // by default in fp64 from 12 288 walkers on: one wave carries the whole product of its 16 walkers (37 MFMAs of 66 cycles at
         // d = 50), which is the shorter chain only once the scalar-factor form's 8-cycle DPP products queue up behind each other
         // (rotated C3, moves/s against the scalar-factor form -- fp64: 4 096 walkers -6 %, 8 192 -14 %, 12 288 +24 %, 16 384 +16 %,
         // 32 768 +20 %, 65 536 +25 %, 262 144 +23 %; fp32, whose DPP product issues in 4 cycles: -5 ... -25 %: profiles/r04w_mfma_sizes.log)
         // Smaller dimensions: the chain is a few MFMAs and this form has no barrier -- d <= 32 in fp64 +10 ... +45 % at every size from
         // 2 048 to 16 384 walkers, d = 40 +-0 ... +6 %; fp32 d = 10 +5 ... +14 %, d = 24 +-0, d = 32 +5 / -8 % (tools/emcee_mfma_dims.sh)
-        const bool want = mv ? atoi(mv) != 0 : (MHX_EMCEE_MFMA_DEFAULT != 0 && (MHX_REAL64 ? (d <= 40 || r->n >= 12288) : d <= 16));
+        const bool want = opt_int(ctx, "EMCEE_MFMA", MHX_EMCEE_MFMA_DEFAULT != 0 && (MHX_REAL64 ? (d <= 40 || r->n >= 12288) : d <= 16)) != 0;
         if (want && can_coop && band_bw < 0 && d >= 8 && d <= (MHX_REAL64 ? 64 : 128) && (cfg->reduce_lanes == 0 || cfg->reduce_lanes == 4) &&
             !opt(ctx, "EMCEE_SCALAR")) {
             int rcm = emcee_create_mfma(r.get(), t, d);
             if (rcm == MHX_OK) {
-                if (r->variant == 10) {
-                    HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
-                    if (r->jit_sweep) {
-                        HIP_TRY(hipMalloc(&r->d_xw2, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
-                        HIP_TRY(hipMalloc(&r->d_lp2, NT * sizeof(mhx_real)));
-                    }
-                    return done();
+                HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
+                if (r->jit_sweep) {
+                    HIP_TRY(hipMalloc(&r->d_xw2, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
+                    HIP_TRY(hipMalloc(&r->d_lp2, NT * sizeof(mhx_real)));
                 }
-            } else if (cfg->reduce_lanes == 4 && mv) return rcm;
+                return done();
+            } else if (cfg->reduce_lanes == 4 && opt(ctx, "EMCEE_MFMA")) return rcm;
         }
     }
     bool scal = false;
     int scal_mode = 1;
     {
-        const char* sv = opt(ctx, "EMCEE_SCALAR");
-        const int forced = sv ? atoi(sv) : -1;
+        const int forced = opt_int(ctx, "EMCEE_SCALAR", -1);
         const int xp = (d + 3) & ~3, b4 = (int)(sizeof(mhx_real) / 4);
         // registers of a lane in phase 2: the walker's candidate, plus (broadcast form) this wave's pieces of the factor
         auto pieces = [&](int nw) { int p = 0; for (int m = 0; nw * m < d; ++m) p += (std::min(nw * m + nw - 1, d - 1)) / 16 + 1; return p; };
@@ -268,8 +256,7 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
             else if (cfg->reduce_lanes == 0) nw = 8;
             else if (forced > 0 && (cfg->reduce_lanes == 4 || cfg->reduce_lanes == 8 || cfg->reduce_lanes == 16)) nw = cfg->reduce_lanes;
             if (nw && nw <= d) {
-                const char* sm = opt(ctx, "EMCEE_SCAL_MODE");       // tuning knob
-                scal_mode = sm ? (atoi(sm) ? 1 : 0) : (fits(nw, 1) ? 1 : 0);
+                scal_mode = opt_int(ctx, "EMCEE_SCAL_MODE", fits(nw, 1)) ? 1 : 0;       // tuning knob
                 if (fits(nw, scal_mode) || forced > 0) { scal = true; L = nw; }
             }
         }
@@ -277,28 +264,18 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
     if (user || L > 1 || (want_reg && !(r->flags & MHX_FLAG_NO_JIT))) {
         const int jd = (L > 1 || (want_reg && !(r->flags & MHX_FLAG_NO_JIT))) ? d : 0;
         jit_module* m = nullptr;
-        // timing probe (tools/emcee_probe.sh): MHX_EMCEE_PROBE=n ends the cooperative half-step after its n-th phase -- wrong
-        // chains, right latencies
-        const char* probe = MHX_PROBE_OPT(ctx, "EMCEE_PROBE");
         // a banded precision factor (exact zeros below the band): the cooperative kernel's band form -- no factor image in LDS,
         // no block barrier, BW + 1 products per row.  MHX_FLAG_DENSE_FACTOR keeps the dense form.
         const int bw = L > 1 ? band_bw : -1;
         r->emcee_band = bw;
-        const std::string key = "emcee/d=" + std::to_string(jd) + "/tk=" + std::to_string(tk) + "/l=" + std::to_string(L) +
-                                "/bw=" + std::to_string(bw) + (scal ? std::string("/scal") + (opt(ctx, "EMCEE_SCAL_WPB") ? opt(ctx, "EMCEE_SCAL_WPB") : ((r->n / 2 + 63) / 64 >= 512 ? "64" : "32")) +
-                                                                       (scal_mode ? "m1" : "m0") + (opt(ctx, "EMCEE_SCAL_REC") ? std::string("r") + opt(ctx, "EMCEE_SCAL_REC") : std::string()) +
-                                                                       (MHX_PROBE_OPT(ctx, "EMCEE_STAMPS") ? "/stamps" : "") : std::string()) +
-                                "/" + t->user_key + (probe ? std::string("/probe=") + probe : std::string()) +
-                                (opt(ctx, "EMCEE_WAVES") ? std::string("/w=") + opt(ctx, "EMCEE_WAVES") : std::string()) +
-                                (opt(ctx, "EMCEE_REC_STORE") ? std::string("/rs=") + opt(ctx, "EMCEE_REC_STORE") : std::string()) +
-                                (opt(ctx, "EMCEE_ROW_STORE") ? std::string("/ws=") + opt(ctx, "EMCEE_ROW_STORE") : std::string()) +
-                                (opt(ctx, "EMCEE_COOP_REC") ? std::string("/cr=") + opt(ctx, "EMCEE_COOP_REC") : std::string());
         std::vector<std::string> defs = {"MHX_JIT_EMCEE=1", "MHX_JIT_DIM=" + std::to_string(jd), "MHX_JIT_TK=" + std::to_string(tk),
                                          "MHX_JIT_L=" + std::to_string(L)};
         if (const char* rs = opt(ctx, "EMCEE_REC_STORE")) defs.push_back(std::string("MHX_EMCEE_REC_STORE=") + rs);   // tuning knob
         if (const char* rs = opt(ctx, "EMCEE_ROW_STORE")) defs.push_back(std::string("MHX_EMCEE_ROW_STORE=") + rs);   // tuning knob
 #ifdef MHX_TOOLS_BUILD
-        if (probe) {
+        // timing probe (tools/emcee_probe.sh): MHX_EMCEE_PROBE=n ends the cooperative half-step after its n-th phase -- wrong
+        // chains, right latencies
+        if (const char* probe = opt(ctx, "EMCEE_PROBE")) {
             defs.push_back(std::string("MHX_EMCEE_PROBE=") + probe);
             fprintf(stderr, "mhx (tools build): EMCEE_PROBE=%s -- timing probe: the half-step ends early, this run's chains are NOT valid (stats.tainted = 1)\n", probe);
         }
@@ -307,8 +284,7 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
             defs.push_back("MHX_JIT_SCAL=1");
             // walkers per block: 64 fill the lanes of phase 2 (the throughput shape: large ensembles), 32 spread a latency-bound
             // half-step over twice the CUs (C3: 8192 moving walkers = 256 blocks, one per CU; 6.4 against 7.4 us in fp64)
-            const char* wpb = opt(ctx, "EMCEE_SCAL_WPB");               // tuning knob: 64, 32, 16
-            r->emcee_wpb = wpb ? atoi(wpb) : ((r->n / 2 + 63) / 64 >= 512 ? 64 : 32);
+            r->emcee_wpb = opt_int(ctx, "EMCEE_SCAL_WPB", (r->n / 2 + 63) / 64 >= 512 ? 64 : 32);      // tuning knob: 64, 32, 16
             if (r->emcee_wpb != 16 && r->emcee_wpb != 32) r->emcee_wpb = 64;
             defs.push_back("MHX_EMCEE_SCAL_WPB=" + std::to_string(r->emcee_wpb));
 #ifdef MHX_TOOLS_BUILD
@@ -338,93 +314,74 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
         // thread count is a compile-time launch bound (the registers of a lane: 512 / waves per SIMD)
         int persist_threads = 0;
         {
-            const char* pz = opt(ctx, "EMCEE_PERSIST");
             const int threads = ((r->n + 63) / 64) * 64;
             const int regs = (int)(sizeof(mhx_real) / 4) * 2 * ((jd + 3) & ~3) + 48;         // walker + candidate + the rest, per lane
             const size_t lds = (size_t)r->n * (size_t)(((jd + 3) & ~3) + 1) * sizeof(mhx_real);
-            if (!scal && L == 1 && jd > 0 && r->n <= 1024 && (pz ? atoi(pz) != 0 : true) && lds <= MHX_LDS_PER_BLOCK &&
+            if (!scal && L == 1 && jd > 0 && r->n <= 1024 && opt_int(ctx, "EMCEE_PERSIST", 1) != 0 && lds <= MHX_LDS_PER_BLOCK &&
                 regs <= 512 / ((threads / 64 + 3) / 4)) {
                 persist_threads = threads;
                 defs.push_back("MHX_JIT_PERSIST_THREADS=" + std::to_string(threads));
             }
         }
         // kernarg preload of the half-step's hot arguments (mhx_jit_emcee_half, MHX_JIT_PRELOAD); MHX_EMCEE_PRELOAD=0|1 tuning knob
-        const char* plv = opt(ctx, "EMCEE_PRELOAD");
-        r->emcee_preload = plv ? atoi(plv) != 0 : MHX_EMCEE_PRELOAD_DEFAULT != 0;
+        r->emcee_preload = opt_int(ctx, "EMCEE_PRELOAD", MHX_EMCEE_PRELOAD_DEFAULT) != 0;
         std::vector<std::string> xopts;
         if (L == 1) xopts = {"-mllvm", "-amdgpu-unroll-threshold-private=100000"};   // a user's loop over the candidate unrolls whatever it costs (see rwmh_create)
         if (r->emcee_preload) {
             defs.push_back("MHX_JIT_PRELOAD=1");
             xopts.push_back("-mllvm"); xopts.push_back("-amdgpu-kernarg-preload-count=9");
         }
-        rc = jit_compile(ctx, key + (r->emcee_preload ? "/pl" : "") + (persist_threads ? "/pt=" + std::to_string(persist_threads) : std::string()),
-                         jit_source(t, "mhx_emcee_kernels.h"), defs, &m, xopts);
+        rc = jit_compile(ctx, jit_source(t, "mhx_emcee_kernels.h"), defs, &m, xopts);
         if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_half", &r->jit_step);
         if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_init", &r->jit_init);
+        const int xp = (d + 3) & ~3, u = 16 / (int)sizeof(mhx_real), ys = ((xp / u) | 1) * u;      // mhx_emcee_sgeom::YS
         if (rc == MHX_OK && scal) {
-            const int xp = (d + 3) & ~3, u = 16 / (int)sizeof(mhx_real);
-            const int ys = ((xp / u) | 1) * u;                           // mhx_emcee_sgeom::YS
             r->dense_lds = (size_t)(r->emcee_wpb * ys + L * 64) * sizeof(mhx_real);
-            r->emcee_scal = true;
-            if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->dense_lds) != hipSuccess)
-                rc = mhx_fail(MHX_EHIP, "scalar-factor stretch move: %zu bytes of LDS refused", r->dense_lds);
+            rc = kernel_lds_limit((const void*)r->jit_step, r->dense_lds, "scalar-factor stretch move");
         } else if (rc == MHX_OK && L > 1) {
             if (dense_coop_lds_bytes(d, L, 1, r->coop_waves) > MHX_LDS_PER_BLOCK) rc = mhx_fail(MHX_EINVAL, "emcee: the factor image of dim %d with %d lanes per walker exceeds the LDS", d, L);
             else {
                 r->dense_lds = dense_coop_lds_bytes(d, L, 1, r->coop_waves);
-                if (hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->dense_lds) != hipSuccess)
-                    rc = mhx_fail(MHX_EHIP, "cooperative stretch move: %zu bytes of LDS refused", r->dense_lds);
+                rc = kernel_lds_limit((const void*)r->jit_step, r->dense_lds, "cooperative stretch move");
             }
         }
         // one launch per sweep (mhx_emcee_coop_sweep_body): the lane-group form with three candidate rows per walker in LDS.  By
         // default for a banded factor only: with the dense image the second half's three full row products cost more than the
         // launch they save (rotated C3: 16.2 us per sweep against 2 x 7.1); MHX_EMCEE_FUSED=0|1 forces it off / on (tuning knob)
-        const char* fz = opt(ctx, "EMCEE_FUSED");
         const bool fused_size = MHX_EMCEE_FUSED_DEFAULT != 0 && r->n <= MHX_EMCEE_FUSED_MAX_W;
         // (the lane-group form's launch fills the machine later the smaller the dimension: one launch against two at d = 10 / 24 is
         // +25 % / +28 % at 32 768 walkers, +18 % / +13 % at 49 152, -1 % / -7 % at 65 536 -- profiles/r04u_fused_sizes.log)
         const bool fused_size_band = MHX_EMCEE_FUSED_DEFAULT != 0 && (long)r->n <= std::min(61440L, (long)MHX_EMCEE_FUSED_MAX_W * 50 / std::max(d, 20));
-        if (rc == MHX_OK && !scal && L > 1 && (fz ? atoi(fz) != 0 : (fused_size_band && bw >= 0))) {
+        // (a sweep kernel that is missing, or refused its LDS, is done without: the half-step launches stay)
+        auto try_sweep = [&](size_t lds) {
+            r->sweep_lds = lds;
+            if (lds > MHX_LDS_PER_BLOCK || jit_kernel(m, "mhx_jit_emcee_sweep", &r->jit_sweep, lds, "stretch move sweep") != MHX_OK) r->jit_sweep = nullptr;
+        };
+        if (rc == MHX_OK && !scal && L > 1 && opt_int(ctx, "EMCEE_FUSED", fused_size_band && bw >= 0) != 0) {
             const size_t rows = (size_t)r->coop_waves * (64 / L) * (size_t)(((d + 3) & ~3) + 4) * sizeof(mhx_real);
-            const size_t lds = r->dense_lds + 2 * rows;
-            if (lds <= MHX_LDS_PER_BLOCK && jit_function(m, "mhx_jit_emcee_sweep", &r->jit_sweep) == MHX_OK) {
-                r->sweep_lds = lds;
-                if (hipFuncSetAttribute((const void*)r->jit_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) r->jit_sweep = nullptr;
-            } else r->jit_sweep = nullptr;
+            try_sweep(r->dense_lds + 2 * rows);
         }
         // ... and the scalar-factor form (mhx_emcee_scal_sweep_body; DPP operand mode, the latency shape of <= 32 walkers per block)
-        if (rc == MHX_OK && scal && scal_mode == 1 && r->emcee_wpb == 32 && L >= 2 && (fz ? atoi(fz) != 0 : fused_size)) {
-            const int xp = (d + 3) & ~3, u = 16 / (int)sizeof(mhx_real);
-            const int ys = ((xp / u) | 1) * u;
-            const size_t lds = (size_t)(2 * r->emcee_wpb * ys + L * 64 + 2 * r->emcee_wpb) * sizeof(mhx_real);
-            if (lds <= MHX_LDS_PER_BLOCK && jit_function(m, "mhx_jit_emcee_sweep", &r->jit_sweep) == MHX_OK) {
-                r->sweep_lds = lds;
-                if (hipFuncSetAttribute((const void*)r->jit_sweep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) r->jit_sweep = nullptr;
-            } else r->jit_sweep = nullptr;
-        }
+        if (rc == MHX_OK && scal && scal_mode == 1 && r->emcee_wpb == 32 && L >= 2 && opt_int(ctx, "EMCEE_FUSED", fused_size) != 0)
+            try_sweep((size_t)(2 * r->emcee_wpb * ys + L * 64 + 2 * r->emcee_wpb) * sizeof(mhx_real));
         // ... and the lane-per-walker register kernel (any target: the second half evaluates the log-density twice)
-        if (rc == MHX_OK && !scal && L == 1 && jd > 0 && jd <= MHX_EMCEE_REG_SWEEP_MAX_DIM && (fz ? atoi(fz) != 0 : fused_size)) {
-            if (jit_function(m, "mhx_jit_emcee_sweep", &r->jit_sweep) != MHX_OK) r->jit_sweep = nullptr;
-            r->sweep_lds = 0;
-        }
+        if (rc == MHX_OK && !scal && L == 1 && jd > 0 && jd <= MHX_EMCEE_REG_SWEEP_MAX_DIM && opt_int(ctx, "EMCEE_FUSED", fused_size) != 0)
+            try_sweep(0);
         // ... and, for an ensemble of at most 1024 walkers whose rows fit the LDS of one block, the whole call in ONE launch of one
-        // persistent block (mhx_emcee_persist_body, variant 6); MHX_EMCEE_PERSIST=0 keeps the sweep launches (tuning knob).  The 64 KB
+        // persistent block (mhx_emcee_persist_body, KF_EMCEE_PERSIST); MHX_EMCEE_PERSIST=0 keeps the sweep launches (tuning knob).  The 64 KB
         // of registers a 1024-thread block leaves each lane hold the walker and its candidate up to d = 24 in fp64 (48 in fp32)
         bool persist = false;
-        if (rc == MHX_OK && persist_threads > 0 && jit_function(m, "mhx_jit_emcee_persist", &r->jit_persist) == MHX_OK) {
-            r->persist_lds = (size_t)r->n * (size_t)(((jd + 3) & ~3) + 1) * sizeof(mhx_real);
-            if (r->persist_lds > 65536 &&
-                hipFuncSetAttribute((const void*)r->jit_persist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->persist_lds) != hipSuccess)
-                r->jit_persist = nullptr;
-            persist = r->jit_persist != nullptr;
-        } else r->jit_persist = nullptr;
-        if (rc == MHX_OK) { r->variant = scal ? 9 : (L > 1 ? 4 : (jd > 0 ? (persist ? 6 : 2) : 0)); r->coop_L = L; }
+        r->persist_lds = (size_t)r->n * (size_t)(((jd + 3) & ~3) + 1) * sizeof(mhx_real);
+        if (rc == MHX_OK && persist_threads > 0 && jit_kernel(m, "mhx_jit_emcee_persist", &r->jit_persist, r->persist_lds, "persistent-block ensemble") == MHX_OK)
+            persist = true;
+        else r->jit_persist = nullptr;
+        if (rc == MHX_OK) { r->variant = scal ? KF_EMCEE_SCAL : (L > 1 ? KF_COOP_JIT : (jd > 0 ? (persist ? KF_EMCEE_PERSIST : KF_REG_JIT) : KF_GENERIC)); r->coop_L = L; }
         else if (user || cfg->reduce_lanes > 1) return rc;
         else { r->jit_step = nullptr; r->jit_init = nullptr; r->coop_L = 1; }
     }
-    if (r->variant == 0) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * NT * sizeof(mhx_real)));
+    if (r->variant == KF_GENERIC) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * NT * sizeof(mhx_real)));
     // the compile-time-dimension kernels (cooperative, register) keep the walkers walker-major
-    if (r->variant == 4 || r->variant == 2 || r->variant == 9 || r->variant == 6) HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
+    if (r->variant == KF_COOP_JIT || r->variant == KF_REG_JIT || r->variant == KF_EMCEE_SCAL || r->variant == KF_EMCEE_PERSIST) HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
     if (r->jit_sweep) {
         HIP_TRY(hipMalloc(&r->d_xw2, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
         HIP_TRY(hipMalloc(&r->d_lp2, NT * sizeof(mhx_real)));
@@ -468,9 +425,9 @@ static int emcee_launch_half(mhx_run* r, mhx_emcee_args a, int h, int begin, int
     a.t_count = count;
     if (count <= 0) return MHX_OK;
     const bool coop = r->coop_L > 1;
-    const int per_block = r->emcee_scal ? r->emcee_wpb : (64 / r->coop_L) * (coop ? r->coop_waves : 1);      // walkers per block
+    const int per_block = r->variant == KF_EMCEE_SCAL ? r->emcee_wpb : (64 / r->coop_L) * (coop ? r->coop_waves : 1);      // walkers per block
     const unsigned grid = (unsigned)((count + per_block - 1) / per_block), E = (unsigned)r->n_ens;
-    if (r->emcee_mfma) {
+    if (r->variant == KF_EMCEE_MFMA) {
         const mhx_real* img = r->d_mfma_img;
         void* params[] = {&a, &img};
         HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, E, 1, 64 * r->coop_waves, 1, 1, (unsigned)r->sweep_lds, ctx->stream, params, nullptr));
@@ -512,7 +469,7 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
 {
     const int W = r->ens_w, halfW = W / 2;
     const unsigned E = (unsigned)r->n_ens;                   // ensembles: the second grid dimension of every launch
-    if (r->variant == 7) {                                   // the reference's sequential sweep: one launch, one wave per ensemble
+    if (r->variant == KF_EMCEE_SEQ) {                        // the reference's sequential sweep: one launch, one wave per ensemble
         mhx_emcee_args a = emcee_args(r);
         a.sweep = (uint32_t)(r->tau + 1);
         a.nsweeps = (int)nsteps;
@@ -531,7 +488,7 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
         r->tau += nsteps;
         return MHX_OK;
     }
-    if (r->variant == 6 && r->jit_persist && !opt(r->ctx, "EMCEE_DEFER")) {      // a small ensemble: the whole call in one persistent block
+    if (r->variant == KF_EMCEE_PERSIST && r->jit_persist && !opt(r->ctx, "EMCEE_DEFER")) {      // a small ensemble: the whole call in one persistent block
         uint64_t done = 0;
         while (done < nsteps) {
             const uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
@@ -564,14 +521,12 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
     // first launch of sweep k + 1 writes the record of half B of sweep k; these stores leave at the START of a launch, off
     // its critical path, where the launch that moved the half would have had to wait for them at its end.  What is still
     // owed when the call ends (half B of the last recorded sweep) is written by k_emcee_record_half.
-    const char* dfe = opt(r->ctx, "EMCEE_DEFER");                      // tuning knob
-    const bool deferred = E == 1 && r->variant == 4 && (dfe ? atoi(dfe) != 0 : MHX_EMCEE_DEFER_DEFAULT);      // (tuning experiments: one ensemble only)
+    const bool deferred = E == 1 && r->variant == KF_COOP_JIT && opt_int(r->ctx, "EMCEE_DEFER", MHX_EMCEE_DEFER_DEFAULT) != 0;      // (tuning knob; one ensemble only)
     long owed_b = -1;                                        // slot whose half B has not been recorded yet
     // MHX_EMCEE_SWEEP_DEFER=1 (tuning knob, off): sweep launches of the lane-group form record a sweep at the top of the NEXT launch, from
     // the rows every group loads anyway (mhx_emcee_coop_sweep_body) -- measured SLOWER, 8.34 against 7.60 us per sweep on one box: 6.7 MB
     // of stores at the head of the launch sit in front of the row loads the whole chain waits for
-    const char* sde = opt(r->ctx, "EMCEE_SWEEP_DEFER");
-    const bool sweep_defer = E == 1 && r->jit_sweep && r->variant == 4 && sde && atoi(sde) != 0;
+    const bool sweep_defer = E == 1 && r->jit_sweep && r->variant == KF_COOP_JIT && opt_on(r->ctx, "EMCEE_SWEEP_DEFER");
     for (uint64_t s = 0; s < nsteps; ++s) {
         mhx_emcee_args a = emcee_args(r);
         a.sweep = (uint32_t)(r->tau + 1);
@@ -591,11 +546,11 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
             }
             a.all_rows = s == 0 ? 1 : 0;                     // the other buffer holds nothing of this state yet
             // lane-group form: blocks of one half each, the second half's first; scalar-factor form: mixed blocks, wpb / 2 walkers of each half
-            const bool coop = r->emcee_scal || r->coop_L > 1;
-            const int per_block = r->emcee_scal ? r->emcee_wpb / 2 : (coop ? (64 / r->coop_L) * r->coop_waves : 64);
-            const unsigned grid = r->emcee_scal ? (unsigned)((W - halfW + per_block - 1) / per_block)
+            const bool scal = r->variant == KF_EMCEE_SCAL, coop = scal || r->coop_L > 1;
+            const int per_block = scal ? r->emcee_wpb / 2 : (coop ? (64 / r->coop_L) * r->coop_waves : 64);
+            const unsigned grid = scal ? (unsigned)((W - halfW + per_block - 1) / per_block)
                                                 : (unsigned)((halfW + per_block - 1) / per_block + (W - halfW + per_block - 1) / per_block);
-            const mhx_real* tp = r->emcee_mfma ? r->d_mfma_img : r->target->dparams;
+            const mhx_real* tp = r->variant == KF_EMCEE_MFMA ? r->d_mfma_img : r->target->dparams;
             void* params[] = {&a, &tp};
             HIP_TRY(hipModuleLaunchKernel(r->jit_sweep, grid, E, 1, coop ? 64 * r->coop_waves : 64, 1, 1, (unsigned)r->sweep_lds, r->ctx->stream, params, nullptr));
             std::swap(r->d_xw, r->d_xw2);
@@ -650,7 +605,7 @@ int api_emcee_half_step(mhx_run* r, int half, int begin, int count)
     if (!r->initialised) return mhx_fail(MHX_ESTATE, "mhx_emcee_half_step: run is not initialised");
     const int W = r->n, halfW = W / 2, cnt = half ? W - halfW : halfW;
     if (r->n_ens > 1) return mhx_fail(MHX_EINVAL, "mhx_emcee_half_step: a run of %d ensembles is not ONE ensemble to shard", r->n_ens);
-    if (r->variant == 7) return mhx_fail(MHX_EINVAL, "mhx_emcee_half_step: the sequential sweep has no halves");
+    if (r->variant == KF_EMCEE_SEQ) return mhx_fail(MHX_EINVAL, "mhx_emcee_half_step: the sequential sweep has no halves");
     if ((half != 0 && half != 1) || begin < 0 || count < 0 || begin + count > cnt)
         return mhx_fail(MHX_EINVAL, "mhx_emcee_half_step: slice [%d, %d) is outside half %d of %d walkers", begin, begin + count, half, cnt);
     HIP_TRY(hipSetDevice(r->ctx->device));

@@ -142,12 +142,9 @@ static int compact_setup(mhx_ctx* ctx)
         HIP_TRY(hipEventCreateWithFlags(&P.scattered, hipEventDisableTiming));
     }
     if (!ctx->hdr_pinned) HIP_TRY(hipHostMalloc((void**)&ctx->hdr_pinned, 3 * sizeof(mhx_compact_hdr), hipHostMallocDefault));
-    const char* ot = opt(ctx, "HOST_THREADS");
-    const char* oc = opt(ctx, "HOST_CHUNK");
-    const char* on = opt(ctx, "HOST_NUMA");
-    const int want_t = ot ? atoi(ot) : 0, want_c = oc ? atoi(oc) : 0;
+    const int want_t = opt_int(ctx, "HOST_THREADS", 0), want_c = opt_int(ctx, "HOST_CHUNK", 0);
     int want_n = -1;
-    if (!on || atoi(on) != 0) {                      // HOST_NUMA = 0: no placement (A/B)
+    if (opt_int(ctx, "HOST_NUMA", 1) != 0) {                      // HOST_NUMA = 0: no placement (A/B)
         char bus[32] = {0};
         if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, ctx->device) == hipSuccess) want_n = mhx_numa_node_of_pci(bus);
         else (void)hipGetLastError();
@@ -249,8 +246,7 @@ int api_run_sample_to_host(mhx_run* r, const mhx_schedule* s, mhx_real* host_sam
     K = std::min(K, N);
     // the accept-compacted form (include/mhx.h): context option HOST_COMPACT = 1 / 0, else when rows repeat (thinning == 1) and there
     // are chains enough for the host threads to share
-    const char* oc = opt(ctx, "HOST_COMPACT");
-    const bool compact = oc ? atoi(oc) != 0 : (s->thinning == 1 && r->n >= 1024);
+    const bool compact = opt_int(ctx, "HOST_COMPACT", s->thinning == 1 && r->n >= 1024) != 0;
     if (compact) {
         K = std::min<size_t>(K, (size_t)0xffffffffull / n);                     // a block's ranks are 32-bit
         rc = compact_setup(ctx);

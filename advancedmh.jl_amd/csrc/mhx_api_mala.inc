@@ -32,6 +32,27 @@ static mhx_mala_args mala_args(const mhx_run* r)
     return a;
 }
 
+// the matrix-core MALA kernels that stream their operands: the images of A and of A^T, side by side in global memory, built by
+// the module's own fill kernels
+static int mala_mfma_images(mhx_run* r, jit_module* m)
+{
+    hipFunction_t fimg = nullptr, fimgT = nullptr;
+    int rc = jit_function(m, "mhx_jit_mfma_image", &fimg);
+    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image_T", &fimgT);
+    if (rc) return rc;
+    const size_t ra = mfma_image_reals(r->dim), rt = mfma_image_reals_T(r->dim);
+    HIP_TRY(hipMalloc(&r->d_mfma_img, (ra + rt) * sizeof(mhx_real)));
+    const mhx_real* src = r->target->dparams;
+    mhx_real* dst = r->d_mfma_img;
+    void* pa[] = {(void*)&src, &dst};
+    rc = launch_module(fimg, 1, 256, r->ctx->stream, pa);
+    mhx_real* dstT = r->d_mfma_img + ra;
+    void* pt[] = {(void*)&src, &dstT};
+    if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, r->ctx->stream, pt);
+    if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(r->ctx->stream));
+    return rc;
+}
+
 int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, mhx_run** out)
 {
     if (!ctx || !t || !cfg || !out) return mhx_fail(MHX_EINVAL, "mhx_mala_create: NULL argument");
@@ -59,7 +80,7 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
     const bool split = t->kind != MHX_TARGET_CORR_GAUSS && r->dim > regmax && r->dim <= MHX_MALA_SPLIT_MAX_DIM;
     const bool want_reg = !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && (r->dim <= regmax || split) &&
                           !(t->kind == MHX_TARGET_IID_NORMAL && t->nparams > 4096);
-    r->variant = 0;
+    r->variant = KF_GENERIC;
     // MHX_FLAG_ZIGGURAT (round 5): the noise by the table ziggurat -- the lane-per-chain register kernel's form (both widths, any target
     // with a gradient, d within that kernel's reach); the cooperative / matrix-core / state-in-HBM kernels draw Box-Muller
     const bool zig = (cfg->flags & MHX_FLAG_ZIGGURAT) != 0;
@@ -73,11 +94,11 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
     // with the ONE factor all chains share; reduction shape 4.  Asked for (reduce_lanes = 4), or by default above the
     // register kernel's budget, wherever both operand images fit LDS
     const size_t mfma_lds = (mfma_image_reals(r->dim) + mfma_image_reals_T(r->dim)) * sizeof(mhx_real);
-    const char* no_mfma = opt(ctx, "NO_MFMA");                                    // tuning knob
+    const bool no_mfma = opt_on(ctx, "NO_MFMA");                                  // tuning knob
     const bool mfma = t->kind == MHX_TARGET_CORR_GAUSS && !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && r->dim >= 16 &&
                       !zig && (cfg->reduce_lanes == 4 || (cfg->reduce_lanes == 0 && r->dim > regmax)) && mfma_lds <= MHX_LDS_PER_BLOCK &&
                       ((uint64_t)r->dim + 1) * (uint64_t)r->n * sizeof(mhx_real) < (1ull << 32) &&      // 32-bit slab offsets
-                      !(no_mfma && atoi(no_mfma));
+                      !no_mfma;
     // ... and where they do not: both images in global memory, walked through an LDS ring; x and grad(x) re-read from their slabs
     // (candidate, noise, w and the candidate's gradient are what a lane keeps: 4 ceil(d/4) reals)
     const int mNS = (r->dim + 3) / 4, mNT = (r->dim + 15) / 16;
@@ -89,7 +110,7 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
     const bool mfma_s = !mfma && t->kind == MHX_TARGET_CORR_GAUSS && !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && r->dim >= 16 &&
                         (cfg->reduce_lanes == 4 || (cfg->reduce_lanes == 0 && r->dim > regmax)) && mNS <= (MHX_REAL64 ? 50 : 100) &&
                         mala_ring <= MHX_LDS_PER_BLOCK && ((uint64_t)r->dim + 1) * (uint64_t)r->n * sizeof(mhx_real) < (1ull << 32) &&
-                        !(no_mfma && atoi(no_mfma));
+                        !no_mfma;
     // ... and past that (fp64 d = 201 ... 512, fp32 d = 401 ... 1000): the LEAN form -- one vector per lane, A y and A^T w in place,
     // the noise through the z slab, one tile (or a pair, while the ring holds it) per chunk
     const size_t lean_pair_ring = std::max(mfma_ring_bytes(r->dim, true), ringT);
@@ -98,63 +119,21 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
     const bool mfma_l = !mfma && !mfma_s && t->kind == MHX_TARGET_CORR_GAUSS && !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && r->dim >= 16 &&
                         (cfg->reduce_lanes == 4 || (cfg->reduce_lanes == 0 && r->dim > regmax)) && mNS <= (MHX_REAL64 ? 128 : 250) &&
                         lean_ring <= MHX_LDS_PER_BLOCK && ((uint64_t)r->dim + 1) * (uint64_t)r->n * sizeof(mhx_real) < (1ull << 32) &&
-                        !(no_mfma && atoi(no_mfma));
+                        !no_mfma;
     if (cfg->reduce_lanes > 1 && !mfma && !mfma_s && !mfma_l && (!separable || (r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT))))
         return mhx_fail(MHX_EINVAL, "mhx_mala_create: reduce_lanes > 1 needs a separable catalogue target (iso-Gaussian, banana, funnel) "
                                 "or the dense Gaussian target with reduce_lanes = 4 (16 <= dim, both factor images within LDS), and JIT");
-    if (mfma_s) {
+    if (mfma_s || mfma_l) {
+        // the streamed form and the lean form: one shape on the host -- the step kernel and its ring, the two images
         jit_module* m = nullptr;
-        const std::string key = "mala_mfma_stream/d=" + std::to_string(r->dim);
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_mala_mfma_kernels.h"),
-                         {"MHX_JIT_MALA_MFMA_STREAM=1", "MHX_JIT_DIM=" + std::to_string(r->dim)}, &m,
-                         {"-mllvm", "-pragma-unroll-threshold=4000000"});
-        hipFunction_t fimg = nullptr, fimgT = nullptr;
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mala_mfma_stream", &r->jit_step);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image", &fimg);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image_T", &fimgT);
-        if (rc == MHX_OK && hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mala_ring) != hipSuccess)
-            rc = mhx_fail(MHX_EHIP, "streamed matrix-core MALA kernel: %zu bytes of LDS refused", mala_ring);
-        if (rc == MHX_OK) {
-            const size_t ra = mfma_image_reals(r->dim), rt = mfma_image_reals_T(r->dim);
-            HIP_TRY(hipMalloc(&r->d_mfma_img, (ra + rt) * sizeof(mhx_real)));
-            const mhx_real* src = t->dparams;
-            mhx_real* dst = r->d_mfma_img;
-            void* pa[] = {(void*)&src, &dst};
-            rc = launch_module(fimg, 1, 256, ctx->stream, pa);
-            mhx_real* dstT = r->d_mfma_img + ra;
-            void* pt[] = {(void*)&src, &dstT};
-            if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, ctx->stream, pt);
-            if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        if (rc == MHX_OK) { r->variant = 8; r->coop_L = 4; r->dense_lds = mala_ring; r->mfma_stream = true; }
-        else if (cfg->reduce_lanes > 1) return rc;
-        else r->jit_step = nullptr;
-    }
-    if (mfma_l) {
-        jit_module* m = nullptr;
-        const std::string key = "mala_mfma_lean/d=" + std::to_string(r->dim) + "/pair=" + std::to_string(lean_pair ? 1 : 0);
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_mala_mfma_kernels.h"),
-                         {"MHX_JIT_MALA_MFMA_LEAN=1", "MHX_JIT_DIM=" + std::to_string(r->dim), std::string("MHX_JIT_PAIR=") + (lean_pair ? "1" : "0")}, &m,
-                         {"-mllvm", "-pragma-unroll-threshold=4000000"});
-        hipFunction_t fimg = nullptr, fimgT = nullptr;
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mala_mfma_lean", &r->jit_step);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image", &fimg);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image_T", &fimgT);
-        if (rc == MHX_OK && hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lean_ring) != hipSuccess)
-            rc = mhx_fail(MHX_EHIP, "lean matrix-core MALA kernel: %zu bytes of LDS refused", lean_ring);
-        if (rc == MHX_OK) {
-            const size_t ra = mfma_image_reals(r->dim), rt = mfma_image_reals_T(r->dim);
-            HIP_TRY(hipMalloc(&r->d_mfma_img, (ra + rt) * sizeof(mhx_real)));
-            const mhx_real* src = t->dparams;
-            mhx_real* dst = r->d_mfma_img;
-            void* pa[] = {(void*)&src, &dst};
-            rc = launch_module(fimg, 1, 256, ctx->stream, pa);
-            mhx_real* dstT = r->d_mfma_img + ra;
-            void* pt[] = {(void*)&src, &dstT};
-            if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, ctx->stream, pt);
-            if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        if (rc == MHX_OK) { r->variant = 8; r->coop_L = 4; r->dense_lds = lean_ring; r->mfma_stream = true; }
+        std::vector<std::string> defs = {mfma_s ? "MHX_JIT_MALA_MFMA_STREAM=1" : "MHX_JIT_MALA_MFMA_LEAN=1", "MHX_JIT_DIM=" + std::to_string(r->dim)};
+        if (mfma_l) defs.push_back(std::string("MHX_JIT_PAIR=") + (lean_pair ? "1" : "0"));
+        r->dense_lds = mfma_s ? mala_ring : lean_ring;
+        rc = jit_compile(ctx, jit_source(t, "mhx_mala_mfma_kernels.h"), defs, &m, {"-mllvm", "-pragma-unroll-threshold=4000000"});
+        if (rc == MHX_OK) rc = jit_kernel(m, mfma_s ? "mhx_jit_mala_mfma_stream" : "mhx_jit_mala_mfma_lean", &r->jit_step, r->dense_lds,
+                                          mfma_s ? "streamed matrix-core MALA kernel" : "lean matrix-core MALA kernel");
+        if (rc == MHX_OK) rc = mala_mfma_images(r.get(), m);
+        if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->mfma_stream = true; }
         else if (cfg->reduce_lanes > 1) return rc;
         else r->jit_step = nullptr;
     }
@@ -163,13 +142,10 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
         const int NS = (r->dim + 3) / 4;
         const char* wenv = opt(ctx, "MFMA_WAVES");
         const int waves = wenv ? std::max(1, atoi(wenv)) : (MHX_REAL64 ? 1 : (NS <= 16 ? 2 : 1));
-        const std::string key = "mala_mfma/d=" + std::to_string(r->dim) + "/w=" + std::to_string(waves);
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_mala_mfma_kernels.h"),
+        rc = jit_compile(ctx, jit_source(t, "mhx_mala_mfma_kernels.h"),
                          {"MHX_JIT_MALA_MFMA=1", "MHX_JIT_DIM=" + std::to_string(r->dim), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mala_mfma", &r->jit_step);
-        if (rc == MHX_OK && hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mfma_lds) != hipSuccess)
-            rc = mhx_fail(MHX_EHIP, "matrix-core MALA kernel: %zu bytes of LDS refused", mfma_lds);
-        if (rc == MHX_OK) { r->variant = 8; r->coop_L = 4; r->dense_lds = mfma_lds; }
+        if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_mala_mfma", &r->jit_step, mfma_lds, "matrix-core MALA kernel");
+        if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->dense_lds = mfma_lds; }
         else if (cfg->reduce_lanes > 1) return rc;
         else r->jit_step = nullptr;
     }
@@ -187,45 +163,41 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
         if (NBL <= nbl_max) {
             jit_module* m = nullptr;
             const int waves = NBL <= (MHX_REAL64 ? 1 : 3) ? 4 : 2;
-            const std::string key = "mala_coop/l=" + std::to_string(L) + "/nbl=" + std::to_string(NBL) + "/tk=" + std::to_string(t->kind);
-            rc = jit_compile(ctx, key, jit_source(t, "mhx_mala_kernels.h"),
+            rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"),
                              {"MHX_JIT_MALA_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
                               "MHX_JIT_TK=" + std::to_string(t->kind), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mala_coop", &r->jit_step);
-            if (rc == MHX_OK) { r->variant = 4; r->coop_L = L; }
+            if (rc == MHX_OK) { r->variant = KF_COOP_JIT; r->coop_L = L; }
             else if (cfg->reduce_lanes > 1) return rc;
             else r->jit_step = nullptr;
         } else if (cfg->reduce_lanes > 1) {
             return mhx_fail(MHX_EINVAL, "mhx_mala_create: reduce_lanes=%d leaves %d blocks per lane (max %d)", L, NBL, nbl_max);
         }
     }
-    if (want_reg && !r->variant) {
+    if (want_reg && r->variant == KF_GENERIC) {
         jit_module* m = nullptr;
         // registers next to the generator's temporaries: 2 D reals of candidate + gradient, 3 XR of state / gradient / noise
         int xr = r->dim;
         if (split) xr = std::max(0, std::min(r->dim, ((MHX_REAL64 ? 200 : 400) - 2 * r->dim) / 3));
         if (const char* xe = opt(ctx, "MALA_XR")) xr = std::max(0, std::min(r->dim, atoi(xe)));          // tuning knob
-        const std::string key = "mala_reg/d=" + std::to_string(r->dim) + "/tk=" + std::to_string(t->kind) + "/xr=" + std::to_string(xr) + (zig ? "/zig" : "") + "/" + t->user_key;
         std::vector<std::string> defs = {"MHX_JIT_MALA=1", "MHX_JIT_DIM=" + std::to_string(r->dim), "MHX_JIT_TK=" + std::to_string(t->kind),
                                          "MHX_JIT_XR=" + std::to_string(xr)};
         if (zig) defs.push_back("MHX_JIT_GEN=1");
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_mala_kernels.h"), defs, &m, {"-mllvm", "-amdgpu-unroll-threshold-private=100000"});
-        if (rc == MHX_OK) rc = jit_function(m, zig ? "mhx_jit_mala_zig" : (xr < r->dim ? "mhx_jit_mala_split" : "mhx_jit_mala"), &r->jit_step);
+        rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"), defs, &m, {"-mllvm", "-amdgpu-unroll-threshold-private=100000"});
         r->reg_lds = xr < r->dim ? (size_t)3 * (r->dim - xr) * 64 * sizeof(mhx_real) : 0;
         if (zig) { r->reg_lds = MHX_MALA_ZIG_LDS_BYTES(r->dim, xr); r->normal_gen = MHX_GEN_ZIGGURAT; }      // one wave per block: mala_advance launches by reg_lds
-        if (rc == MHX_OK && r->reg_lds > 65536 &&
-            hipFuncSetAttribute((const void*)r->jit_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r->reg_lds) != hipSuccess)
-            rc = mhx_fail(MHX_EHIP, "MALA register kernel: %zu bytes of LDS refused", r->reg_lds);
+        if (rc == MHX_OK) rc = jit_kernel(m, zig ? "mhx_jit_mala_zig" : (xr < r->dim ? "mhx_jit_mala_split" : "mhx_jit_mala"), &r->jit_step, r->reg_lds,
+                                          "MALA register kernel");
         if (rc == MHX_OK && user) rc = jit_function(m, "mhx_jit_mala_init", &r->jit_init);
-        if (rc == MHX_OK) r->variant = 2;
+        if (rc == MHX_OK) r->variant = KF_REG_JIT;
         else if (zig) return rc;                                         // (no other kernel of this sampler has the ziggurat)
         else { r->jit_step = nullptr; r->jit_init = nullptr; }           // the run-time-dimension kernel computes the same chain
     }
-    if (user && !r->variant) {
+    if (user && r->variant == KF_GENERIC) {
         // the user source must also define MHX_LOGDENSITY_AND_GRADIENT (the reference's
         // check_capabilities, src/MALA.jl:42-52, throws when no gradient is available)
         jit_module* m = nullptr;
-        rc = jit_compile(ctx, "mala/" + t->user_key, jit_source(t, "mhx_mala_kernels.h"),
+        rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"),
                          {"MHX_JIT_MALA=1", "MHX_JIT_TK=" + std::to_string(t->kind)}, &m);
         if (rc) return rc;
         if ((rc = jit_function(m, "mhx_jit_mala", &r->jit_step))) return rc;
@@ -275,21 +247,21 @@ static int mala_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_slot = save_slot;
         a.thinning = thinning;
         unsigned grid = (unsigned)((r->n + 255) / 256);
-        if (r->variant == 4) {                                   // L lanes per chain: whole waves
+        if (r->variant == KF_COOP_JIT) {                         // L lanes per chain: whole waves
             const long threads = (((long)r->n + (64 / r->coop_L) - 1) / (64 / r->coop_L)) * 64;
             grid = (unsigned)((threads + 255) / 256);
         }
-        if (r->variant == 8 && r->mfma_stream) {
+        if (r->variant == KF_MFMA && r->mfma_stream) {
             grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
             mhx_real* gA = r->d_mfma_img;
             mhx_real* gAT = r->d_mfma_img + mfma_image_reals(r->dim);
             void* params[] = {&a, &tp, &gA, &gAT};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds, ctx->stream, params, nullptr));
-        } else if (r->variant == 8) {
+        } else if (r->variant == KF_MFMA) {
             grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
             void* params[] = {&a, &tp};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds, ctx->stream, params, nullptr));
-        } else if (r->jit_step && r->variant == 2 && r->reg_lds) {
+        } else if (r->jit_step && r->variant == KF_REG_JIT && r->reg_lds) {
             void* params[] = {&a, &tp};
             HIP_TRY(hipModuleLaunchKernel(r->jit_step, (unsigned)((r->n + 63) / 64), 1, 1, 64, 1, 1, (unsigned)r->reg_lds, ctx->stream, params, nullptr));
         } else if (r->jit_step) {

@@ -53,8 +53,7 @@ static const ram_shape k_ram_shapes[] = {
 // smallest pre-built shape that holds `d` rows (the table is ordered by G R)
 static const ram_shape* ram_pick_shape(const mhx_ctx* ctx, int d)
 {
-    const char* force = opt(ctx, "RAM_G");              // tuning knob: restrict to one group width
-    const int fg = force ? atoi(force) : 0;
+    const int fg = opt_int(ctx, "RAM_G", 0);           // tuning knob: restrict to one group width
     if (MHX_REAL64 && !fg)                                  // fp64: at most 4 rows per lane while a wider group can hold the chain
         for (const auto& sh : k_ram_shapes)
             if (d <= sh.G * sh.R && sh.R <= 4) return &sh;
@@ -208,7 +207,7 @@ int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mh
         // the deferred-factor form: its own rounding (spec 3.12), one chain per wave
         if (d > 256) return mhx_fail(MHX_EINVAL, "mhx_ram_create: MHX_FLAG_RAM_DEFERRED holds a chain in one wave: dim %ld > 256", d);
         r->defer_R = (int)((d + 63) / 64);
-        r->variant = 12;
+        r->variant = KF_RAM_DEFER;
         const size_t per = (size_t)MHX_RAM_DEFER_REALS(MHX_RAM_DEFER_K, r->defer_R);
         HIP_TRY(hipMalloc(&r->d_defer, per * (size_t)n * sizeof(mhx_real)));
         HIP_TRY(hipMemsetAsync(r->d_defer, 0, per * (size_t)n * sizeof(mhx_real), ctx->stream));
@@ -217,11 +216,10 @@ int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mh
         const ram_shape* sh = ram_pick_shape(ctx, (int)d);
         jit_module* m = nullptr;
         const int jg = r->defer_R ? 64 : sh->G, jr = r->defer_R ? r->defer_R : sh->R;
-        const std::string key = "ram/g=" + std::to_string(jg) + "/r=" + std::to_string(jr) + (r->defer_R ? "/defer" : "") + "/" + t->user_key;
         std::vector<std::string> defs = {"MHX_JIT_RAM=1", "MHX_JIT_G=" + std::to_string(jg), "MHX_JIT_R=" + std::to_string(jr),
                                          "MHX_JIT_TK=" + std::to_string(t->kind)};
         if (r->defer_R) defs.push_back("MHX_JIT_DEFER_K=" + std::to_string(MHX_RAM_DEFER_K));
-        rc = jit_compile(ctx, key, jit_source(t, "mhx_ram_kernels.h"), defs, &m);
+        rc = jit_compile(ctx, jit_source(t, "mhx_ram_kernels.h"), defs, &m);
         if (rc) return rc;
         if ((rc = jit_function(m, "mhx_jit_ram", &r->jit_step))) return rc;
         if ((rc = jit_function(m, "mhx_jit_ram_init", &r->jit_init))) return rc;
@@ -470,7 +468,7 @@ static int ram_advance(mhx_run* r, uint64_t nsteps, uint64_t n_adapt, uint32_t s
     if (const char* pad = opt(r->ctx, "RAM_LDS_PAD")) {               // tuning knob: fewer resident waves per CU (DESIGN.md 6.3)
         lds += (size_t)atol(pad);
         if (lds > 65536 && !r->jit_step)
-            HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            if (int rcl = kernel_lds_limit((const void*)fn, lds, "RAM kernel")) return rcl;
     }
     const long nwaves = ((long)r->n + cpw - 1) / cpw;
     const unsigned grid = (unsigned)(((nwaves + 7) / 8) * 8);
