@@ -182,6 +182,15 @@ CREATE(emcee, mhx_emcee_cfg)
 CREATE(ram, mhx_ram_cfg)
 CREATE(mala, mhx_mala_cfg)
 
+extern "C" int mhx_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
+                                          int32_t ncomps, mhx_run** out)
+{
+    NEED(ctx, "mhx_rwmh_create_components");
+    if (!same(ctx, t)) return MIXED("mhx_rwmh_create_components");
+    return is64(ctx) ? mhx_f64::api_rwmh_create_components(C64(ctx), CT64(t), cfg, comps, ncomps, reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_rwmh_create_components(C32(ctx), CT32(t), cfg, comps, ncomps, reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
+
 extern "C" int mhx_ram_set_factor(mhx_run* r, const void* S)
 {
     NEED(r, "mhx_ram_set_factor");

@@ -25,6 +25,7 @@
 #include <rocprim/rocprim.hpp>   // device radix sort for the rank-normalised ESS (after <cstring>: it calls memset)
 
 #include "mhx_rwmh_kernels.h"
+#include "mhx_rwmh_family_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
 #include "mhx_mala_kernels.h"
@@ -94,6 +95,23 @@ k_record_state(const mhx_real* __restrict__ x, const mhx_real* __restrict__ lp, 
                mhx_real* samples, unsigned char* accepted, const int n, const long ld, const int d, const long slot)
 {
     mhx_record_state_body(x, lp, last_acc, samples, accepted, n, ld, d, slot);
+}
+
+// proposals of univariate family components (mhx_rwmh_family_kernels.h): the state-in-HBM form, the initial draw, q(x) of a static run
+__global__ void __launch_bounds__(256)
+k_fam_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_fam_comp* __restrict__ fam, const int symmetric)
+{
+    mhx_fam_generic_body<MHX_TARGET_DYNAMIC>(a, tparams, fam, symmetric);
+}
+__global__ void __launch_bounds__(256)
+k_fam_init_draw(const mhx_rwmh_args a, const mhx_fam_comp* __restrict__ fam)
+{
+    mhx_fam_init_draw_body(a, fam);
+}
+__global__ void __launch_bounds__(256)
+k_fam_q(const mhx_rwmh_args a, const mhx_fam_comp* __restrict__ fam)
+{
+    mhx_fam_q_body(a, fam);
 }
 
 // (MHX_COOP_WAVES, the occupancy target of the cooperative kernel, comes from mhx_rwmh_kernels.h)
@@ -448,10 +466,12 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
     const char* hdr_src[] = {k_src_mhx_zig_table_h, k_src_mhx_device_math_h, k_src_mhx_targets_h, k_src_mhx_rwmh_kernels_h,
                              k_src_mhx_emcee_kernels_h, k_src_mhx_ram_kernels_h, k_src_mhx_mala_kernels_h,
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
-                             k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h};
+                             k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
-                              "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h"};
+                              "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
+                              "mhx_rwmh_family_kernels.h"};
+    const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
 #ifdef MHX_TOOLS_BUILD
@@ -484,9 +504,9 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
     const bool want_ext = !(jc && !strcmp(jc, "hiprtc")) && !mhx_jit_ext_identity().empty();
     if (jc && !strcmp(jc, "clang") && !want_ext) return mhx_fail(MHX_EJIT, "JIT_COMPILER=clang: no clang++ found (MHX_JIT_CLANG, ROCM_PATH, /opt/rocm)");
     const std::string cdir = jit_cache_dir();
-    const std::string cname = cdir.empty() ? std::string() : jit_cache_name(source, opts, hdr_src, 11, want_ext ? mhx_jit_ext_identity() : std::string());
+    const std::string cname = cdir.empty() ? std::string() : jit_cache_name(source, opts, hdr_src, nhdr, want_ext ? mhx_jit_ext_identity() : std::string());
     // (where the offline compiler is preferred but failed on this source before, hiprtc's object is there under its own name)
-    const std::string cname_rtc = (cdir.empty() || !want_ext) ? cname : jit_cache_name(source, opts, hdr_src, 11, std::string());
+    const std::string cname_rtc = (cdir.empty() || !want_ext) ? cname : jit_cache_name(source, opts, hdr_src, nhdr, std::string());
     std::vector<char> code;
     bool from_cache = !cdir.empty() && (jit_cache_read(cdir + "/" + cname, &code) || (want_ext && jit_cache_read(cdir + "/" + cname_rtc, &code)));
     if (from_cache) {
@@ -502,7 +522,7 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
     }
     if (want_ext) {
         std::string xlog;
-        if (mhx_jit_ext_compile(source, hdr_src, hdr_name, 11, opts, &code, &xlog)) {
+        if (mhx_jit_ext_compile(source, hdr_src, hdr_name, nhdr, opts, &code, &xlog)) {
             std::unique_ptr<jit_module> m(new jit_module);
             const hipError_t e = hipModuleLoadData(&m->mod, code.data());
             if (e == hipSuccess) {
@@ -528,7 +548,7 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
         }
     }
     hiprtcProgram prog = nullptr;
-    hiprtcResult r = hiprtcCreateProgram(&prog, source.c_str(), "mhx_jit.hip", 11, hdr_src, hdr_name);
+    hiprtcResult r = hiprtcCreateProgram(&prog, source.c_str(), "mhx_jit.hip", nhdr, hdr_src, hdr_name);
     if (r != HIPRTC_SUCCESS) return mhx_fail(MHX_EJIT, "hiprtcCreateProgram: %s", hiprtcGetErrorString(r));
     std::vector<const char*> copts;
     for (auto& o : opts) copts.push_back(o.c_str());
@@ -785,6 +805,7 @@ enum kernel_form {
     KF_EMCEE_MFMA = 10,     // matrix-core form of the stretch move
     KF_WAVE = 11,           // a wave per chain
     KF_RAM_DEFER = 12,      // RAM with a deferred factor
+    KF_FAMILY = 13,         // a proposal of univariate family components: specialised register form or state in HBM
 };
 
 struct mhx_run : mhx_handle_hdr {
@@ -809,6 +830,9 @@ struct mhx_run : mhx_handle_hdr {
     mhx_real* d_mfma_img = nullptr;         // streamed matrix-core kernel: the operand images [target][proposal] in global memory
     bool mfma_stream = false;
     mhx_real* d_qx = nullptr;               // static proposal: logpdf of the proposal at each chain's state (up to its constant)
+    mhx_fam_comp* d_fam = nullptr;          // KF_FAMILY: the component table [dim]
+    bool fam_reg = false;                   // ... stepped by the specialised register form (jit_step), else by the state-in-HBM form
+    int fam_symmetric = 0;                  // ... a random walk declared symmetric: no ratio
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -881,7 +905,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam};
         for (void* p : ptrs) if (p) (void)hipFree(p);
     }
 };
@@ -930,6 +954,9 @@ static int rwmh_whiten(mhx_run* r)
 {
     if (!r->d_qx) return MHX_OK;
     mhx_rwmh_args a = rwmh_args(r);
+    if (r->variant == KF_FAMILY)
+        hipLaunchKernelGGL(k_fam_q, dim3((unsigned)((r->n + 255) / 256)), dim3(256), 0, r->ctx->stream, a, (const mhx_fam_comp*)r->d_fam);
+    else
     hipLaunchKernelGGL(k_rwmh_whiten, dim3((unsigned)((r->n + 255) / 256)), dim3(256), 0, r->ctx->stream, a, r->d_pvec);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
@@ -1310,6 +1337,114 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     return MHX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// A proposal of independent univariate components (include/mhx.h: mhx_rwmh_create_components)
+int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
+                               int32_t ncomps, mhx_run** out)
+{
+    const char* me = "mhx_rwmh_create_components";
+    if (!ctx || !t || !cfg || !comps || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
+    if (cfg->dim != t->dim) return mhx_fail(MHX_EINVAL, "%s: proposal dim %d != model dim %d", me, cfg->dim, t->dim);
+    if (ncomps != cfg->dim) return mhx_fail(MHX_EINVAL, "%s: %d components for dim %d (one component per parameter)", me, ncomps, cfg->dim);
+    if (cfg->nchains <= 0) return mhx_fail(MHX_EINVAL, "%s: nchains must be positive", me);
+    if (cfg->flags & MHX_FLAG_ZIGGURAT)
+        return mhx_fail(MHX_EINVAL, "%s: MHX_FLAG_ZIGGURAT -- a family run draws its Normal components by Box-Muller only", me);
+    if (cfg->reduce_lanes > 1)
+        return mhx_fail(MHX_EINVAL, "%s: reduce_lanes = %d -- a family run is one lane per chain (reduce_lanes 0 or 1)", me, cfg->reduce_lanes);
+    const int d = cfg->dim;
+    if (d >= (1 << 20)) return mhx_fail(MHX_EINVAL, "%s: dim must be below 2^20 (the Gamma blocks are numbered component << 8 | attempt)", me);
+    const bool stat = (cfg->flags & MHX_FLAG_STATIC_PROPOSAL) != 0;
+    // the table: parameters and what the kernels derive from them once, in double, each rounded once to the engine's width
+    std::vector<mhx_fam_comp> tab((size_t)d);
+    std::string pattern;
+    for (int k = 0; k < d; ++k) {
+        const mhx_proposal_component& c = comps[k];
+        const double p0 = c.p0, p1 = c.p1;
+        mhx_fam_comp& o = tab[(size_t)k];
+        memset(&o, 0, sizeof o);
+        o.family = c.family;
+        const bool fin0 = std::isfinite(p0), fin1 = std::isfinite(p1);
+        const char* bad = nullptr;
+        switch (c.family) {
+        case MHX_FAMILY_NORMAL: if (!fin0 || !fin1 || !(p1 > 0.0)) bad = "Normal(mu, sigma) needs finite mu and sigma > 0"; break;
+        case MHX_FAMILY_UNIFORM: if (!fin0 || !fin1 || !(p0 < p1)) bad = "Uniform(a, b) needs finite a < b"; break;
+        case MHX_FAMILY_LAPLACE: if (!fin0 || !fin1 || !(p1 > 0.0)) bad = "Laplace(mu, theta) needs finite mu and theta > 0"; break;
+        case MHX_FAMILY_CAUCHY: if (!fin0 || !fin1 || !(p1 > 0.0)) bad = "Cauchy(mu, sigma) needs finite mu and sigma > 0"; break;
+        case MHX_FAMILY_EXPONENTIAL: if (!fin0 || !(p0 > 0.0)) bad = "Exponential(theta) needs finite theta > 0"; break;
+        case MHX_FAMILY_GAMMA: if (!fin0 || !fin1 || !(p0 > 0.0) || !(p1 > 0.0)) bad = "Gamma(alpha, theta) needs finite alpha > 0 and theta > 0"; break;
+        case MHX_FAMILY_INVERSE_GAMMA: if (!fin0 || !fin1 || !(p0 > 0.0) || !(p1 > 0.0)) bad = "InverseGamma(alpha, theta) needs finite alpha > 0 and theta > 0"; break;
+        default: return mhx_fail(MHX_EINVAL, "%s: component %d has unknown family %d", me, k, c.family);
+        }
+        if (bad) return mhx_fail(MHX_EINVAL, "%s: component %d: %s, got (%g, %g)", me, k, bad, p0, p1);
+        o.p[0] = (mhx_real)p0;
+        o.p[1] = (mhx_real)p1;
+        if (c.family == MHX_FAMILY_UNIFORM) {
+            o.p[2] = o.p[1] - o.p[0];                       // the rounded bounds' difference, in the engine's width
+            if (!(o.p[0] < o.p[1])) bad = "Uniform(a, b): a and b round to the same number in this width";
+        } else if (c.family == MHX_FAMILY_GAMMA || c.family == MHX_FAMILY_INVERSE_GAMMA) {
+            // everything from alpha AS ROUNDED to the run's width -- the number the kernel compares with 1 to apply the boost
+            const double al = (double)o.p[0];
+            const double ae = al < 1.0 ? al + 1.0 : al, dd = ae - 1.0 / 3.0;
+            o.p[2] = (mhx_real)dd;
+            o.p[3] = (mhx_real)(1.0 / std::sqrt(9.0 * dd));
+            o.p[4] = (mhx_real)(1.0 / al);
+            o.p[5] = (mhx_real)(c.family == MHX_FAMILY_GAMMA ? al - 1.0 : -(al + 1.0));
+            if (!(o.p[0] > MHX_R(0.0)) || !(o.p[1] > MHX_R(0.0)) || !std::isfinite((double)o.p[4])) bad = "the parameters leave this width's range";
+        } else if (c.family != MHX_FAMILY_UNIFORM && c.family != MHX_FAMILY_EXPONENTIAL && !(o.p[1] > MHX_R(0.0))) {
+            bad = "the scale rounds to zero in this width";
+        }
+        if (c.family == MHX_FAMILY_EXPONENTIAL && !(o.p[0] > MHX_R(0.0))) bad = "the scale rounds to zero in this width";
+        if (bad) return mhx_fail(MHX_EINVAL, "%s: component %d: %s, got (%g, %g)", me, k, bad, p0, p1);
+        if (k) pattern += ',';
+        pattern += std::to_string(c.family);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<mhx_run> r(new mhx_run);
+    r->dtype = ctx->dtype;
+    r->ctx = ctx; r->target = t; r->kind = RUN_RWMH;
+    r->dim = d; r->n = cfg->nchains; r->seed = cfg->seed; r->first_id = cfg->first_chain;
+    r->flags = cfg->flags;
+    r->prop_kind = 3;                                        // none of mhx_proposal_kind: a checkpoint of an (Mv)Normal run does not load here
+    r->variant = KF_FAMILY;
+    r->fam_symmetric = (!stat && (cfg->flags & MHX_FLAG_SYMMETRIC_PROPOSAL)) ? 1 : 0;
+    HIP_TRY(hipMalloc(&r->d_fam, tab.size() * sizeof(mhx_fam_comp)));
+    COPY_SYNC(ctx->stream, r->d_fam, tab.data(), tab.size() * sizeof(mhx_fam_comp), hipMemcpyHostToDevice);
+    int rc = run_alloc_state(r.get());
+    if (rc) return rc;
+    if (stat) HIP_TRY(hipMalloc(&r->d_qx, (size_t)r->n * sizeof(mhx_real)));
+    const int tk = t->kind;
+    // the register form addresses a [dim+1][nchains] slab with 32-bit byte offsets and holds x and y in VGPRs
+    const bool small = ((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) < (1ull << 32);
+    if (!(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && small && d <= MHX_FAM_REG_MAX_DIM &&
+        !(tk == MHX_TARGET_CORR_GAUSS && d > (MHX_REAL64 ? 32 : 64)) && !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096)) {
+        jit_module* m = nullptr;
+        // the component loop must unroll whole (y[k] indexed by a constant): its body -- Philox, a draw, two log-kernels -- passes
+        // hipcc's size limit for `#pragma unroll` from about 48 components on, and y would then live in scratch
+        const char* ut = opt(ctx, "REG_UNROLL");
+        std::vector<std::string> xo = {"-mllvm", "-pragma-unroll-threshold=4000000"};
+        if (!ut || atoi(ut) > 0) { xo.push_back("-mllvm"); xo.push_back(std::string("-amdgpu-unroll-threshold-private=") + (ut ? ut : "100000")); }
+        rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_family_kernels.h"),
+                         {"MHX_JIT_FAM_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
+                          "MHX_JIT_FAM_LIST=" + pattern, std::string("MHX_JIT_FAM_STATIC=") + (stat ? "1" : "0"),
+                          std::string("MHX_JIT_FAM_SYM=") + (r->fam_symmetric ? "1" : "0")}, &m, xo);
+        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_fam_reg", &r->jit_step);
+        if (rc) return rc;
+        r->fam_reg = true;
+    }
+    if (tk == MHX_TARGET_USER) {
+        jit_module* m = nullptr;
+        if ((rc = jit_generic_rwmh(t, &m))) return rc;
+        if ((rc = jit_function(m, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
+        if (!r->fam_reg) {
+            if ((rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_family_kernels.h"), {"MHX_JIT_FAM_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
+            if ((rc = jit_function(m, "mhx_jit_fam_generic", &r->jit_step))) return rc;
+        }
+    }
+    if (!r->fam_reg) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
+    *out = r.release();
+    return MHX_OK;
+}
+
 // ---- emcee / ram creation, init and stepping live in their own sections below
 static int emcee_init(mhx_run* r, const mhx_real* init);
 static int emcee_sync_state(mhx_run* r, int to_abi);
@@ -1354,6 +1489,11 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
     const mhx_real* pv = r->d_pvec;
     int draw = init ? 0 : 1;
     const unsigned grid = (unsigned)((r->n + 255) / 256);
+    if (r->variant == KF_FAMILY && draw) {         // the bare draw from the component proposal; the kernel below then evaluates lp
+        hipLaunchKernelGGL(k_fam_init_draw, dim3(grid), dim3(256), 0, ctx->stream, a, (const mhx_fam_comp*)r->d_fam);
+        HIP_TRY(hipGetLastError());
+        draw = 0;
+    }
     if (r->target->kind == MHX_TARGET_USER) {
         void* params[] = {&a, &tp, &pv, &draw};
         int rc = launch_module(r->jit_init, grid, 256, ctx->stream, params);
@@ -1382,7 +1522,20 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->variant == KF_COOP || r->variant == KF_COOP_JIT) {
+        if (r->variant == KF_FAMILY) {
+            const mhx_fam_comp* fam = r->d_fam;
+            int sym = r->fam_symmetric;
+            if (r->fam_reg) {
+                void* params[] = {&a, &tp, &fam};
+                HIP_TRY(hipModuleLaunchKernel(r->jit_step, (unsigned)((r->n + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, params, nullptr));
+            } else if (r->target->kind == MHX_TARGET_USER) {
+                void* params[] = {&a, &tp, &fam, &sym};
+                int rc = launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, ctx->stream, params);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(k_fam_generic, dim3((unsigned)((r->n + 255) / 256)), dim3(256), 0, ctx->stream, a, tp, fam, sym);
+            }
+        } else if (r->variant == KF_COOP || r->variant == KF_COOP_JIT) {
             const long threads = (((long)r->n + (64 / r->coop_L) - 1) / (64 / r->coop_L)) * 64;   // whole waves
             unsigned grid = (unsigned)((threads + 255) / 256);
             if (r->coop_L >= 32) grid = (grid + 7u) & ~7u;          // the kernel's XCD-aware block -> chain map wants whole rounds of 8
@@ -1537,6 +1690,9 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->rec_loga_view = nullptr;
     if (save_samples == MHX_SAVE_MOMENTS) {
         // running moments instead of a sample tensor
+        if (r->kind == RUN_RWMH && r->variant == KF_FAMILY)
+            return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run whose proposal is a vector of family "
+                                    "components (kernel variant 13): record samples");
         if (r->kind != RUN_RWMH || (r->variant != KF_GENERIC && r->variant != KF_COOP && r->variant != KF_COOP_JIT))
             return mhx_fail(MHX_EINVAL, "running moments need an RWMH run on the cooperative or the generic kernel "
                                     "(separable target, or MHX_FLAG_GENERIC); this run uses kernel variant %d", r->variant);

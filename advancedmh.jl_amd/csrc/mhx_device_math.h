@@ -512,6 +512,15 @@ MHX_DEV mhx_emcee_draws mhx_emcee_draw(const mhx_philox_key& ks, mhx_u32 walker,
     o.logu = mhx_log_pos(mhx_u01_open(v.x, v.y));
     return o;
 }
+
+// Proposal families, how a Philox block of a family stream is spent in fp64: words (x, y) are the uniform,
+// words (z, w) the second uniform / the 64-bit phase, bit 31 of z the sign; a Marsaglia-Tsang normal is normal 0 of the block's
+// Box-Muller pair.  The draws and log-kernels built from these are below the two width sections.
+MHX_DEV double mhx_fam_u_open(const mhx_u32x4& w) { return mhx_u01_open(w.x, w.y); }
+MHX_DEV double mhx_fam_u_half(const mhx_u32x4& w) { return mhx_u01_half(w.x, w.y); }
+MHX_DEV double mhx_fam_u_open2(const mhx_u32x4& w) { return mhx_u01_open(w.z, w.w); }
+MHX_DEV void mhx_fam_phase(const mhx_u32x4& w, double& s, double& c) { mhx_sincos2pi_u64(w.z, w.w, s, c); }
+MHX_DEV double mhx_fam_normal(const mhx_u32x4& w) { double n0, n1; mhx_normal_pair(w, n0, n1); return n0; }
 #else
 // ---------------------------------------------------------------------------------------------
 MHX_DEV mhx_u32 mhx_f2u(float f) { return __builtin_bit_cast(mhx_u32, f); }
@@ -841,7 +850,103 @@ MHX_DEV mhx_emcee_draws mhx_emcee_draw(const mhx_philox_key& ks, mhx_u32 walker,
     o.logu = mhx_log_pos(mhx_u01_open(w.z));
     return o;
 }
+
+// Proposal families, how a Philox block of a family stream is spent in fp32: word x is the uniform, word z
+// the second uniform / the 32-bit phase, bit 31 of z the sign; a Marsaglia-Tsang normal is normal 0 of the Box-Muller pair (x, y).
+MHX_DEV float mhx_fam_u_open(const mhx_u32x4& w) { return mhx_u01_open(w.x); }
+MHX_DEV float mhx_fam_u_half(const mhx_u32x4& w) { return mhx_u01_half(w.x); }
+MHX_DEV float mhx_fam_u_open2(const mhx_u32x4& w) { return mhx_u01_open(w.z); }
+MHX_DEV void mhx_fam_phase(const mhx_u32x4& w, float& s, float& c) { mhx_sincos2pi_u32(w.z, s, c); }
+MHX_DEV float mhx_fam_normal(const mhx_u32x4& w) { float n0, n1; mhx_normal_pair(w.x, w.y, n0, n1); return n0; }
 #endif
+
+// ---------------------------------------------------------------------------------------------
+// Univariate proposal families (src/proposal.jl:23-35,41-83 with a vector of Distributions univariates).
+// Component k of a proposal is one of the families below with two parameters as in Distributions.jl; its draw is a pure function of
+// (seed, chain id, step, k, attempt) and its log-kernel is logpdf minus the terms that do not depend on the argument (they cancel in
+// every ratio the sampler forms).  Streams: a Normal component takes normal k of the Box-Muller stream the (Mv)Normal proposals use
+// (MHX_STREAM_PROPOSAL / MHX_STREAM_INIT); every other family takes block k of stream `sbase`, and the Gamma families blocks
+// (k << 8 | attempt) of streams sbase + 1 (the Marsaglia-Tsang normal) and sbase + 2 (its uniforms).  sbase is MHX_STREAM_FAMILY for a
+// transition and MHX_STREAM_FAMILY_INIT for the initial draw; ids 0 .. 7 belong to the older streams and their retry twins.
+#define MHX_FAMILY_NORMAL        0
+#define MHX_FAMILY_UNIFORM       1
+#define MHX_FAMILY_LAPLACE       2
+#define MHX_FAMILY_CAUCHY        3
+#define MHX_FAMILY_EXPONENTIAL   4
+#define MHX_FAMILY_GAMMA         5
+#define MHX_FAMILY_INVERSE_GAMMA 6
+#define MHX_STREAM_FAMILY      8u
+#define MHX_STREAM_FAMILY_INIT 12u
+#define MHX_FAM_GAMMA_ATTEMPTS 128u
+
+// One row of the wave-uniform parameter table, rounded once from double on the host (api_rwmh_create_components):
+//   Normal (mu, sigma) | Uniform (a, b, b - a) | Laplace (mu, theta) | Cauchy (mu, sigma) | Exponential (theta)
+//   Gamma / InverseGamma (alpha, theta, d, c, 1 / alpha, e):  d = alpha' - 1/3 and c = 1 / sqrt(9 d) of Marsaglia-Tsang with
+//   alpha' = alpha (alpha >= 1) or alpha + 1 (the boost);  e = alpha - 1 (Gamma) or -(alpha + 1) (InverseGamma), the power of the argument
+struct mhx_fam_comp { int family; int reserved; mhx_real p[6]; };
+
+// Gamma(alpha, 1) by Marsaglia & Tsang (2000): attempt t takes a normal n and a uniform u; v = (1 + c n)^3 is accepted iff 1 + c n > 0
+// and log u < n^2 / 2 + d - d v + d log v, the draw is d v -- times u2^(1 / alpha), u2 the accepted attempt's second uniform, when
+// alpha < 1.  The loop runs while any lane of the wave is undecided; MHX_FAM_GAMMA_ATTEMPTS attempts without success give NaN (a
+// candidate that is rejected; probability < 1e-150).
+MHX_DEV mhx_real mhx_fam_gamma(const mhx_real* __restrict__ p, const mhx_philox_key& ks, const mhx_u32 id_lo, const mhx_u32 id_hi,
+                               const mhx_u32 step, const mhx_u32 sbase, const mhx_u32 k)
+{
+    const mhx_real alpha = p[0], d = p[2], c = p[3], inva = p[4];
+    mhx_real g = MHX_NAN;
+    bool done = false;
+    for (mhx_u32 t = 0u; t < MHX_FAM_GAMMA_ATTEMPTS && __ballot(!done) != 0ull; ++t) {
+        const mhx_u32 blk = (k << 8) | t;
+        const mhx_real n = mhx_fam_normal(mhx_philox(ks, id_lo, id_hi, step, ((sbase + 1u) << 28) | blk));
+        const mhx_u32x4 wu = mhx_philox(ks, id_lo, id_hi, step, ((sbase + 2u) << 28) | blk);
+        const mhx_real v1 = mhx_fma(c, n, MHX_R(1.0));
+        const mhx_real v = (v1 * v1) * v1;
+        const mhx_real lu = mhx_log_pos(mhx_fam_u_open(wu));
+        const mhx_real h = (MHX_R(0.5) * n) * n;
+        const mhx_real rhs = mhx_fma(d, mhx_log(v), h + (d - d * v));
+        const bool ok = v1 > MHX_R(0.0) && lu < rhs;
+        mhx_real gt = d * v;
+        if (alpha < MHX_R(1.0)) gt = gt * mhx_exp(mhx_log_pos(mhx_fam_u_open2(wu)) * inva);      // (wave-uniform)
+        if (ok && !done) { g = gt; done = true; }
+    }
+    return g;
+}
+
+// xi_k: the draw of component k; `nk` is standard normal k of the step (read by the Normal family only)
+MHX_DEV mhx_real mhx_fam_draw(const int family, const mhx_real* __restrict__ p, const mhx_real nk, const mhx_philox_key& ks,
+                              const mhx_u32 id_lo, const mhx_u32 id_hi, const mhx_u32 step, const mhx_u32 sbase, const mhx_u32 k)
+{
+    if (family == MHX_FAMILY_NORMAL) return mhx_fma(p[1], nk, p[0]);
+    if (family == MHX_FAMILY_GAMMA) return mhx_fam_gamma(p, ks, id_lo, id_hi, step, sbase, k) * p[1];
+    if (family == MHX_FAMILY_INVERSE_GAMMA) return p[1] / mhx_fam_gamma(p, ks, id_lo, id_hi, step, sbase, k);
+    const mhx_u32x4 w = mhx_philox(ks, id_lo, id_hi, step, (sbase << 28) | k);
+    if (family == MHX_FAMILY_UNIFORM) {
+        const mhx_real v = mhx_fma(p[2], mhx_fam_u_half(w), p[0]);
+        return v > p[1] ? p[1] : v;                                  // (b - a rounded up must not carry the draw past b)
+    }
+    if (family == MHX_FAMILY_CAUCHY) {
+        mhx_real s, c;
+        mhx_fam_phase(w, s, c);
+        return mhx_fma(p[1], s / c, p[0]);
+    }
+    // Exponential(theta) = -theta log u; Laplace(mu, theta) = mu +- that, the sign from a bit of its own (no 1 - 2 |u| cancellation)
+    const mhx_real e = -mhx_log_pos(mhx_fam_u_open(w));
+    if (family == MHX_FAMILY_EXPONENTIAL) return e * p[0];
+    const mhx_real m = e * p[1];
+    return p[0] + ((w.z >> 31) ? -m : m);
+}
+
+// log-kernel of component `family` at v: logpdf minus its constant, -Inf outside the support
+MHX_DEV mhx_real mhx_fam_logk(const int family, const mhx_real* __restrict__ p, const mhx_real v)
+{
+    if (family == MHX_FAMILY_NORMAL) { const mhx_real t = (v - p[0]) / p[1]; return -MHX_R(0.5) * (t * t); }
+    if (family == MHX_FAMILY_UNIFORM) return (v >= p[0] && v <= p[1]) ? MHX_R(0.0) : -MHX_INF;
+    if (family == MHX_FAMILY_LAPLACE) return -(mhx_abs(v - p[0]) / p[1]);
+    if (family == MHX_FAMILY_CAUCHY) { const mhx_real t = (v - p[0]) / p[1]; return -mhx_log(mhx_fma(t, t, MHX_R(1.0))); }
+    if (family == MHX_FAMILY_EXPONENTIAL) return v >= MHX_R(0.0) ? -(v / p[0]) : -MHX_INF;
+    if (family == MHX_FAMILY_GAMMA) return v > MHX_R(0.0) ? mhx_fma(p[5], mhx_log(v), -(v / p[1])) : -MHX_INF;
+    return v > MHX_R(0.0) ? mhx_fma(p[5], mhx_log(v), -(p[1] / v)) : -MHX_INF;         // InverseGamma
+}
 
 // ---------------------------------------------------------------------------------------------
 // One step of the xor-butterfly of the reduction shapes (spec 3.7): q + (the q of lane ^ DIST), DIST a power of two below 64.

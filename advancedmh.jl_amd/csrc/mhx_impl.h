@@ -41,6 +41,8 @@ void mhx_jit_unlock();
     int api_target_destroy(mhx_target* t);                                                                             \
     int api_target_eval(mhx_ctx* ctx, const mhx_target* t, const REAL* x, int n, REAL* lp);                            \
     int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, mhx_run** out);                    \
+    int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                         \
+                                   const mhx_proposal_component* comps, int32_t ncomps, mhx_run** out);                \
     int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg, mhx_run** out);                  \
     int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mhx_run** out);                      \
     int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, mhx_run** out);                    \

@@ -65,10 +65,14 @@ end
 struct DiagCfg
     max_lag::Int32; ess_chains::Int32; split::Int32
 end
+struct ProposalComponent
+    family::Int32; reserved::Int32; p0::Cdouble; p1::Cdouble
+end
 const MHX_FLAG_STATIC_PROPOSAL = Int32(4)
 const MHX_FLAG_EMCEE_SEQUENTIAL = Int32(8)
 const MHX_FLAG_ZIGGURAT = Int32(16)
 const MHX_FLAG_RAM_DEFERRED = Int32(64)
+const MHX_FLAG_SYMMETRIC_PROPOSAL = Int32(128)
 
 """
     LangevinProposal(σ²)
@@ -253,6 +257,24 @@ proposal_mean(d::Normal) = [mean(d)]
 proposal_mean(ds::AbstractVector{<:Normal}) = [mean(d) for d in ds]
 ptr_or_null(v::Vector) = isempty(v) ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(v))
 
+# a univariate of one of the device families -> its row of the component table (mhx_family, parameters as Distributions.jl has them)
+proposal_component(d::Normal) = ProposalComponent(0, 0, mean(d), std(d))
+proposal_component(d::Uniform) = ProposalComponent(1, 0, minimum(d), maximum(d))
+proposal_component(d::Laplace) = ProposalComponent(2, 0, params(d)[1], params(d)[2])
+proposal_component(d::Cauchy) = ProposalComponent(3, 0, params(d)[1], params(d)[2])
+proposal_component(d::Exponential) = ProposalComponent(4, 0, scale(d), 0.0)
+proposal_component(d::Gamma) = ProposalComponent(5, 0, shape(d), scale(d))
+proposal_component(d::InverseGamma) = ProposalComponent(6, 0, shape(d), scale(d))
+proposal_component(d::TDist) = dof(d) == 1 ? ProposalComponent(3, 0, 0.0, 1.0) :
+    throw(ArgumentError("TDist($(dof(d))): only TDist(1) = Cauchy(0, 1) is lowered to the device"))
+proposal_component(d) = throw(ArgumentError("no device sampler for a proposal component $(typeof(d))"))
+# a vector of univariates with a component that is not Normal (or one such univariate): the component table; else nothing
+function proposal_components(p)
+    ds = p isa UnivariateDistribution ? [p] : p
+    (ds isa AbstractVector && all(d -> d isa UnivariateDistribution, ds) && !all(d -> d isa Normal, ds)) || return nothing
+    return ProposalComponent[proposal_component(d) for d in ds]
+end
+
 # the number of parameters of a closure's model, from what the call carries (the reference never needs it: a closure takes any vector)
 function model_dim(sampler, initial_params)
     initial_params isa AbstractVector{<:Real} && return length(initial_params)
@@ -432,7 +454,17 @@ function make_run(::Type{T}, ctx::Ptr{Cvoid}, tgt::Ptr{Cvoid}, d::Integer, sampl
     if sampler isa AdvancedMH.MetropolisHastings
         prop = sampler.proposal
         prop isa Union{AdvancedMH.RandomWalkProposal, AdvancedMH.StaticProposal} ||
-            throw(ArgumentError("the GPU path implements RandomWalkProposal and StaticProposal over (Mv)Normal only"))
+            throw(ArgumentError("the GPU path implements RandomWalkProposal and StaticProposal over (Mv)Normal and vectors of univariate components only"))
+        comps = proposal_components(prop.proposal)
+        if comps !== nothing
+            flags = prop isa AdvancedMH.StaticProposal ? MHX_FLAG_STATIC_PROPOSAL :
+                    (prop isa AdvancedMH.RandomWalkProposal{true} ? MHX_FLAG_SYMMETRIC_PROPOSAL : Int32(0))
+            ens.ziggurat && (flags |= MHX_FLAG_ZIGGURAT)          # the library refuses it for a family run: no silent rerouting
+            cfg = RwmhCfg(d, n, seed, first, Int32(0), 1.0, Ptr{Cvoid}(C_NULL), flags, Ptr{Cvoid}(C_NULL), 0)
+            GC.@preserve comps check(ccall((:mhx_rwmh_create_components, libmhx), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{RwmhCfg}, Ptr{ProposalComponent}, Int32, Ref{Ptr{Cvoid}}), ctx, tgt, cfg, comps, length(comps), run))
+            return run[], Int(n), initial_params
+        end
         kind, scale, vec = proposal_spec(T, prop.proposal)
         μ = T.(proposal_mean(prop.proposal))
         flags = prop isa AdvancedMH.StaticProposal ? MHX_FLAG_STATIC_PROPOSAL : Int32(0)

@@ -21,6 +21,10 @@ FLAG_EMCEE_SEQUENTIAL = 8
 FLAG_ZIGGURAT = 16
 FLAG_DENSE_FACTOR = 32
 FLAG_RAM_DEFERRED = 64
+FLAG_SYMMETRIC_PROPOSAL = 128
+# mhx_family: the univariate families a proposal component may be (mhx_rwmh_create_components)
+(FAMILY_NORMAL, FAMILY_UNIFORM, FAMILY_LAPLACE, FAMILY_CAUCHY, FAMILY_EXPONENTIAL, FAMILY_GAMMA,
+ FAMILY_INVERSE_GAMMA) = range(7)
 
 
 class MhxError(RuntimeError):
@@ -48,6 +52,11 @@ class RwmhCfg(C.Structure):
                 ("proposal_kind", C.c_int32), ("proposal_scale", C.c_double),
                 ("proposal_vec", C.c_void_p), ("flags", C.c_int32),
                 ("proposal_mean", C.c_void_p), ("reduce_lanes", C.c_int32)]
+
+
+class ProposalComponent(C.Structure):
+    """mhx_proposal_component: one univariate component of a proposal, parameters as in Distributions.jl"""
+    _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
 
 
 class EmceeCfg(C.Structure):
@@ -110,7 +119,7 @@ EXPORTS = [
     "mhx_ctx_set_option", "mhx_ctx_get_option", "mhx_ctx_pci_bus_id", "mhx_run_shape", "mhx_comm_init_timed", "mhx_comm_set_timeout",
     "mhx_group_create", "mhx_group_destroy", "mhx_group_size", "mhx_group_ctx", "mhx_group_shard", "mhx_group_attach", "mhx_group_run",
     "mhx_group_init", "mhx_group_sample", "mhx_group_sample_to_host", "mhx_group_stats", "mhx_group_diagnostics", "mhx_group_ess_bulk_tail",
-    "mhx_compact_expand", "mhx_run_host_stats",
+    "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -171,6 +180,7 @@ def lib():
         L.mhx_target_destroy.argtypes = [vp]
         L.mhx_target_eval.argtypes = [vp, vp, rp, C.c_int, rp]
         L.mhx_rwmh_create.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(vp)]
+        L.mhx_rwmh_create_components.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.POINTER(vp)]
         L.mhx_emcee_create.argtypes = [vp, vp, C.POINTER(EmceeCfg), C.POINTER(vp)]
         L.mhx_ram_create.argtypes = [vp, vp, C.POINTER(RamCfg), C.POINTER(vp)]
         L.mhx_mala_create.argtypes = [vp, vp, C.POINTER(MalaCfg), C.POINTER(vp)]

@@ -41,19 +41,159 @@ def zeros(d):
 
 
 class Normal:
+    family = L.FAMILY_NORMAL
+
     def __init__(self, mu=0.0, sigma=1.0):
         self.mu, self.sigma = float(mu), float(sigma)
 
     def rand(self, rng):
         return self.mu + self.sigma * rng.standard_normal()
 
+    def params(self):
+        return self.mu, self.sigma
+
 
 class InverseGamma:
-    def __init__(self, shape, scale):
+    family = L.FAMILY_INVERSE_GAMMA
+
+    def __init__(self, shape=1.0, scale=1.0):
         self.shape, self.scale = float(shape), float(scale)
 
     def rand(self, rng):
         return self.scale / rng.gamma(self.shape)
+
+    def params(self):
+        return self.shape, self.scale
+
+
+# The other univariate families a proposal component may be (src/proposal.jl:23-35 with a vector of Distributions univariates;
+# test/runtests.jl:188-189,266-271), parameters as in Distributions.jl.  `rand` is the host draw (ensemble initialisation); as a
+# component of a RandomWalkProposal / StaticProposal they are drawn on the device.
+class Uniform:
+    family = L.FAMILY_UNIFORM
+
+    def __init__(self, a=0.0, b=1.0):
+        self.a, self.b = float(a), float(b)
+
+    def rand(self, rng):
+        return self.a + (self.b - self.a) * rng.random()
+
+    def params(self):
+        return self.a, self.b
+
+
+class Laplace:
+    family = L.FAMILY_LAPLACE
+
+    def __init__(self, mu=0.0, theta=1.0):
+        self.mu, self.theta = float(mu), float(theta)
+
+    def rand(self, rng):
+        return rng.laplace(self.mu, self.theta)
+
+    def params(self):
+        return self.mu, self.theta
+
+
+class Cauchy:
+    family = L.FAMILY_CAUCHY
+
+    def __init__(self, mu=0.0, sigma=1.0):
+        self.mu, self.sigma = float(mu), float(sigma)
+
+    def rand(self, rng):
+        return self.mu + self.sigma * rng.standard_cauchy()
+
+    def params(self):
+        return self.mu, self.sigma
+
+
+class Exponential:
+    family = L.FAMILY_EXPONENTIAL
+
+    def __init__(self, theta=1.0):
+        self.theta = float(theta)
+
+    def rand(self, rng):
+        return rng.exponential(self.theta)
+
+    def params(self):
+        return self.theta, 0.0
+
+
+class Gamma:
+    family = L.FAMILY_GAMMA
+
+    def __init__(self, alpha=1.0, theta=1.0):
+        self.alpha, self.theta = float(alpha), float(theta)
+
+    def rand(self, rng):
+        return rng.gamma(self.alpha, self.theta)
+
+    def params(self):
+        return self.alpha, self.theta
+
+
+class TDist:
+    """TDist(nu).  As a proposal component only nu = 1 is lowered: it IS Cauchy(0, 1)."""
+
+    def __init__(self, nu):
+        self.nu = float(nu)
+
+    def rand(self, rng):
+        return rng.standard_t(self.nu)
+
+
+_UNIVARIATES = (Normal, Uniform, Laplace, Cauchy, Exponential, Gamma, InverseGamma)
+
+
+def _lower_univariate(dist):
+    """a univariate of one of the device families, checked: TDist(1) -> Cauchy(0, 1); bad parameters raise"""
+    if isinstance(dist, TDist):
+        if dist.nu != 1.0:
+            raise L.ArgumentError(L.MHX_EINVAL, "TDist(%g): only TDist(1) = Cauchy(0, 1) is lowered to the device; any other number of "
+                                  "degrees of freedom has no device sampler" % dist.nu)
+        return Cauchy(0.0, 1.0)
+    if not isinstance(dist, _UNIVARIATES):
+        return None
+    p0, p1 = dist.params()
+    name = type(dist).__name__
+    ok = math.isfinite(p0) and math.isfinite(p1)
+    if isinstance(dist, Uniform):
+        ok = ok and p0 < p1
+    elif isinstance(dist, Exponential):
+        ok = ok and p0 > 0
+    elif isinstance(dist, (Gamma, InverseGamma)):
+        ok = ok and p0 > 0 and p1 > 0
+    else:
+        ok = ok and p1 > 0
+    if not ok:
+        raise L.ArgumentError(L.MHX_EINVAL, "%s%r: bad parameters (scale and shape parameters must be positive, Uniform needs a < b, "
+                              "everything finite)" % (name, dist.params() if not isinstance(dist, Exponential) else (p0,)))
+    return dist
+
+
+class ComponentProposal:
+    """A proposal distribution made of independent univariate components, at least one of them not Normal: what
+    RandomWalkProposal / StaticProposal hold for `[Normal(0, 1), InverseGamma(2, 3)]`, `Laplace()`, ... (an all-Normal vector is an
+    MvNormal, as before).  `table()` is the component table of mhx_rwmh_create_components."""
+
+    def __init__(self, comps):
+        self.comps = list(comps)
+        self.dim = len(self.comps)
+
+    def table(self):
+        return [(c.family,) + tuple(c.params()) for c in self.comps]
+
+    def symmetric_about_zero(self):
+        def sym(c):
+            if isinstance(c, (Normal, Laplace, Cauchy)):
+                return c.params()[0] == 0
+            return isinstance(c, Uniform) and c.a == -c.b
+        return all(sym(c) for c in self.comps)
+
+    def rand(self, rng):
+        return np.array([c.rand(rng) for c in self.comps])
 
 
 class MvNormal:
@@ -113,8 +253,25 @@ def _as_mvnormal(dist):
     if isinstance(dist, (list, tuple)) and all(isinstance(p, Normal) for p in dist):
         mv = MvNormal([p.mu for p in dist], np.array([p.sigma ** 2 for p in dist]))
         return mv
-    raise L.ArgumentError(L.MHX_EINVAL, "the GPU path supports MvNormal / vector-of-Normal random-walk proposals; "
-                          "got %r (static, function and NamedTuple proposals stay on the CPU reference)" % (dist,))
+    raise L.ArgumentError(L.MHX_EINVAL, "the GPU path supports MvNormal / vector-of-Normal proposals here; "
+                          "got %r (function proposals stay on the CPU reference)" % (dist,))
+
+
+def _as_proposal(dist):
+    """What a RandomWalkProposal / StaticProposal holds: an MvNormal (everything _as_mvnormal takes, exactly as it lowers it), or a
+    ComponentProposal for one univariate of a device family / a vector mixing them with Normals."""
+    if isinstance(dist, ComponentProposal):
+        return dist
+    one = None if isinstance(dist, Normal) else _lower_univariate(dist)
+    if one is not None:
+        return ComponentProposal([one])
+    if isinstance(dist, (list, tuple)) and len(dist) and not all(isinstance(p, Normal) for p in dist):
+        comps = [_lower_univariate(p) for p in dist]
+        if any(c is None for c in comps):
+            raise L.ArgumentError(L.MHX_EINVAL, "a vector proposal takes Normal, Uniform, Laplace, Cauchy, Exponential, Gamma, InverseGamma "
+                                  "or TDist(1) components; got %r" % (dist,))
+        return ComponentProposal(comps)
+    return _as_mvnormal(dist)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -310,11 +467,14 @@ class RandomWalkProposal:
     """RandomWalkProposal{issymmetric}(dist) -- src/proposal.jl:13-21."""
 
     def __init__(self, proposal, issymmetric=False):
-        self.proposal = _as_mvnormal(proposal)
+        self.proposal = _as_proposal(proposal)
         self.issymmetric = issymmetric
         # a non-zero mean makes the walk drift; its Hastings ratio (src/proposal.jl:58-64,190-192) is then
         # evaluated on the device (generic kernel).  Declaring such a proposal symmetric would skip it.
-        if issymmetric and np.any(self.proposal.mean != 0):
+        if isinstance(self.proposal, ComponentProposal):
+            if issymmetric and not self.proposal.symmetric_about_zero():
+                raise L.ArgumentError(L.MHX_EINVAL, "a random-walk proposal with a component that is not symmetric about zero is not symmetric")
+        elif issymmetric and np.any(self.proposal.mean != 0):
             raise L.ArgumentError(L.MHX_EINVAL, "a random-walk proposal with a non-zero mean is not symmetric")
 
 
@@ -325,18 +485,20 @@ def SymmetricRandomWalkProposal(proposal):
 class StaticProposal:
     """StaticProposal(dist) -- src/proposal.jl:9-11: every candidate is a fresh draw from `dist`, whatever the
     current state (independence sampler); the acceptance ratio carries logpdf(dist, x) - logpdf(dist, y)
-    (src/proposal.jl:66-83).  `dist`: Normal / list of Normals / MvNormal."""
+    (src/proposal.jl:66-83).  `dist`: Normal / list of Normals / MvNormal, or a univariate of a device family / a list mixing them
+    with Normals (README.md:106: StaticProposal([Normal(0, 1), InverseGamma(2, 3)]))."""
 
     issymmetric = False
 
     def __init__(self, proposal):
-        self.proposal = _as_mvnormal(proposal)
+        self.proposal = _as_proposal(proposal)
 
 
 class MetropolisHastings:
     """MetropolisHastings(proposal) -- src/mh-core.jl:44-46.  `proposal`: a RandomWalkProposal / StaticProposal, or -- the
-    reference's NamedTuple of proposals, test/runtests.jl:136-160, :187 -- a dict {name: proposal} of scalar Normal proposals
-    of ONE kind (all random-walk or all static); its keys name the parameters (src/AdvancedMH.jl:96-104)."""
+    reference's NamedTuple of proposals, test/runtests.jl:136-160, :187-189 -- a dict {name: proposal} of scalar proposals
+    of ONE kind (all random-walk or all static; Normal or any other device family); its keys name the parameters
+    (src/AdvancedMH.jl:96-104)."""
 
     def __init__(self, proposal):
         self.param_names = None
@@ -350,8 +512,14 @@ class MetropolisHastings:
             parts = list(proposal.values())
             if any(q.proposal.dim != 1 for q in parts):
                 raise L.ArgumentError(L.MHX_EINVAL, "a NamedTuple of proposals takes one scalar Normal per name")
-            mv = MvNormal([float(q.proposal.mean[0]) for q in parts],
-                          np.array([float(q.proposal.vec[0]) ** 2 if q.proposal.kind == L.PROP_DIAG else q.proposal.scale ** 2 for q in parts]))
+            if any(isinstance(q.proposal, ComponentProposal) for q in parts):
+                # a name with a non-Normal scalar proposal (test/runtests.jl:189): the component vector, Normals by their (mu, sigma)
+                mv = ComponentProposal([q.proposal.comps[0] if isinstance(q.proposal, ComponentProposal) else
+                                        Normal(float(q.proposal.mean[0]), float(q.proposal.vec[0]) if q.proposal.kind == L.PROP_DIAG else q.proposal.scale)
+                                        for q in parts])
+            else:
+                mv = MvNormal([float(q.proposal.mean[0]) for q in parts],
+                              np.array([float(q.proposal.vec[0]) ** 2 if q.proposal.kind == L.PROP_DIAG else q.proposal.scale ** 2 for q in parts]))
             self.param_names = [str(k) for k in proposal]
             if kinds == {StaticProposal}:
                 proposal = StaticProposal(mv)
@@ -359,7 +527,7 @@ class MetropolisHastings:
                 proposal = RandomWalkProposal(mv, all(q.issymmetric for q in parts))
         if not isinstance(proposal, (RandomWalkProposal, StaticProposal)):
             raise L.ArgumentError(L.MHX_EINVAL, "the GPU path implements RandomWalkProposal and StaticProposal "
-                                  "over (Mv)Normal distributions only")
+                                  "over (Mv)Normal distributions and vectors of univariate components only")
         self.proposal = proposal
 
 
@@ -540,13 +708,21 @@ class Run:
             mv = sampler.proposal.proposal
             if mv.dim != d:
                 raise L.ArgumentError(L.MHX_EINVAL, "proposal dimension %d != model dimension %d" % (mv.dim, d))
-            vec = None if mv.vec is None else f32(mv.vec)
-            mean = f32(mv.mean) if np.any(mv.mean != 0) else None
-            self._keep += [vec, mean]
             if isinstance(sampler.proposal, StaticProposal):
                 flags |= L.MHX_FLAG_STATIC_PROPOSAL
-            cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
-            L.check(lib.mhx_rwmh_create(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(self.h)))
+            if isinstance(mv, ComponentProposal):
+                # univariate family components: their own entry point, the (Mv)Normal fields of the configuration unused
+                if sampler.proposal.issymmetric:
+                    flags |= L.FLAG_SYMMETRIC_PROPOSAL
+                tab = (L.ProposalComponent * mv.dim)(*[L.ProposalComponent(f, 0, p0, p1) for f, p0, p1 in mv.table()])
+                cfg = L.RwmhCfg(d, nchains, seed, first_chain, L.PROP_ISO, 1.0, None, flags, None, reduce_lanes)
+                L.check(lib.mhx_rwmh_create_components(self.ctx.h, model.handle(self.ctx), C.byref(cfg), tab, mv.dim, C.byref(self.h)))
+            else:
+                vec = None if mv.vec is None else f32(mv.vec)
+                mean = f32(mv.mean) if np.any(mv.mean != 0) else None
+                self._keep += [vec, mean]
+                cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
+                L.check(lib.mhx_rwmh_create(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(self.h)))
             self.n = nchains
             self.kind = "rwmh"
         elif isinstance(sampler, Ensemble):

@@ -207,6 +207,39 @@ typedef struct {
 
 int mhx_rwmh_create(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, mhx_run **out);
 
+/* A proposal made of independent univariate components (src/proposal.jl:23-35 with a vector of Distributions univariates): component
+ * k of a RandomWalkProposal / StaticProposal is one of the families below, its two parameters as in Distributions.jl (Exponential
+ * has one; sigma, theta, alpha > 0, a < b, all finite).  The draws, the streams they take their bits from and the unnormalised
+ * log-kernels the acceptance ratio sums are the arithmetic spec's section 3.13. */
+typedef enum {
+    MHX_FAMILY_NORMAL = 0,        /* Normal(mu, sigma) */
+    MHX_FAMILY_UNIFORM = 1,       /* Uniform(a, b) */
+    MHX_FAMILY_LAPLACE = 2,       /* Laplace(mu, theta) */
+    MHX_FAMILY_CAUCHY = 3,        /* Cauchy(mu, sigma); TDist(1) is Cauchy(0, 1) */
+    MHX_FAMILY_EXPONENTIAL = 4,   /* Exponential(theta): p0 = theta, p1 unused */
+    MHX_FAMILY_GAMMA = 5,         /* Gamma(alpha, theta) */
+    MHX_FAMILY_INVERSE_GAMMA = 6  /* InverseGamma(alpha, theta) */
+} mhx_family;
+
+typedef struct {
+    int32_t family;   /* one of mhx_family */
+    int32_t reserved; /* 0 */
+    double p0;
+    double p1;
+} mhx_proposal_component;
+
+#define MHX_FLAG_SYMMETRIC_PROPOSAL 128 /* mhx_rwmh_create_components, random walk only: the proposal was declared symmetric
+                                           (RandomWalkProposal{true}, src/proposal.jl:195) -- the ratio q(x - y) - q(y - x) is not formed */
+
+/* An RWMH run whose proposal is comps[0 .. ncomps-1], ncomps == cfg->dim; cfg->proposal_kind / _scale / _vec / _mean are ignored,
+ * MHX_FLAG_STATIC_PROPOSAL selects y = xi with the ratio q(x) - q(y) (else y = x + xi with q(x - y) - q(y - x)).  One lane per chain,
+ * Box-Muller normals: MHX_FLAG_ZIGGURAT, reduce_lanes > 1, a bad parameter and (at mhx_run_sample) MHX_SAVE_MOMENTS are MHX_EINVAL.
+ * Kernel variant 13 in both of its forms: run-time specialised to the pattern of families with the state in registers (dim <= 32 in
+ * fp64, 48 in fp32: what compiles without scratch memory), or -- MHX_FLAG_GENERIC / MHX_FLAG_NO_JIT / larger dim -- the pre-built state-in-HBM form; the same chain bit for
+ * bit.  A one-sided family in a random walk never accepts (q(x - y) = -Inf), exactly as the reference behaves. */
+int mhx_rwmh_create_components(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_proposal_component *comps,
+                               int32_t ncomps, mhx_run **out);
+
 /* ---------------------------------------------------------------------------------------------
  * Affine-invariant ensemble.  Replaces Ensemble{StretchProposal} (src/emcee.jl:1-4, :63-68), its
  * step (:14-24), sweep (:39-58) and stretch move (:70-102).  The device sweep is the parallel
@@ -417,7 +450,9 @@ typedef struct {
                                   11 a WAVE per chain (RWMH on the data-sum target MHX_TARGET_IID_NORMAL with few chains -- the
                                   reference's own README example, one chain: the 64 lanes split the likelihood's terms, the draws of
                                   64 steps are made side by side off the chain's critical path; reduction shape 64),
-                                  12 RAM with a deferred factor (MHX_FLAG_RAM_DEFERRED) */
+                                  12 RAM with a deferred factor (MHX_FLAG_RAM_DEFERRED),
+                                  13 a proposal of univariate family components (mhx_rwmh_create_components), lane per chain: the
+                                  run-time specialised register form or the pre-built state-in-HBM form, the same chain */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
