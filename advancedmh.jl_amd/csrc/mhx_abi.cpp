@@ -191,6 +191,17 @@ extern "C" int mhx_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, con
                      : mhx_f32::api_rwmh_create_components(C32(ctx), CT32(t), cfg, comps, ncomps, reinterpret_cast<mhx_f32::mhx_run**>(out));
 }
 
+extern "C" int mhx_rwmh_create_conditional(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
+                                           int32_t ncomps, const char* params_src, const void* data, size_t ndata, mhx_run** out)
+{
+    NEED(ctx, "mhx_rwmh_create_conditional");
+    if (!same(ctx, t)) return MIXED("mhx_rwmh_create_conditional");
+    return is64(ctx) ? mhx_f64::api_rwmh_create_conditional(C64(ctx), CT64(t), cfg, comps, ncomps, params_src, CD(data), ndata,
+                                                            reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_rwmh_create_conditional(C32(ctx), CT32(t), cfg, comps, ncomps, params_src, CF(data), ndata,
+                                                            reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
+
 extern "C" int mhx_ram_set_factor(mhx_run* r, const void* S)
 {
     NEED(r, "mhx_ram_set_factor");

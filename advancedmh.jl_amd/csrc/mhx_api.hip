@@ -26,6 +26,7 @@
 
 #include "mhx_rwmh_kernels.h"
 #include "mhx_rwmh_family_kernels.h"
+#include "mhx_rwmh_cond_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
 #include "mhx_mala_kernels.h"
@@ -466,11 +467,12 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
     const char* hdr_src[] = {k_src_mhx_zig_table_h, k_src_mhx_device_math_h, k_src_mhx_targets_h, k_src_mhx_rwmh_kernels_h,
                              k_src_mhx_emcee_kernels_h, k_src_mhx_ram_kernels_h, k_src_mhx_mala_kernels_h,
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
-                             k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h};
+                             k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
+                             k_src_mhx_rwmh_cond_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
-                              "mhx_rwmh_family_kernels.h"};
+                              "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -806,6 +808,7 @@ enum kernel_form {
     KF_WAVE = 11,           // a wave per chain
     KF_RAM_DEFER = 12,      // RAM with a deferred factor
     KF_FAMILY = 13,         // a proposal of univariate family components: specialised register form or state in HBM
+    KF_COND = 14,           // ... whose parameters are a function of the state (a conditional proposal): the same two forms
 };
 
 struct mhx_run : mhx_handle_hdr {
@@ -833,6 +836,13 @@ struct mhx_run : mhx_handle_hdr {
     mhx_fam_comp* d_fam = nullptr;          // KF_FAMILY: the component table [dim]
     bool fam_reg = false;                   // ... stepped by the specialised register form (jit_step), else by the state-in-HBM form
     int fam_symmetric = 0;                  // ... a random walk declared symmetric: no ratio
+    // KF_COND (mhx_api_cond.inc): d_fam, fam_reg and fam_symmetric as above, and
+    std::string cond_src;                   // the parameter map's source (MHX_PROPOSAL_PARAMS)
+    mhx_real* d_cond_data = nullptr;        // its data block
+    int cond_ndata = 0;
+    mhx_real* d_cond_p = nullptr;           // [2 dim][n] p(x) of the check kernel; the state-in-HBM form: [4 dim][n], p(x) then p(y)
+    int* d_cond_bad = nullptr;              // chains whose p(x) the last check found invalid
+    hipFunction_t jit_cond_check = nullptr;
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -905,7 +915,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad};
         for (void* p : ptrs) if (p) (void)hipFree(p);
     }
 };
@@ -950,8 +960,10 @@ k_rwmh_whiten(const mhx_rwmh_args a, const mhx_real* __restrict__ pvec)
     mhx_rwmh_whiten_body(a, pvec);
 }
 // logpdf of a static proposal at the current states (after init / set_state)
+static int cond_check(mhx_run* r);
 static int rwmh_whiten(mhx_run* r)
 {
+    if (r->variant == KF_COND) return cond_check(r);         // no cached q(x); p(x) must be a distribution's
     if (!r->d_qx) return MHX_OK;
     mhx_rwmh_args a = rwmh_args(r);
     if (r->variant == KF_FAMILY)
@@ -1337,26 +1349,12 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     return MHX_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// A proposal of independent univariate components (include/mhx.h: mhx_rwmh_create_components; DESIGN.md section 3.13)
-int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
-                               int32_t ncomps, mhx_run** out)
+// the component table of a family proposal: parameters and what the kernels derive from them once, in double, each rounded once
+// to the engine's width; `pattern` is the comma-separated list of families (MHX_JIT_FAM_LIST)
+static int fam_build_table(const char* me, const mhx_proposal_component* comps, const int d, std::vector<mhx_fam_comp>& tab, std::string& pattern)
 {
-    const char* me = "mhx_rwmh_create_components";
-    if (!ctx || !t || !cfg || !comps || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
-    if (cfg->dim != t->dim) return mhx_fail(MHX_EINVAL, "%s: proposal dim %d != model dim %d", me, cfg->dim, t->dim);
-    if (ncomps != cfg->dim) return mhx_fail(MHX_EINVAL, "%s: %d components for dim %d (one component per parameter)", me, ncomps, cfg->dim);
-    if (cfg->nchains <= 0) return mhx_fail(MHX_EINVAL, "%s: nchains must be positive", me);
-    if (cfg->flags & MHX_FLAG_ZIGGURAT)
-        return mhx_fail(MHX_EINVAL, "%s: MHX_FLAG_ZIGGURAT -- a family run draws its Normal components by Box-Muller only", me);
-    if (cfg->reduce_lanes > 1)
-        return mhx_fail(MHX_EINVAL, "%s: reduce_lanes = %d -- a family run is one lane per chain (reduce_lanes 0 or 1)", me, cfg->reduce_lanes);
-    const int d = cfg->dim;
-    if (d >= (1 << 20)) return mhx_fail(MHX_EINVAL, "%s: dim must be below 2^20 (the Gamma blocks are numbered component << 8 | attempt)", me);
-    const bool stat = (cfg->flags & MHX_FLAG_STATIC_PROPOSAL) != 0;
-    // the table: parameters and what the kernels derive from them once, in double, each rounded once to the engine's width
-    std::vector<mhx_fam_comp> tab((size_t)d);
-    std::string pattern;
+    tab.assign((size_t)d, mhx_fam_comp{});
+    pattern.clear();
     for (int k = 0; k < d; ++k) {
         const mhx_proposal_component& c = comps[k];
         const double p0 = c.p0, p1 = c.p1;
@@ -1398,6 +1396,29 @@ int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh
         if (k) pattern += ',';
         pattern += std::to_string(c.family);
     }
+    return MHX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A proposal of independent univariate components (include/mhx.h: mhx_rwmh_create_components; DESIGN.md section 3.13)
+int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
+                               int32_t ncomps, mhx_run** out)
+{
+    const char* me = "mhx_rwmh_create_components";
+    if (!ctx || !t || !cfg || !comps || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
+    if (cfg->dim != t->dim) return mhx_fail(MHX_EINVAL, "%s: proposal dim %d != model dim %d", me, cfg->dim, t->dim);
+    if (ncomps != cfg->dim) return mhx_fail(MHX_EINVAL, "%s: %d components for dim %d (one component per parameter)", me, ncomps, cfg->dim);
+    if (cfg->nchains <= 0) return mhx_fail(MHX_EINVAL, "%s: nchains must be positive", me);
+    if (cfg->flags & MHX_FLAG_ZIGGURAT)
+        return mhx_fail(MHX_EINVAL, "%s: MHX_FLAG_ZIGGURAT -- a family run draws its Normal components by Box-Muller only", me);
+    if (cfg->reduce_lanes > 1)
+        return mhx_fail(MHX_EINVAL, "%s: reduce_lanes = %d -- a family run is one lane per chain (reduce_lanes 0 or 1)", me, cfg->reduce_lanes);
+    const int d = cfg->dim;
+    if (d >= (1 << 20)) return mhx_fail(MHX_EINVAL, "%s: dim must be below 2^20 (the Gamma blocks are numbered component << 8 | attempt)", me);
+    const bool stat = (cfg->flags & MHX_FLAG_STATIC_PROPOSAL) != 0;
+    std::vector<mhx_fam_comp> tab;
+    std::string pattern;
+    { const int rct = fam_build_table(me, comps, d, tab, pattern); if (rct) return rct; }
     HIP_TRY(hipSetDevice(ctx->device));
     std::unique_ptr<mhx_run> r(new mhx_run);
     r->dtype = ctx->dtype;
@@ -1445,6 +1466,8 @@ int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh
     return MHX_OK;
 }
 
+#include "mhx_api_cond.inc"
+
 // ---- emcee / ram creation, init and stepping live in their own sections below
 static int emcee_init(mhx_run* r, const mhx_real* init);
 static int emcee_sync_state(mhx_run* r, int to_abi);
@@ -1479,6 +1502,9 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
 {
     mhx_ctx* ctx = r->ctx;
     const size_t nx = (size_t)r->dim * (size_t)r->n;
+    if (r->variant == KF_COND && !init)
+        return mhx_fail(MHX_EINVAL, "mhx_run_init: a conditional proposal has no distribution to draw the first state from -- "
+                                "give initial_params (as for MALA)");
     if (init) {
         HIP_TRY(hipMemcpyAsync(r->d_x, init, nx * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
         int rcz = rwmh_canonical_zero(r);
@@ -1522,7 +1548,10 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->variant == KF_FAMILY) {
+        if (r->variant == KF_COND) {
+            int rc = cond_launch(r, a);
+            if (rc) return rc;
+        } else if (r->variant == KF_FAMILY) {
             const mhx_fam_comp* fam = r->d_fam;
             int sym = r->fam_symmetric;
             if (r->fam_reg) {
@@ -1690,6 +1719,9 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->rec_loga_view = nullptr;
     if (save_samples == MHX_SAVE_MOMENTS) {
         // running moments instead of a sample tensor
+        if (r->kind == RUN_RWMH && r->variant == KF_COND)
+            return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run with a conditional proposal "
+                                    "(kernel variant 14): record samples");
         if (r->kind == RUN_RWMH && r->variant == KF_FAMILY)
             return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run whose proposal is a vector of family "
                                     "components (kernel variant 13): record samples");

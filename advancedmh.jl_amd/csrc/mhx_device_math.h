@@ -63,6 +63,15 @@ MHX_NS_BEGIN
     MHX_DEV mhx_real mhx_user_logdensity_and_gradient(const MHX_X& x, const MHX_G& g, const int d,              \
                                                       const mhx_real* __restrict__ data, const int ndata)
 
+// the parameter map of a conditional proposal in HIP source form (include/mhx.h, mhx_rwmh_create_conditional; DESIGN.md section
+// 3.14): reads the state x[0 .. d-1] and writes p.set(k, j, value), j = 0 or 1, parameter j of component k as in Distributions.jl.
+// An entry the source does not set keeps the constant of the component table; p.set(k, 0, .) on a Gamma or InverseGamma component
+// (its shape) has no effect.  One text serves both kernel forms and both widths: x and p are whatever the kernel passes.
+#define MHX_PROPOSAL_PARAMS(x, p, d, data, ndata)                                                              \
+    template <class MHX_X, class MHX_P>                                                                        \
+    MHX_DEV void mhx_user_proposal_params(const MHX_X& x, const MHX_P& p, const int d,                         \
+                                          const mhx_real* __restrict__ data, const int ndata)
+
 // wave-uniform base pointer + 32-bit per-lane BYTE offset: lowers to the scalar-base addressing mode
 // (global_load/store v_off, ..., s[base:base+1]) instead of a 64-bit vector address per access
 MHX_DEV mhx_real mhx_ld_off(const mhx_real* base, mhx_u32 byte_off)
@@ -946,6 +955,28 @@ MHX_DEV mhx_real mhx_fam_logk(const int family, const mhx_real* __restrict__ p, 
     if (family == MHX_FAMILY_EXPONENTIAL) return v >= MHX_R(0.0) ? -(v / p[0]) : -MHX_INF;
     if (family == MHX_FAMILY_GAMMA) return v > MHX_R(0.0) ? mhx_fma(p[5], mhx_log(v), -(v / p[1])) : -MHX_INF;
     return v > MHX_R(0.0) ? mhx_fma(p[5], mhx_log(v), -(p[1] / v)) : -MHX_INF;         // InverseGamma
+}
+
+// A conditional proposal has parameters that depend on the state, so two more functions of a row:
+// whether the parameters are those of a distribution (what the constructors of Distributions.jl check: sigma, theta > 0, a < b,
+// everything finite; the shape of a Gamma family is a constant the host checked), and the log-normaliser z, the part of logpdf
+// that depends on the parameters and not on the argument -- minus the constants (log 2, log pi, lgamma alpha) that cancel between
+// the two directions of a transition.  Uniform reads p[2] = b - a.
+MHX_DEV bool mhx_fam_finite(const mhx_real v) { return mhx_abs(v) < MHX_INF; }
+MHX_DEV bool mhx_fam_valid(const int family, const mhx_real* __restrict__ p)
+{
+    if (family == MHX_FAMILY_UNIFORM) return mhx_fam_finite(p[0]) && mhx_fam_finite(p[1]) && p[0] < p[1];
+    if (family == MHX_FAMILY_EXPONENTIAL) return mhx_fam_finite(p[0]) && p[0] > MHX_R(0.0);
+    if (family == MHX_FAMILY_GAMMA || family == MHX_FAMILY_INVERSE_GAMMA) return mhx_fam_finite(p[1]) && p[1] > MHX_R(0.0);
+    return mhx_fam_finite(p[0]) && mhx_fam_finite(p[1]) && p[1] > MHX_R(0.0);                 // Normal, Laplace, Cauchy
+}
+MHX_DEV mhx_real mhx_fam_lognorm(const int family, const mhx_real* __restrict__ p)
+{
+    if (family == MHX_FAMILY_UNIFORM) return -mhx_log(p[2]);
+    if (family == MHX_FAMILY_EXPONENTIAL) return -mhx_log(p[0]);
+    if (family == MHX_FAMILY_GAMMA) return -(p[0] * mhx_log(p[1]));
+    if (family == MHX_FAMILY_INVERSE_GAMMA) return p[0] * mhx_log(p[1]);
+    return -mhx_log(p[1]);                                                                    // Normal, Laplace, Cauchy
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -31,8 +31,9 @@ MHX_NS_BEGIN
 // the candidate of one transition (sbase = MHX_STREAM_FAMILY) or the initial draw (MHX_STREAM_FAMILY_INIT): xi[k] for k < d through
 // `put(k, xi)`.  `famof(k)` is the family of component k -- a table read here, a constant in the specialised kernel.
 // UNROLL: the dimension is a compile-time constant and the component loop is unrolled whatever its size (candidate in registers).
-template <bool UNROLL, class FamOf, class Put>
-MHX_DEV void mhx_fam_draw_all(const int d, const FamOf& famof, const mhx_fam_comp* __restrict__ fam, const mhx_philox_key& ks,
+// `fam[k].p` is the parameter row of component k: the table itself here, a lane's own rows in mhx_rwmh_cond_kernels.h.
+template <bool UNROLL, class FamOf, class Tab, class Put>
+MHX_DEV void mhx_fam_draw_all(const int d, const FamOf& famof, const Tab& fam, const mhx_philox_key& ks,
                               const mhx_u32 id_lo, const mhx_u32 id_hi, const mhx_u32 step, const mhx_u32 nstream, const mhx_u32 sbase,
                               const Put& put)
 {

@@ -119,7 +119,7 @@ EXPORTS = [
     "mhx_ctx_set_option", "mhx_ctx_get_option", "mhx_ctx_pci_bus_id", "mhx_run_shape", "mhx_comm_init_timed", "mhx_comm_set_timeout",
     "mhx_group_create", "mhx_group_destroy", "mhx_group_size", "mhx_group_ctx", "mhx_group_shard", "mhx_group_attach", "mhx_group_run",
     "mhx_group_init", "mhx_group_sample", "mhx_group_sample_to_host", "mhx_group_stats", "mhx_group_diagnostics", "mhx_group_ess_bulk_tail",
-    "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components",
+    "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components", "mhx_rwmh_create_conditional",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -181,6 +181,8 @@ def lib():
         L.mhx_target_eval.argtypes = [vp, vp, rp, C.c_int, rp]
         L.mhx_rwmh_create.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(vp)]
         L.mhx_rwmh_create_components.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.POINTER(vp)]
+        L.mhx_rwmh_create_conditional.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.c_char_p, rp,
+                                                  C.c_size_t, C.POINTER(vp)]
         L.mhx_emcee_create.argtypes = [vp, vp, C.POINTER(EmceeCfg), C.POINTER(vp)]
         L.mhx_ram_create.argtypes = [vp, vp, C.POINTER(RamCfg), C.POINTER(vp)]
         L.mhx_mala_create.argtypes = [vp, vp, C.POINTER(MalaCfg), C.POINTER(vp)]

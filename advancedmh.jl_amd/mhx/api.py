@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from . import trace as _trace
 
 # ------------------------------------------------------------------------------------------------
 # distributions (the subset of Distributions.jl the GPU path accepts)
@@ -40,11 +41,16 @@ def zeros(d):
     return np.zeros(int(d))
 
 
+def _param(v):
+    """a distribution's parameter: a number, or -- inside a function proposal being traced (mhx.trace.trace_proposal) -- a traced one"""
+    return v if isinstance(v, _trace.Sym) else float(v)
+
+
 class Normal:
     family = L.FAMILY_NORMAL
 
     def __init__(self, mu=0.0, sigma=1.0):
-        self.mu, self.sigma = float(mu), float(sigma)
+        self.mu, self.sigma = _param(mu), _param(sigma)
 
     def rand(self, rng):
         return self.mu + self.sigma * rng.standard_normal()
@@ -57,7 +63,7 @@ class InverseGamma:
     family = L.FAMILY_INVERSE_GAMMA
 
     def __init__(self, shape=1.0, scale=1.0):
-        self.shape, self.scale = float(shape), float(scale)
+        self.shape, self.scale = _param(shape), _param(scale)
 
     def rand(self, rng):
         return self.scale / rng.gamma(self.shape)
@@ -73,7 +79,7 @@ class Uniform:
     family = L.FAMILY_UNIFORM
 
     def __init__(self, a=0.0, b=1.0):
-        self.a, self.b = float(a), float(b)
+        self.a, self.b = _param(a), _param(b)
 
     def rand(self, rng):
         return self.a + (self.b - self.a) * rng.random()
@@ -86,7 +92,7 @@ class Laplace:
     family = L.FAMILY_LAPLACE
 
     def __init__(self, mu=0.0, theta=1.0):
-        self.mu, self.theta = float(mu), float(theta)
+        self.mu, self.theta = _param(mu), _param(theta)
 
     def rand(self, rng):
         return rng.laplace(self.mu, self.theta)
@@ -99,7 +105,7 @@ class Cauchy:
     family = L.FAMILY_CAUCHY
 
     def __init__(self, mu=0.0, sigma=1.0):
-        self.mu, self.sigma = float(mu), float(sigma)
+        self.mu, self.sigma = _param(mu), _param(sigma)
 
     def rand(self, rng):
         return self.mu + self.sigma * rng.standard_cauchy()
@@ -112,7 +118,7 @@ class Exponential:
     family = L.FAMILY_EXPONENTIAL
 
     def __init__(self, theta=1.0):
-        self.theta = float(theta)
+        self.theta = _param(theta)
 
     def rand(self, rng):
         return rng.exponential(self.theta)
@@ -125,7 +131,7 @@ class Gamma:
     family = L.FAMILY_GAMMA
 
     def __init__(self, alpha=1.0, theta=1.0):
-        self.alpha, self.theta = float(alpha), float(theta)
+        self.alpha, self.theta = _param(alpha), _param(theta)
 
     def rand(self, rng):
         return rng.gamma(self.alpha, self.theta)
@@ -254,14 +260,37 @@ def _as_mvnormal(dist):
         mv = MvNormal([p.mu for p in dist], np.array([p.sigma ** 2 for p in dist]))
         return mv
     raise L.ArgumentError(L.MHX_EINVAL, "the GPU path supports MvNormal / vector-of-Normal proposals here; "
-                          "got %r (function proposals stay on the CPU reference)" % (dist,))
+                          "got %r" % (dist,))
 
 
-def _as_proposal(dist):
+class ConditionalProposal:
+    """What a RandomWalkProposal / StaticProposal holds for a FUNCTION of the state (src/proposal.jl:92-126): `fn(x)` returns one
+    univariate (dim = 1, x a scalar) or a list of `dim` univariates whose parameters may depend on x.  It is traced once
+    (mhx.trace.trace_proposal): `.table()` is the component table, `.source` / `.data` the parameter map of
+    mhx_rwmh_create_conditional."""
+
+    def __init__(self, fn, dim):
+        if dim is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "a function proposal needs dim=: the number of parameters its function takes")
+        self.fn, self.dim = fn, int(dim)
+        self.traced = _trace.trace_proposal(fn, self.dim)
+        self.source, self.data = self.traced.source, self.traced.data
+        for fam, p0, p1 in self.traced.table:                 # the constants, checked like any component's
+            _lower_univariate(_UNIVARIATES[fam](p0) if fam == L.FAMILY_EXPONENTIAL else _UNIVARIATES[fam](p0, p1))
+
+    def table(self):
+        return list(self.traced.table)
+
+
+def _as_proposal(dist, dim=None):
     """What a RandomWalkProposal / StaticProposal holds: an MvNormal (everything _as_mvnormal takes, exactly as it lowers it), or a
     ComponentProposal for one univariate of a device family / a vector mixing them with Normals."""
-    if isinstance(dist, ComponentProposal):
+    if isinstance(dist, (ComponentProposal, ConditionalProposal)):
         return dist
+    if callable(dist):
+        return ConditionalProposal(dist, dim)
+    if dim is not None and not isinstance(dist, (list, tuple, np.ndarray, MvNormal)) and int(dim) != 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "dim = %d given with a scalar proposal" % dim)
     one = None if isinstance(dist, Normal) else _lower_univariate(dist)
     if one is not None:
         return ComponentProposal([one])
@@ -464,11 +493,15 @@ class Transition:
 
 
 class RandomWalkProposal:
-    """RandomWalkProposal{issymmetric}(dist) -- src/proposal.jl:13-21."""
+    """RandomWalkProposal{issymmetric}(dist) -- src/proposal.jl:13-21.  `dist` may be a function of the state that returns the
+    distribution(s) of the step, e.g. `lambda x: Normal(0, 0.5 + abs(x))` (src/proposal.jl:92-126); it then needs `dim=` and
+    `sample(..., initial_params=...)`, and `issymmetric=True` is the user's word that the ratio may be left out (:195)."""
 
-    def __init__(self, proposal, issymmetric=False):
-        self.proposal = _as_proposal(proposal)
-        self.issymmetric = issymmetric
+    def __init__(self, proposal, issymmetric=False, dim=None):
+        self.proposal = _as_proposal(proposal, dim)
+        self.issymmetric = bool(issymmetric)
+        if isinstance(self.proposal, ConditionalProposal):
+            return
         # a non-zero mean makes the walk drift; its Hastings ratio (src/proposal.jl:58-64,190-192) is then
         # evaluated on the device (generic kernel).  Declaring such a proposal symmetric would skip it.
         if isinstance(self.proposal, ComponentProposal):
@@ -478,20 +511,29 @@ class RandomWalkProposal:
             raise L.ArgumentError(L.MHX_EINVAL, "a random-walk proposal with a non-zero mean is not symmetric")
 
 
-def SymmetricRandomWalkProposal(proposal):
-    return RandomWalkProposal(proposal, True)
+def SymmetricRandomWalkProposal(proposal, dim=None):
+    return RandomWalkProposal(proposal, True, dim)
 
 
 class StaticProposal:
     """StaticProposal(dist) -- src/proposal.jl:9-11: every candidate is a fresh draw from `dist`, whatever the
     current state (independence sampler); the acceptance ratio carries logpdf(dist, x) - logpdf(dist, y)
     (src/proposal.jl:66-83).  `dist`: Normal / list of Normals / MvNormal, or a univariate of a device family / a list mixing them
-    with Normals (README.md:106: StaticProposal([Normal(0, 1), InverseGamma(2, 3)]))."""
+    with Normals (README.md:106: StaticProposal([Normal(0, 1), InverseGamma(2, 3)])), or a function of the state that returns
+    such (src/proposal.jl:92-126, `StaticProposal(lambda x: Normal(x, 1), dim=1)`): the ratio is then
+    q(x | y) - q(y | x) (:120-126), left out when `issymmetric` (StaticProposal{true}, :196)."""
 
-    issymmetric = False
+    def __init__(self, proposal, dim=None, issymmetric=False):
+        self.proposal = _as_proposal(proposal, dim)
+        self.issymmetric = bool(issymmetric)
+        if self.issymmetric and not isinstance(self.proposal, ConditionalProposal):
+            raise L.ArgumentError(L.MHX_EINVAL, "StaticProposal{true}: a static proposal is declared symmetric only as a function of the "
+                                  "state (a fixed distribution's ratio q(x) - q(y) is always formed)")
 
-    def __init__(self, proposal):
-        self.proposal = _as_proposal(proposal)
+
+def SymmetricStaticProposal(proposal, dim=None):
+    """SymmetricStaticProposal(f) = StaticProposal{true}(f) -- src/proposal.jl:11, test/runtests.jl:244."""
+    return StaticProposal(proposal, dim, True)
 
 
 class MetropolisHastings:
@@ -508,8 +550,11 @@ class MetropolisHastings:
             kinds = {type(p) for p in proposal.values()}
             if kinds not in ({RandomWalkProposal}, {StaticProposal}):
                 raise L.ArgumentError(L.MHX_EINVAL, "a NamedTuple of proposals is lowered when every entry is a RandomWalkProposal or "
-                                      "every entry is a StaticProposal (mixed / function proposals stay on the CPU reference)")
+                                      "every entry is a StaticProposal (mixed kinds stay on the CPU reference)")
             parts = list(proposal.values())
+            if any(isinstance(q.proposal, ConditionalProposal) for q in parts):
+                raise L.ArgumentError(L.MHX_EINVAL, "a NamedTuple of function proposals is not lowered: give one function of the whole "
+                                      "state that returns the list of components")
             if any(q.proposal.dim != 1 for q in parts):
                 raise L.ArgumentError(L.MHX_EINVAL, "a NamedTuple of proposals takes one scalar Normal per name")
             if any(isinstance(q.proposal, ComponentProposal) for q in parts):
@@ -527,7 +572,8 @@ class MetropolisHastings:
                 proposal = RandomWalkProposal(mv, all(q.issymmetric for q in parts))
         if not isinstance(proposal, (RandomWalkProposal, StaticProposal)):
             raise L.ArgumentError(L.MHX_EINVAL, "the GPU path implements RandomWalkProposal and StaticProposal "
-                                  "over (Mv)Normal distributions and vectors of univariate components only")
+                                  "over (Mv)Normal distributions, vectors of univariate components and functions of the state "
+                                  "that return such components")
         self.proposal = proposal
 
 
@@ -710,7 +756,17 @@ class Run:
                 raise L.ArgumentError(L.MHX_EINVAL, "proposal dimension %d != model dimension %d" % (mv.dim, d))
             if isinstance(sampler.proposal, StaticProposal):
                 flags |= L.MHX_FLAG_STATIC_PROPOSAL
-            if isinstance(mv, ComponentProposal):
+            if isinstance(mv, ConditionalProposal):
+                # a function of the state: the component table and the traced parameter map, its own entry point
+                if sampler.proposal.issymmetric:
+                    flags |= L.FLAG_SYMMETRIC_PROPOSAL
+                tab = (L.ProposalComponent * mv.dim)(*[L.ProposalComponent(f, 0, p0, p1) for f, p0, p1 in mv.table()])
+                data = None if mv.data is None else f32(mv.data)
+                self._keep += [data]
+                cfg = L.RwmhCfg(d, nchains, seed, first_chain, L.PROP_ISO, 1.0, None, flags, None, reduce_lanes)
+                L.check(lib.mhx_rwmh_create_conditional(self.ctx.h, model.handle(self.ctx), C.byref(cfg), tab, mv.dim,
+                                                        mv.source.encode(), L.fptr(data), 0 if data is None else data.size, C.byref(self.h)))
+            elif isinstance(mv, ComponentProposal):
                 # univariate family components: their own entry point, the (Mv)Normal fields of the configuration unused
                 if sampler.proposal.issymmetric:
                     flags |= L.FLAG_SYMMETRIC_PROPOSAL
@@ -778,6 +834,9 @@ class Run:
     # -- initial AbstractMCMC.step
     def init(self, initial_params=None):
         ip = None
+        if initial_params is None and self.kind == "rwmh" and isinstance(self.sampler.proposal.proposal, ConditionalProposal):
+            raise L.ArgumentError(L.MHX_EINVAL, "a function proposal has no distribution to draw the first state from: "
+                                  "give initial_params (as for MALA)")
         if initial_params is not None:
             ip = np.asarray(initial_params, dtype=self.real)
             if self.kind == "emcee" and ip.ndim == 2 and ip.shape == (self.n, self.dim) and self.n != self.dim:

@@ -30,7 +30,8 @@ import math
 
 import numpy as np
 
-__all__ = ["log", "exp", "sqrt", "abs", "fma", "where", "minimum", "maximum", "square", "sum_over", "trace", "Traced", "Sym", "Vec", "NamedVec", "TraceError"]
+__all__ = ["log", "exp", "sqrt", "abs", "fma", "where", "minimum", "maximum", "square", "sum_over", "trace", "Traced", "Sym", "Vec", "NamedVec", "TraceError",
+           "trace_proposal", "TracedProposal"]
 
 
 class TraceError(TypeError):
@@ -769,3 +770,105 @@ def trace(f, dim, gradient=True, names=None):
     if out.g is not g:
         raise TraceError("the returned value belongs to another trace")
     return Traced(g, out.i, dim, gradient)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# function proposals (src/proposal.jl:92-126): the parameter map of a conditional proposal, DESIGN.md section 3.14
+
+_FAMILY_NAMES = ("Normal", "Uniform", "Laplace", "Cauchy", "Exponential", "Gamma", "InverseGamma")
+_FAM_UNIFORM, _FAM_CAUCHY, _FAM_EXPONENTIAL, _FAM_GAMMA, _FAM_INVERSE_GAMMA = 1, 3, 4, 5, 6
+
+
+class TracedProposal(Traced):
+    """The recorded parameter map of a function proposal: `.families` (one mhx_family per component), `.table` ([(family, p0, p1)]:
+    the constants, and valid defaults where the source sets the entry), `.source` (MHX_PROPOSAL_PARAMS), `.data` (the rows of its
+    sum_over loops or None), `.evaluate(x)` ([(p0, p1)] of the same program in numpy float64, for checks).  Unpacks as
+    (families, table, source)."""
+
+    def __init__(self, g, sets, table, dim):
+        self.g, self.dim = g, int(dim)
+        self._ld = {}
+        self.grad = None
+        self.sets = sets                                    # [(component, parameter index, node)]
+        self.table = table
+        self.families = [f for f, _, _ in table]
+        self.data = np.concatenate(g.data) if g.data else None
+        lines, name = self._body([i for _, _, i in sets])
+        src = ["// traced by mhx.trace (advancedmh.jl_amd/mhx/trace.py): the parameter map of a proposal, %d operations in the source%s" % (
+                   self._nops, "" if self.data is None else "; data block of %d reals" % self.data.size),
+               "MHX_PROPOSAL_PARAMS(x, p, d, data, ndata)", "{"] + lines
+        src += ["    p.set(%d, %d, %s);" % (k, j, name(i)) for k, j, i in sets] + ["}"]
+        self.source = "\n".join(src) + "\n"
+
+    def __iter__(self):
+        return iter((self.families, self.table, self.source))
+
+    def evaluate(self, x):
+        x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+        out = [[p0, p1] for _, p0, p1 in self.table]
+        if self.sets:
+            for (k, j, _), v in zip(self.sets, self._run(x, [i for _, _, i in self.sets])):
+                out[k][j] = v
+        return [tuple(r) for r in out]
+
+
+def trace_proposal(fn, dim):
+    """Run `fn` -- a function of the state that returns one univariate distribution (dim = 1; the state is then a scalar) or a list
+    of `dim` of them (the state is a Vec) -- once over traced parameters, and return its families, constant table and kernel
+    source (a `TracedProposal`).  A distribution is anything with `.family` (an mhx_family) and `.params()`; TDist(1) is Cauchy(0, 1).
+    Each parameter is a number (it goes to the table) or a traced expression (it becomes a p.set of the source)."""
+    dim = int(dim)
+    if dim < 1:
+        raise TraceError("dim must be >= 1")
+    g = _Graph()
+    g.node("c", _const_key(0.0))
+    xs = [Sym(g, g.node("x", k)) for k in range(dim)]
+    _ACTIVE.append(g)
+    try:
+        out = fn(xs[0] if dim == 1 else Vec(xs))
+    finally:
+        _ACTIVE.pop()
+    if not isinstance(out, (list, tuple)):
+        out = [out]
+    if len(out) != dim:
+        raise TraceError("a function proposal of dimension %d must return %d univariate distributions (one per parameter), got %d" % (
+            dim, dim, len(out)))
+    sets, table = [], []
+    for k, dist in enumerate(out):
+        if hasattr(dist, "nu") and not hasattr(dist, "family"):                      # TDist
+            if dist.nu != 1.0:
+                raise TraceError("component %d: TDist(%g) -- only TDist(1) = Cauchy(0, 1) has a device sampler" % (k, dist.nu))
+            fam, params = _FAM_CAUCHY, (0.0, 1.0)
+        else:
+            fam = getattr(dist, "family", None)
+            if not isinstance(fam, int) or not 0 <= fam < len(_FAMILY_NAMES) or not hasattr(dist, "params"):
+                raise TraceError("component %d: %r is not one of the device families (%s, TDist(1))" % (k, dist, ", ".join(_FAMILY_NAMES)))
+            params = tuple(dist.params())
+        row = []
+        for j, v in enumerate(params):
+            if isinstance(v, Sym):
+                if v.g is not g:
+                    raise TraceError("component %d: the parameter belongs to another trace" % k)
+                if j == 0 and fam in (_FAM_GAMMA, _FAM_INVERSE_GAMMA):
+                    raise TraceError("component %d: the shape alpha of %s must not depend on the state (its lgamma would not cancel in "
+                                     "the ratio, and the sampler's constants are derived from it on the host)" % (k, _FAMILY_NAMES[fam]))
+                if j == 1 and fam == _FAM_EXPONENTIAL:
+                    raise TraceError("component %d: Exponential has one parameter" % k)
+                sets.append((k, j, v.i))
+                row.append(None)
+            elif isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
+                row.append(float(v))
+            else:
+                raise TraceError("component %d: parameter %d of %s is %r, not a number or a traced number" % (k, j, _FAMILY_NAMES[fam], v))
+        # an entry the source sets still needs a valid constant in the table: 0 for a location, 1 for a scale, a bound 1 away
+        if fam == _FAM_UNIFORM:
+            a, b = row
+            if a is None:
+                a = 0.0 if b is None else b - 1.0
+            if b is None:
+                b = a + 1.0
+            row = [a, b]
+        else:
+            row = [(0.0 if j == 0 and fam != _FAM_EXPONENTIAL else 1.0) if v is None else v for j, v in enumerate(row)]
+        table.append((fam, row[0], row[1]))
+    return TracedProposal(g, sets, table, dim)

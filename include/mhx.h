@@ -229,7 +229,8 @@ typedef struct {
 } mhx_proposal_component;
 
 #define MHX_FLAG_SYMMETRIC_PROPOSAL 128 /* mhx_rwmh_create_components, random walk only: the proposal was declared symmetric
-                                           (RandomWalkProposal{true}, src/proposal.jl:195) -- the ratio q(x - y) - q(y - x) is not formed */
+                                           (RandomWalkProposal{true}, src/proposal.jl:195) -- the ratio q(x - y) - q(y - x) is not formed.
+                                           mhx_rwmh_create_conditional: walk or static */
 
 /* An RWMH run whose proposal is comps[0 .. ncomps-1], ncomps == cfg->dim; cfg->proposal_kind / _scale / _vec / _mean are ignored,
  * MHX_FLAG_STATIC_PROPOSAL selects y = xi with the ratio q(x) - q(y) (else y = x + xi with q(x - y) - q(y - x)).  One lane per chain,
@@ -239,6 +240,31 @@ typedef struct {
  * bit.  A one-sided family in a random walk never accepts (q(x - y) = -Inf), exactly as the reference behaves. */
 int mhx_rwmh_create_components(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_proposal_component *comps,
                                int32_t ncomps, mhx_run **out);
+
+/* A CONDITIONAL proposal: the function proposals of src/proposal.jl:92-126 -- StaticProposal(x -> Normal(x, 1)),
+ * RandomWalkProposal(x -> Laplace(x, 1)).  Component k keeps the fixed family comps[k].family; its parameters are a function of the
+ * whole state, given as HIP source (the arithmetic: DESIGN.md section 3.14):
+ *
+ *     MHX_PROPOSAL_PARAMS(x, p, d, data, ndata) { p.set(0, 1, MHX_R(0.5) + x[0] * x[0]); }
+ *
+ * x[j] reads coordinate j of the state, p.set(k, j, value) sets parameter j (0 or 1, as in mhx_proposal_component) of component k, data
+ * points to the ndata reals (of the context's width) passed here.  An entry the source does not set keeps comps[k].p0 / p1, which
+ * must be valid parameters on their own.  The shape alpha of a Gamma / InverseGamma component cannot depend on the state (its lgamma
+ * would not cancel, and the sampler's constants are derived from it on the host): p.set(k, 0, .) on such a component has no effect.
+ * Every transition evaluates p at the candidate y and checks it (sigma, theta > 0, a < b, everything finite); a candidate whose
+ * parameters are not a distribution's is REJECTED -- the one departure from the reference, which would throw from the
+ * distribution's constructor at the next step.  The ratio is (K(p(y); x - y) - K(p(x); y - x)) + (Z(p(y)) - Z(p(x))) for a walk,
+ * (K(p(y); x) - K(p(x); y)) + (Z(p(y)) - Z(p(x))) with MHX_FLAG_STATIC_PROPOSAL; MHX_FLAG_SYMMETRIC_PROPOSAL (here allowed with a
+ * static proposal too: StaticProposal{true}, src/proposal.jl:195-196) leaves it out.  A map that sets nothing, or constants, runs the
+ * chain of mhx_rwmh_create_components bit for bit.
+ * Kernel variant 14, compiled at run time only, in two forms with the same chain: state, candidate and both parameter sets in
+ * registers (dim <= 20 in fp64, 32 in fp32: what compiles without scratch memory), or -- MHX_FLAG_GENERIC / larger dim -- in HBM.  MHX_EINVAL: MHX_FLAG_NO_JIT (nothing is
+ * pre-built), MHX_FLAG_ZIGGURAT, reduce_lanes > 1, MHX_SAVE_MOMENTS at mhx_run_sample, mhx_run_init without initial_params (there is no
+ * distribution to draw a first state from) and initial or mhx_run_set_state states at which p is not valid.  A compile error in
+ * params_src is MHX_EJIT with the compiler's log in mhx_last_error, as for mhx_target_from_hip_source; a user log-density and a
+ * parameter map compile together in one module. */
+int mhx_rwmh_create_conditional(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_proposal_component *comps,
+                                int32_t ncomps, const char *params_src, const void *data, size_t ndata, mhx_run **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Affine-invariant ensemble.  Replaces Ensemble{StretchProposal} (src/emcee.jl:1-4, :63-68), its
@@ -452,7 +478,9 @@ typedef struct {
                                   64 steps are made side by side off the chain's critical path; reduction shape 64),
                                   12 RAM with a deferred factor (MHX_FLAG_RAM_DEFERRED),
                                   13 a proposal of univariate family components (mhx_rwmh_create_components), lane per chain: the
-                                  run-time specialised register form or the pre-built state-in-HBM form, the same chain */
+                                  run-time specialised register form or the pre-built state-in-HBM form, the same chain,
+                                  14 a conditional proposal (mhx_rwmh_create_conditional), lane per chain, compiled at run time:
+                                  the register form or the state-in-HBM form, the same chain */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
