@@ -202,6 +202,18 @@ extern "C" int mhx_rwmh_create_conditional(mhx_ctx* ctx, const mhx_target* t, co
                                                             reinterpret_cast<mhx_f32::mhx_run**>(out));
 }
 
+extern "C" int mhx_rwmh_create_composite(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
+                                         int32_t ncomps, const mhx_proposal_block* blocks, int32_t nblocks, const int32_t* mapped,
+                                         const char* params_src, const void* data, size_t ndata, mhx_run** out)
+{
+    NEED(ctx, "mhx_rwmh_create_composite");
+    if (!same(ctx, t)) return MIXED("mhx_rwmh_create_composite");
+    return is64(ctx) ? mhx_f64::api_rwmh_create_composite(C64(ctx), CT64(t), cfg, comps, ncomps, blocks, nblocks, mapped, params_src,
+                                                          CD(data), ndata, reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_rwmh_create_composite(C32(ctx), CT32(t), cfg, comps, ncomps, blocks, nblocks, mapped, params_src,
+                                                          CF(data), ndata, reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
+
 extern "C" int mhx_ram_set_factor(mhx_run* r, const void* S)
 {
     NEED(r, "mhx_ram_set_factor");

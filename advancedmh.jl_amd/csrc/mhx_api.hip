@@ -27,6 +27,7 @@
 #include "mhx_rwmh_kernels.h"
 #include "mhx_rwmh_family_kernels.h"
 #include "mhx_rwmh_cond_kernels.h"
+#include "mhx_rwmh_composite_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
 #include "mhx_mala_kernels.h"
@@ -468,11 +469,11 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
                              k_src_mhx_emcee_kernels_h, k_src_mhx_ram_kernels_h, k_src_mhx_mala_kernels_h,
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
                              k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
-                             k_src_mhx_rwmh_cond_kernels_h};
+                             k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
-                              "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h"};
+                              "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -809,6 +810,7 @@ enum kernel_form {
     KF_RAM_DEFER = 12,      // RAM with a deferred factor
     KF_FAMILY = 13,         // a proposal of univariate family components: specialised register form or state in HBM
     KF_COND = 14,           // ... whose parameters are a function of the state (a conditional proposal): the same two forms
+    KF_COMPOSITE = 15,      // ... and whose kind, symmetric flag and parameter map vary per block of components (a composite proposal)
 };
 
 struct mhx_run : mhx_handle_hdr {
@@ -843,6 +845,10 @@ struct mhx_run : mhx_handle_hdr {
     mhx_real* d_cond_p = nullptr;           // [2 dim][n] p(x) of the check kernel; the state-in-HBM form: [4 dim][n], p(x) then p(y)
     int* d_cond_bad = nullptr;              // chains whose p(x) the last check found invalid
     hipFunction_t jit_cond_check = nullptr;
+    // KF_COMPOSITE (mhx_api_composite.inc): everything of KF_COND, and
+    int* d_cmp_tab = nullptr;               // {kind bit, mapped mask} per component, then {first, count, flags} per block
+    int cmp_nblocks = 0;
+    bool cmp_mapped = false;                // some parameter is mapped: the first state must be given
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -915,7 +921,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab};
         for (void* p : ptrs) if (p) (void)hipFree(p);
     }
 };
@@ -963,7 +969,7 @@ k_rwmh_whiten(const mhx_rwmh_args a, const mhx_real* __restrict__ pvec)
 static int cond_check(mhx_run* r);
 static int rwmh_whiten(mhx_run* r)
 {
-    if (r->variant == KF_COND) return cond_check(r);         // no cached q(x); p(x) must be a distribution's
+    if (r->variant == KF_COND || r->variant == KF_COMPOSITE) return cond_check(r);         // no cached q(x); p(x) must be a distribution's
     if (!r->d_qx) return MHX_OK;
     mhx_rwmh_args a = rwmh_args(r);
     if (r->variant == KF_FAMILY)
@@ -1467,6 +1473,7 @@ int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh
 }
 
 #include "mhx_api_cond.inc"
+#include "mhx_api_composite.inc"
 
 // ---- emcee / ram creation, init and stepping live in their own sections below
 static int emcee_init(mhx_run* r, const mhx_real* init);
@@ -1502,7 +1509,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
 {
     mhx_ctx* ctx = r->ctx;
     const size_t nx = (size_t)r->dim * (size_t)r->n;
-    if (r->variant == KF_COND && !init)
+    if ((r->variant == KF_COND || (r->variant == KF_COMPOSITE && r->cmp_mapped)) && !init)
         return mhx_fail(MHX_EINVAL, "mhx_run_init: a conditional proposal has no distribution to draw the first state from -- "
                                 "give initial_params (as for MALA)");
     if (init) {
@@ -1515,7 +1522,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
     const mhx_real* pv = r->d_pvec;
     int draw = init ? 0 : 1;
     const unsigned grid = (unsigned)((r->n + 255) / 256);
-    if (r->variant == KF_FAMILY && draw) {         // the bare draw from the component proposal; the kernel below then evaluates lp
+    if ((r->variant == KF_FAMILY || r->variant == KF_COMPOSITE) && draw) {         // the bare draw from the component proposal; the kernel below then evaluates lp
         hipLaunchKernelGGL(k_fam_init_draw, dim3(grid), dim3(256), 0, ctx->stream, a, (const mhx_fam_comp*)r->d_fam);
         HIP_TRY(hipGetLastError());
         draw = 0;
@@ -1548,7 +1555,7 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->variant == KF_COND) {
+        if (r->variant == KF_COND || r->variant == KF_COMPOSITE) {
             int rc = cond_launch(r, a);
             if (rc) return rc;
         } else if (r->variant == KF_FAMILY) {
@@ -1719,6 +1726,9 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->rec_loga_view = nullptr;
     if (save_samples == MHX_SAVE_MOMENTS) {
         // running moments instead of a sample tensor
+        if (r->kind == RUN_RWMH && r->variant == KF_COMPOSITE)
+            return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run with a composite proposal "
+                                    "(kernel variant 15): record samples");
         if (r->kind == RUN_RWMH && r->variant == KF_COND)
             return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run with a conditional proposal "
                                     "(kernel variant 14): record samples");
@@ -1975,7 +1985,7 @@ int api_run_stats(mhx_run* r, mhx_stats* out)
     if (!r || !out) return mhx_fail(MHX_EINVAL, "mhx_run_stats: NULL argument");
     *out = r->stats;
     out->tainted = r->ctx->tainted ? 1 : 0;
-    out->reserved_ = 0;
+    out->register_form = r->fam_reg ? 1 : 0;
     return MHX_OK;
 }
 

@@ -15,7 +15,9 @@ static std::string cond_source(const mhx_run* r)
     }
     s += "#line 1 \"proposal_params.hip\"\n";
     s += r->cond_src;
-    s += "\n#define MHX_HAVE_PROPOSAL_PARAMS 1\n#include \"mhx_rwmh_cond_kernels.h\"\n";
+    s += "\n#define MHX_HAVE_PROPOSAL_PARAMS 1\n#include \"";
+    s += r->variant == KF_COMPOSITE ? "mhx_rwmh_composite_kernels.h" : "mhx_rwmh_cond_kernels.h";
+    s += "\"\n";
     return s;
 }
 
@@ -30,7 +32,8 @@ static int cond_check(mhx_run* r)
     mhx_real* pbuf = r->d_cond_p;
     int* nbad = r->d_cond_bad;
     HIP_TRY(hipMemsetAsync(nbad, 0, sizeof(int), ctx->stream));
-    void* params[] = {&a, &fam, &cdata, &ncdata, &pbuf, &nbad};
+    const int* ctab = r->d_cmp_tab;                         // (the last argument of a composite run's check kernel only)
+    void* params[] = {&a, &fam, &cdata, &ncdata, &pbuf, &nbad, &ctab};
     int rc = launch_module(r->jit_cond_check, (unsigned)((r->n + 255) / 256), 256, ctx->stream, params);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
@@ -58,9 +61,57 @@ static int cond_launch(mhx_run* r, const mhx_rwmh_args& a0)
         return MHX_OK;
     }
     mhx_real* pbuf = r->d_cond_p;
+    if (r->variant == KF_COMPOSITE) {
+        const int* ctab = r->d_cmp_tab;
+        int nblocks = r->cmp_nblocks;
+        void* params[] = {&a, &tp, &fam, &cdata, &ncdata, &pbuf, &ctab, &nblocks};
+        return launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, r->ctx->stream, params);
+    }
     int stat = (r->flags & MHX_FLAG_STATIC_PROPOSAL) ? 1 : 0, sym = r->fam_symmetric;
     void* params[] = {&a, &tp, &fam, &cdata, &ncdata, &pbuf, &stat, &sym};
     return launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, r->ctx->stream, params);
+}
+
+// What mhx_rwmh_create_conditional and mhx_rwmh_create_composite share once the run's tables are on the device: the chain state,
+// the module (the register form when `fits` and the shape allows it -- `reg_flag` and `reg_defines` beside the dimension and the
+// target kind --, else the state-in-HBM form), the check kernel, the parameter buffer and the initial kernel of a user target.
+static int cond_build(mhx_run* r, const bool fits, const char* reg_flag, const std::vector<std::string>& reg_defines, const char* reg_name,
+                      const char* generic_flag, const char* generic_name, const char* check_name)
+{
+    mhx_ctx* ctx = r->ctx;
+    const mhx_target* t = r->target;
+    const int d = r->dim, tk = t->kind;
+    int rc = run_alloc_state(r);
+    if (rc) return rc;
+    const std::string src = cond_source(r);
+    // the register form addresses a [dim+1][nchains] slab with 32-bit byte offsets and holds x, y and parameters in VGPRs
+    const bool small = ((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) < (1ull << 32);
+    jit_module* m = nullptr;
+    if (!(r->flags & MHX_FLAG_GENERIC) && small && fits &&
+        !(tk == MHX_TARGET_CORR_GAUSS && d > (MHX_REAL64 ? 32 : 64)) && !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096)) {
+        // (the unrolling options: see api_rwmh_create_components)
+        const char* ut = opt(ctx, "REG_UNROLL");
+        std::vector<std::string> xo = {"-mllvm", "-pragma-unroll-threshold=4000000"};
+        if (!ut || atoi(ut) > 0) { xo.push_back("-mllvm"); xo.push_back(std::string("-amdgpu-unroll-threshold-private=") + (ut ? ut : "100000")); }
+        std::vector<std::string> defs = {reg_flag, "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk)};
+        defs.insert(defs.end(), reg_defines.begin(), reg_defines.end());
+        rc = jit_compile(ctx, src, defs, &m, xo);
+        if (rc == MHX_OK) rc = jit_function(m, reg_name, &r->jit_step);
+        if (rc) return rc;
+        r->fam_reg = true;
+    } else {
+        if ((rc = jit_compile(ctx, src, {generic_flag, "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
+        if ((rc = jit_function(m, generic_name, &r->jit_step))) return rc;
+        HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
+    }
+    if ((rc = jit_function(m, check_name, &r->jit_cond_check))) return rc;
+    HIP_TRY(hipMalloc(&r->d_cond_p, (r->fam_reg ? 2 : 4) * (size_t)d * (size_t)r->n * sizeof(mhx_real)));
+    if (tk == MHX_TARGET_USER) {
+        jit_module* mu = nullptr;
+        if ((rc = jit_generic_rwmh(t, &mu))) return rc;
+        if ((rc = jit_function(mu, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
+    }
+    return MHX_OK;
 }
 
 int api_rwmh_create_conditional(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_proposal_component* comps,
@@ -101,38 +152,11 @@ int api_rwmh_create_conditional(mhx_ctx* ctx, const mhx_target* t, const mhx_rwm
     HIP_TRY(hipMalloc(&r->d_cond_data, (ndata ? ndata : 1) * sizeof(mhx_real)));      // (one dummy element keeps the pointer valid)
     if (ndata) COPY_SYNC(ctx->stream, r->d_cond_data, data, ndata * sizeof(mhx_real), hipMemcpyHostToDevice);
     HIP_TRY(hipMalloc(&r->d_cond_bad, sizeof(int)));
-    int rc = run_alloc_state(r.get());
+    int rc = cond_build(r.get(), d <= MHX_COND_REG_MAX_DIM, "MHX_JIT_COND_REG=1",
+                        {"MHX_JIT_FAM_LIST=" + pattern, std::string("MHX_JIT_FAM_STATIC=") + (stat ? "1" : "0"),
+                         std::string("MHX_JIT_FAM_SYM=") + (r->fam_symmetric ? "1" : "0")},
+                        "mhx_jit_cond_reg", "MHX_JIT_COND_GENERIC=1", "mhx_jit_cond_generic", "mhx_jit_cond_check");
     if (rc) return rc;
-    const int tk = t->kind;
-    const std::string src = cond_source(r.get());
-    // the register form addresses a [dim+1][nchains] slab with 32-bit byte offsets and holds x, y, p(x) and p(y) in VGPRs
-    const bool small = ((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) < (1ull << 32);
-    jit_module* m = nullptr;
-    if (!(r->flags & MHX_FLAG_GENERIC) && small && d <= MHX_COND_REG_MAX_DIM &&
-        !(tk == MHX_TARGET_CORR_GAUSS && d > (MHX_REAL64 ? 32 : 64)) && !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096)) {
-        // (the unrolling options: see api_rwmh_create_components)
-        const char* ut = opt(ctx, "REG_UNROLL");
-        std::vector<std::string> xo = {"-mllvm", "-pragma-unroll-threshold=4000000"};
-        if (!ut || atoi(ut) > 0) { xo.push_back("-mllvm"); xo.push_back(std::string("-amdgpu-unroll-threshold-private=") + (ut ? ut : "100000")); }
-        rc = jit_compile(ctx, src,
-                         {"MHX_JIT_COND_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
-                          "MHX_JIT_FAM_LIST=" + pattern, std::string("MHX_JIT_FAM_STATIC=") + (stat ? "1" : "0"),
-                          std::string("MHX_JIT_FAM_SYM=") + (r->fam_symmetric ? "1" : "0")}, &m, xo);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_cond_reg", &r->jit_step);
-        if (rc) return rc;
-        r->fam_reg = true;
-    } else {
-        if ((rc = jit_compile(ctx, src, {"MHX_JIT_COND_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
-        if ((rc = jit_function(m, "mhx_jit_cond_generic", &r->jit_step))) return rc;
-        HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
-    }
-    if ((rc = jit_function(m, "mhx_jit_cond_check", &r->jit_cond_check))) return rc;
-    HIP_TRY(hipMalloc(&r->d_cond_p, (r->fam_reg ? 2 : 4) * (size_t)d * (size_t)r->n * sizeof(mhx_real)));
-    if (tk == MHX_TARGET_USER) {
-        jit_module* mu = nullptr;
-        if ((rc = jit_generic_rwmh(t, &mu))) return rc;
-        if ((rc = jit_function(mu, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
-    }
     *out = r.release();
     return MHX_OK;
 }

@@ -46,6 +46,10 @@ void mhx_jit_unlock();
     int api_rwmh_create_conditional(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                        \
                                     const mhx_proposal_component* comps, int32_t ncomps, const char* params_src,       \
                                     const REAL* data, size_t ndata, mhx_run** out);                                    \
+    int api_rwmh_create_composite(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                          \
+                                  const mhx_proposal_component* comps, int32_t ncomps, const mhx_proposal_block* blocks, \
+                                  int32_t nblocks, const int32_t* mapped, const char* params_src, const REAL* data,     \
+                                  size_t ndata, mhx_run** out);                                                        \
     int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg, mhx_run** out);                  \
     int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mhx_run** out);                      \
     int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, mhx_run** out);                    \

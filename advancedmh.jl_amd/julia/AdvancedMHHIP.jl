@@ -60,7 +60,7 @@ end
 struct Stats
     transitions::UInt64; accepted::UInt64; kernel_ms::Cdouble; wall_ms::Cdouble
     kernel_variant::Int32; launches::Int32; reduce_lanes::Int32; dtype::Int32; normal_gen::Int32; factor_band::Int32
-    tainted::Int32; reserved_::Int32
+    tainted::Int32; register_form::Int32
 end
 struct DiagCfg
     max_lag::Int32; ess_chains::Int32; split::Int32

@@ -2,8 +2,8 @@
 from ._lib import (ArgumentError, Context, MhxError, PosDefException, FLAG_GENERIC, FLAG_NO_JIT, FLAG_EMCEE_SEQUENTIAL, FLAG_ZIGGURAT, FLAG_DENSE_FACTOR, FLAG_RAM_DEFERRED, FLAG_SYMMETRIC_PROPOSAL, LIB_PATH,
                    EXPORTS, MHX_EINVAL, MHX_ESTATE, Schedule, check, host_array, lib, get_default_dtype, set_default_dtype, use_library, TOOLS_LIB_PATH)
 from .dist import Group
-from .api import (I, Banana, Cauchy, Chains, ComponentProposal, ConditionalProposal, CorrGaussian, DensityModel, Ensemble, Exponential, Funnel, Gamma, HipLogDensity, IIDNormal,
-                  InverseGamma, IsoGaussian, Laplace, LogDensityModel, MALA, MCMCDistributed, MCMCHIP, MCMCSerial, MCMCThreads, MetropolisHastings, MvNormal, Normal, RandomWalkProposal,
+from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposal, ConditionalProposal, CorrGaussian, DensityModel, Ensemble, Exponential, Funnel, Gamma, HipLogDensity, IIDNormal,
+                  InverseGamma, IsoGaussian, Laplace, LogDensityModel, MALA, MCMCDistributed, MCMCHIP, MCMCSerial, MCMCThreads, MetropolisHastings, MvNormal, NamedProposals, Normal, RandomWalkProposal,
                   RobustAdaptiveMetropolis, Run, RWMH, StaticMH, StaticProposal, StructArray, combine_diagnostics, StretchProposal,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
                   logdensity, pack_lower, sample, unpack_lower, zeros)

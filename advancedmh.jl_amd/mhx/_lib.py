@@ -59,6 +59,14 @@ class ProposalComponent(C.Structure):
     _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
 
 
+class ProposalBlock(C.Structure):
+    """mhx_proposal_block: components first .. first + count - 1 of a composite proposal, BLOCK_STATIC | BLOCK_SYMMETRIC"""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+BLOCK_STATIC, BLOCK_SYMMETRIC = 1, 2
+
+
 class EmceeCfg(C.Structure):
     _fields_ = [("dim", C.c_int32), ("nwalkers", C.c_int32), ("seed", C.c_uint64), ("ensemble_id", C.c_uint64),
                 ("stretch", C.c_double), ("flags", C.c_int32), ("reduce_lanes", C.c_int32),
@@ -81,7 +89,7 @@ class Stats(C.Structure):
     _fields_ = [("transitions", C.c_uint64), ("accepted", C.c_uint64), ("kernel_ms", C.c_double),
                 ("wall_ms", C.c_double), ("kernel_variant", C.c_int32), ("launches", C.c_int32),
                 ("reduce_lanes", C.c_int32), ("dtype", C.c_int32), ("normal_gen", C.c_int32), ("factor_band", C.c_int32),
-                ("tainted", C.c_int32), ("reserved_", C.c_int32)]
+                ("tainted", C.c_int32), ("register_form", C.c_int32)]
 
 
 class HostStats(C.Structure):
@@ -120,6 +128,7 @@ EXPORTS = [
     "mhx_group_create", "mhx_group_destroy", "mhx_group_size", "mhx_group_ctx", "mhx_group_shard", "mhx_group_attach", "mhx_group_run",
     "mhx_group_init", "mhx_group_sample", "mhx_group_sample_to_host", "mhx_group_stats", "mhx_group_diagnostics", "mhx_group_ess_bulk_tail",
     "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components", "mhx_rwmh_create_conditional",
+    "mhx_rwmh_create_composite",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -183,6 +192,8 @@ def lib():
         L.mhx_rwmh_create_components.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.POINTER(vp)]
         L.mhx_rwmh_create_conditional.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.c_char_p, rp,
                                                   C.c_size_t, C.POINTER(vp)]
+        L.mhx_rwmh_create_composite.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalComponent), C.c_int32, C.POINTER(ProposalBlock),
+                                                C.c_int32, C.POINTER(C.c_int32), C.c_char_p, rp, C.c_size_t, C.POINTER(vp)]
         L.mhx_emcee_create.argtypes = [vp, vp, C.POINTER(EmceeCfg), C.POINTER(vp)]
         L.mhx_ram_create.argtypes = [vp, vp, C.POINTER(RamCfg), C.POINTER(vp)]
         L.mhx_mala_create.argtypes = [vp, vp, C.POINTER(MalaCfg), C.POINTER(vp)]

@@ -282,6 +282,56 @@ class ConditionalProposal:
         return list(self.traced.table)
 
 
+class NamedProposals:
+    """NamedProposals(a=p1, b=p2, ...): the reference's NamedTuple of proposals `(a = ..., b = ...)` (src/proposal.jl:163-175) in its
+    full form -- each entry a RandomWalkProposal or StaticProposal of any kind, scalar or vector, fixed or a function of the entry's
+    OWN slice of the state.  The keys name the parameters; a vector entry `a` of length n names `a[1] .. a[n]`."""
+
+    def __init__(self, **entries):
+        if not entries:
+            raise L.ArgumentError(L.MHX_EINVAL, "NamedProposals: empty proposal")
+        self.entries = dict(entries)
+
+
+class CompositeProposal:
+    """What MetropolisHastings holds for a list of proposals or a NamedProposals that does not fold into one vector proposal: an
+    ordered list of blocks, each with its own kind, symmetric flag and (for a function entry) parameter map over its own slice
+    (DESIGN.md section 3.15).  `.blocks` [(first, count, flags)], `.table()`, `.mapped`, `.source` / `.data`: the arguments of
+    mhx_rwmh_create_composite."""
+
+    issymmetric = False
+
+    def __init__(self, labels, parts, named):
+        entries, self.blocks, names, first = [], [], [], 0
+        for label, q in zip(labels, parts):
+            pr = q.proposal
+            if isinstance(pr, ConditionalProposal):
+                n, what = pr.dim, pr.fn
+            elif isinstance(pr, ComponentProposal):
+                n, what = pr.dim, list(pr.comps)
+            else:
+                if pr.kind == L.PROP_DENSE:
+                    raise L.ArgumentError(L.MHX_EINVAL, "entry %r: an MvNormal with a dense covariance is not a list of independent components: "
+                                          "a composite proposal takes isotropic or diagonal covariances (give a dense proposal alone)" % (label,))
+                n = pr.dim
+                what = [Normal(float(pr.mean[i]), float(pr.vec[i]) if pr.kind == L.PROP_DIAG else pr.scale) for i in range(n)]
+            flags = (L.BLOCK_STATIC if isinstance(q, StaticProposal) else 0) | (L.BLOCK_SYMMETRIC if q.issymmetric else 0)
+            self.blocks.append((first, n, flags))
+            entries.append((label, n, what))
+            names += [str(label)] if n == 1 else ["%s[%d]" % (label, i + 1) for i in range(n)]
+            first += n
+        self.dim = first
+        self.param_names = names if named else None
+        self.traced = _trace.trace_composite(entries)
+        self.mapped, self.source, self.data = list(self.traced.mapped), self.traced.source, self.traced.data
+        for fam, p0, p1 in self.traced.table:                 # the constants, checked like any component's
+            _lower_univariate(_UNIVARIATES[fam](p0) if fam == L.FAMILY_EXPONENTIAL else _UNIVARIATES[fam](p0, p1))
+        self.proposal = self                                    # (MetropolisHastings(...).proposal.proposal: what the run lowers)
+
+    def table(self):
+        return list(self.traced.table)
+
+
 def _as_proposal(dist, dim=None):
     """What a RandomWalkProposal / StaticProposal holds: an MvNormal (everything _as_mvnormal takes, exactly as it lowers it), or a
     ComponentProposal for one univariate of a device family / a vector mixing them with Normals."""
@@ -544,6 +594,31 @@ class MetropolisHastings:
 
     def __init__(self, proposal):
         self.param_names = None
+        if isinstance(proposal, (list, tuple, NamedProposals)):
+            # the reference's Array{Proposal} / NamedTuple{Proposal} in full (src/proposal.jl:128-175): entries that are all scalar,
+            # constant and of one kind fold exactly as the mapping form below does; anything else is a composite run
+            named = isinstance(proposal, NamedProposals)
+            labels = list(proposal.entries) if named else list(range(1, len(proposal) + 1))
+            parts = list(proposal.entries.values()) if named else list(proposal)
+            if not parts:
+                raise L.ArgumentError(L.MHX_EINVAL, "MetropolisHastings: empty proposal")
+            for label, q in zip(labels, parts):
+                if not isinstance(q, (RandomWalkProposal, StaticProposal)):
+                    raise L.ArgumentError(L.MHX_EINVAL, "entry %r of a list of proposals / NamedProposals is %r, not a RandomWalkProposal or a "
+                                          "StaticProposal" % (label, q))
+            folds = len({type(q) for q in parts}) == 1 and all(
+                not isinstance(q.proposal, ConditionalProposal) and q.proposal.dim == 1 for q in parts)
+            if folds:
+                proposal = {str(k): q for k, q in zip(labels, parts)}
+            else:
+                comp = CompositeProposal(labels, parts, named)
+                self.param_names = comp.param_names
+                self.proposal = comp
+                return
+            if not named:
+                self.__init__(proposal)
+                self.param_names = None
+                return
         if isinstance(proposal, dict):
             if not proposal:
                 raise L.ArgumentError(L.MHX_EINVAL, "MetropolisHastings: empty proposal")
@@ -756,7 +831,18 @@ class Run:
                 raise L.ArgumentError(L.MHX_EINVAL, "proposal dimension %d != model dimension %d" % (mv.dim, d))
             if isinstance(sampler.proposal, StaticProposal):
                 flags |= L.MHX_FLAG_STATIC_PROPOSAL
-            if isinstance(mv, ConditionalProposal):
+            if isinstance(mv, CompositeProposal):
+                # blocks with their own kind, symmetric flag and parameter map: the tables and one traced source, its own entry point
+                tab = (L.ProposalComponent * mv.dim)(*[L.ProposalComponent(f, 0, p0, p1) for f, p0, p1 in mv.table()])
+                blk = (L.ProposalBlock * len(mv.blocks))(*[L.ProposalBlock(f, n, fl, 0) for f, n, fl in mv.blocks])
+                mapped = (C.c_int32 * mv.dim)(*mv.mapped) if any(mv.mapped) else None
+                data = None if mv.data is None else f32(mv.data)
+                self._keep += [data]
+                cfg = L.RwmhCfg(d, nchains, seed, first_chain, L.PROP_ISO, 1.0, None, flags, None, reduce_lanes)
+                L.check(lib.mhx_rwmh_create_composite(self.ctx.h, model.handle(self.ctx), C.byref(cfg), tab, mv.dim, blk, len(mv.blocks), mapped,
+                                                      mv.source.encode() if mv.source else None, L.fptr(data),
+                                                      0 if data is None else data.size, C.byref(self.h)))
+            elif isinstance(mv, ConditionalProposal):
                 # a function of the state: the component table and the traced parameter map, its own entry point
                 if sampler.proposal.issymmetric:
                     flags |= L.FLAG_SYMMETRIC_PROPOSAL
@@ -834,7 +920,8 @@ class Run:
     # -- initial AbstractMCMC.step
     def init(self, initial_params=None):
         ip = None
-        if initial_params is None and self.kind == "rwmh" and isinstance(self.sampler.proposal.proposal, ConditionalProposal):
+        mv = self.sampler.proposal.proposal if self.kind == "rwmh" else None
+        if initial_params is None and (isinstance(mv, ConditionalProposal) or (isinstance(mv, CompositeProposal) and any(mv.mapped))):
             raise L.ArgumentError(L.MHX_EINVAL, "a function proposal has no distribution to draw the first state from: "
                                   "give initial_params (as for MALA)")
         if initial_params is not None:
@@ -992,7 +1079,7 @@ class Run:
         return dict(transitions=st.transitions, accepted=st.accepted, kernel_ms=st.kernel_ms, wall_ms=st.wall_ms,
                     kernel_variant=st.kernel_variant, launches=st.launches, reduce_lanes=st.reduce_lanes,
                     dtype="f64" if st.dtype == L.MHX_F64 else "f32", normal_gen=st.normal_gen, factor_band=st.factor_band,
-                    tainted=st.tainted)
+                    tainted=st.tainted, register_form=st.register_form)
 
     def diagnostics(self, max_lag=0, ess_chains=256, split=False):
         """Sums for R-hat / between-chain ESS (all chains) and, if max_lag > 0, the Geyer ESS from the multi-chain

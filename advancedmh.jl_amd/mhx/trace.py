@@ -812,6 +812,47 @@ class TracedProposal(Traced):
         return [tuple(r) for r in out]
 
 
+def _lower_components(g, out, k0, sets, table, where=""):
+    """the distributions `out` as components k0, k0 + 1, ... : constants go to `table`, traced parameters to `sets`"""
+    for k, dist in enumerate(out, k0):
+        if hasattr(dist, "nu") and not hasattr(dist, "family"):                      # TDist
+            if dist.nu != 1.0:
+                raise TraceError(where + "component %d: TDist(%g) -- only TDist(1) = Cauchy(0, 1) has a device sampler" % (k, dist.nu))
+            fam, params = _FAM_CAUCHY, (0.0, 1.0)
+        else:
+            fam = getattr(dist, "family", None)
+            if not isinstance(fam, int) or not 0 <= fam < len(_FAMILY_NAMES) or not hasattr(dist, "params"):
+                raise TraceError(where + "component %d: %r is not one of the device families (%s, TDist(1))" % (k, dist, ", ".join(_FAMILY_NAMES)))
+            params = tuple(dist.params())
+        row = []
+        for j, v in enumerate(params):
+            if isinstance(v, Sym):
+                if v.g is not g:
+                    raise TraceError(where + "component %d: the parameter belongs to another trace" % k)
+                if j == 0 and fam in (_FAM_GAMMA, _FAM_INVERSE_GAMMA):
+                    raise TraceError(where + "component %d: the shape alpha of %s must not depend on the state (its lgamma would not cancel in "
+                                     "the ratio, and the sampler's constants are derived from it on the host)" % (k, _FAMILY_NAMES[fam]))
+                if j == 1 and fam == _FAM_EXPONENTIAL:
+                    raise TraceError(where + "component %d: Exponential has one parameter" % k)
+                sets.append((k, j, v.i))
+                row.append(None)
+            elif isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
+                row.append(float(v))
+            else:
+                raise TraceError(where + "component %d: parameter %d of %s is %r, not a number or a traced number" % (k, j, _FAMILY_NAMES[fam], v))
+        # an entry the source sets still needs a valid constant in the table: 0 for a location, 1 for a scale, a bound 1 away
+        if fam == _FAM_UNIFORM:
+            a, b = row
+            if a is None:
+                a = 0.0 if b is None else b - 1.0
+            if b is None:
+                b = a + 1.0
+            row = [a, b]
+        else:
+            row = [(0.0 if j == 0 and fam != _FAM_EXPONENTIAL else 1.0) if v is None else v for j, v in enumerate(row)]
+        table.append((fam, row[0], row[1]))
+
+
 def trace_proposal(fn, dim):
     """Run `fn` -- a function of the state that returns one univariate distribution (dim = 1; the state is then a scalar) or a list
     of `dim` of them (the state is a Vec) -- once over traced parameters, and return its families, constant table and kernel
@@ -834,41 +875,64 @@ def trace_proposal(fn, dim):
         raise TraceError("a function proposal of dimension %d must return %d univariate distributions (one per parameter), got %d" % (
             dim, dim, len(out)))
     sets, table = [], []
-    for k, dist in enumerate(out):
-        if hasattr(dist, "nu") and not hasattr(dist, "family"):                      # TDist
-            if dist.nu != 1.0:
-                raise TraceError("component %d: TDist(%g) -- only TDist(1) = Cauchy(0, 1) has a device sampler" % (k, dist.nu))
-            fam, params = _FAM_CAUCHY, (0.0, 1.0)
-        else:
-            fam = getattr(dist, "family", None)
-            if not isinstance(fam, int) or not 0 <= fam < len(_FAMILY_NAMES) or not hasattr(dist, "params"):
-                raise TraceError("component %d: %r is not one of the device families (%s, TDist(1))" % (k, dist, ", ".join(_FAMILY_NAMES)))
-            params = tuple(dist.params())
-        row = []
-        for j, v in enumerate(params):
-            if isinstance(v, Sym):
-                if v.g is not g:
-                    raise TraceError("component %d: the parameter belongs to another trace" % k)
-                if j == 0 and fam in (_FAM_GAMMA, _FAM_INVERSE_GAMMA):
-                    raise TraceError("component %d: the shape alpha of %s must not depend on the state (its lgamma would not cancel in "
-                                     "the ratio, and the sampler's constants are derived from it on the host)" % (k, _FAMILY_NAMES[fam]))
-                if j == 1 and fam == _FAM_EXPONENTIAL:
-                    raise TraceError("component %d: Exponential has one parameter" % k)
-                sets.append((k, j, v.i))
-                row.append(None)
-            elif isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
-                row.append(float(v))
-            else:
-                raise TraceError("component %d: parameter %d of %s is %r, not a number or a traced number" % (k, j, _FAMILY_NAMES[fam], v))
-        # an entry the source sets still needs a valid constant in the table: 0 for a location, 1 for a scale, a bound 1 away
-        if fam == _FAM_UNIFORM:
-            a, b = row
-            if a is None:
-                a = 0.0 if b is None else b - 1.0
-            if b is None:
-                b = a + 1.0
-            row = [a, b]
-        else:
-            row = [(0.0 if j == 0 and fam != _FAM_EXPONENTIAL else 1.0) if v is None else v for j, v in enumerate(row)]
-        table.append((fam, row[0], row[1]))
+    _lower_components(g, out, 0, sets, table)
     return TracedProposal(g, sets, table, dim)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# composite proposals (src/proposal.jl:128-175): one parameter map over several entries, DESIGN.md section 3.15
+
+class TracedComposite(TracedProposal):
+    """The recorded parameter map of a composite proposal: a TracedProposal over the whole state, and `.mapped` (per component: bit j
+    set = the source sets parameter j).  Unpacks as (table, mapped, source, data)."""
+
+    def __init__(self, g, sets, table, dim):
+        TracedProposal.__init__(self, g, sets, table, dim)
+        self.mapped = [0] * self.dim
+        for k, j, _ in sets:
+            self.mapped[k] |= 1 << j
+        if not sets:
+            self.source = ""                                # nothing is mapped: no source (mhx_rwmh_create_composite takes NULL / "")
+
+    def __iter__(self):
+        return iter((self.table, self.mapped, self.source, self.data))
+
+
+def trace_composite(entries):
+    """Trace the entries of a composite proposal in ONE graph.  `entries` is a list of (name, n, what): `what` is a list of n
+    distributions (constants), or a function of the entry's OWN slice of the state -- a scalar for n = 1, a Vec of length n otherwise
+    -- returning one distribution or a list of n.  Entry e covers the global components first_e .. first_e + n - 1 (first_e = the sum
+    of the earlier n): its slice variables are the global x[first_e + i], and its p.set lines carry global component indices.
+    Returns a `TracedComposite`: the table, the mapped mask, one MHX_PROPOSAL_PARAMS source and the data block.  The same emitter and
+    the same refusals as trace_proposal, with the entry named in the message."""
+    dim = sum(int(n) for _, n, _ in entries)
+    if dim < 1:
+        raise TraceError("a composite proposal needs at least one component")
+    g = _Graph()
+    g.node("c", _const_key(0.0))
+    xs = [Sym(g, g.node("x", k)) for k in range(dim)]
+    sets, table = [], []
+    first = 0
+    for name, n, what in entries:
+        n = int(n)
+        where = "entry %r: " % (name,)
+        if n < 1:
+            raise TraceError(where + "an entry covers at least one parameter")
+        if callable(what):
+            _ACTIVE.append(g)
+            try:
+                out = what(xs[first] if n == 1 else Vec(xs[first:first + n]))
+            except TraceError as e:
+                raise TraceError(where + str(e)) from e
+            finally:
+                _ACTIVE.pop()
+        else:
+            out = what
+        if not isinstance(out, (list, tuple)):
+            out = [out]
+        if len(out) != n:
+            raise TraceError(where + "a proposal over %d parameter%s must return %d univariate distribution%s (one per parameter), got %d" % (
+                n, "" if n == 1 else "s", n, "" if n == 1 else "s", len(out)))
+        _lower_components(g, out, first, sets, table, where)
+        first += n
+    return TracedComposite(g, sets, table, dim)

@@ -266,6 +266,37 @@ int mhx_rwmh_create_components(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh
 int mhx_rwmh_create_conditional(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_proposal_component *comps,
                                 int32_t ncomps, const char *params_src, const void *data, size_t ndata, mhx_run **out);
 
+/* A COMPOSITE proposal: the reference's Array{Proposal} and NamedTuple{Proposal} (src/proposal.jl:128-175,198-240) -- an ordered
+ * list of blocks of components, each block with its own kind, its own symmetric flag and, optionally, parameters that depend on the
+ * block's own slice of the state (the arithmetic: DESIGN.md section 3.15).  blocks[b] covers components first .. first + count - 1;
+ * the blocks are contiguous, in order, and cover 0 .. dim-1 exactly.  flags: MHX_BLOCK_STATIC (y_k = xi_k, else y_k = x_k + xi_k),
+ * MHX_BLOCK_SYMMETRIC (the block adds nothing to the ratio: the user is trusted); reserved must be 0. */
+typedef struct {
+    int32_t first, count, flags, reserved;
+} mhx_proposal_block;
+#define MHX_BLOCK_STATIC 1
+#define MHX_BLOCK_SYMMETRIC 2
+
+/* An RWMH run under the composite proposal (comps, blocks).  mapped[k] (or mapped == NULL: nothing is) says which parameters of
+ * component k the source sets: bit j set = p.set(k, j, .) of params_src, an MHX_PROPOSAL_PARAMS source as for
+ * mhx_rwmh_create_conditional, with GLOBAL indices k and x[j]; a p.set on an entry not declared mapped is ignored.  params_src is NULL
+ * or "" when nothing is mapped.  Component k draws exactly as in mhx_rwmh_create_components / _conditional, keyed by its global index,
+ * so the draws do not depend on the grouping; every block not declared symmetric adds r_b = (K_b(p(y); .) - K_b(p(x); .)) +
+ * (Z_b(p(y)) - Z_b(p(x))) to the ratio, in block order; p(y) of every mapped component is checked at every step and an invalid
+ * candidate is rejected.  One block reproduces mhx_rwmh_create_conditional bit for bit, and mhx_rwmh_create_components when nothing is
+ * mapped.  With nothing mapped mhx_run_init(run, NULL) draws the first state x = 0 + xi from the components, for both kinds.
+ * Kernel variant 15, compiled at run time only, in two forms with the same chain: state, candidate and the MAPPED parameters in
+ * registers (nothing mapped: dim <= 32 in fp64, 48 in fp32; else 2 dim + mapped components + half the non-symmetric blocks with a
+ * mapped component <= 60 / 96: what compiles without scratch
+ * memory), or -- MHX_FLAG_GENERIC / larger shapes -- in HBM.  MHX_EINVAL: blocks that do not tile 0 .. dim-1 in order, unknown block
+ * flags or a non-zero reserved, MHX_FLAG_STATIC_PROPOSAL / MHX_FLAG_SYMMETRIC_PROPOSAL in cfg->flags (the blocks carry them), a mapped
+ * shape alpha of a Gamma family, a mask without source or source without a mask, and everything mhx_rwmh_create_conditional refuses
+ * (MHX_FLAG_NO_JIT, MHX_FLAG_ZIGGURAT, reduce_lanes > 1, MHX_SAVE_MOMENTS, init without initial_params when anything is mapped, states at
+ * which p is not valid).  A compile error in params_src is MHX_EJIT with the compiler's log in mhx_last_error. */
+int mhx_rwmh_create_composite(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_proposal_component *comps,
+                              int32_t ncomps, const mhx_proposal_block *blocks, int32_t nblocks, const int32_t *mapped,
+                              const char *params_src, const void *data, size_t ndata, mhx_run **out);
+
 /* ---------------------------------------------------------------------------------------------
  * Affine-invariant ensemble.  Replaces Ensemble{StretchProposal} (src/emcee.jl:1-4, :63-68), its
  * step (:14-24), sweep (:39-58) and stretch move (:70-102).  The device sweep is the parallel
@@ -480,7 +511,9 @@ typedef struct {
                                   13 a proposal of univariate family components (mhx_rwmh_create_components), lane per chain: the
                                   run-time specialised register form or the pre-built state-in-HBM form, the same chain,
                                   14 a conditional proposal (mhx_rwmh_create_conditional), lane per chain, compiled at run time:
-                                  the register form or the state-in-HBM form, the same chain */
+                                  the register form or the state-in-HBM form, the same chain,
+                                  15 a composite proposal (mhx_rwmh_create_composite): blocks of components with their own kind,
+                                  symmetric flag and parameter map; lane per chain, compiled at run time, the same two forms */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
@@ -489,7 +522,8 @@ typedef struct {
                                   (0 = diagonal, 1 = bidiagonal: an AR(1) / Markov model, ...), -1 = none (dense form, other samplers) */
     int32_t tainted;           /* 1: a probe / fault-injection option of the tools build was set on the run's context -- the chains of
                                   such a run may be INVALID (timing probes skip work).  Always 0 from libmhx.so. */
-    int32_t reserved_;
+    int32_t register_form;     /* kernel variants 13, 14 and 15: 1 = the run is stepped by the run-time specialised register form, 0 = by
+                                  the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
 /* dimension and number of chains (walkers) of a run; either pointer may be NULL */
