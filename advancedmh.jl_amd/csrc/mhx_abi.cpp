@@ -348,6 +348,26 @@ extern "C" int mhx_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const 
     return is64(r) ? mhx_f64::api_run_ess_bulk_tail(R64(r), cfg, params, nparams, ess_bulk, ess_tail)
                    : mhx_f32::api_run_ess_bulk_tail(R32(r), cfg, params, nparams, ess_bulk, ess_tail);
 }
+extern "C" int mhx_ctx_order_statistics(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                                        const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
+{
+    NEED(ctx, "mhx_ctx_order_statistics");
+    return is64(ctx) ? mhx_f64::api_ctx_order_statistics(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, ranks, nranks, out)
+                     : mhx_f32::api_ctx_order_statistics(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, ranks, nranks, out);
+}
+extern "C" int mhx_run_order_statistics(mhx_run* r, const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
+{
+    NEED(r, "mhx_run_order_statistics");
+    return is64(r) ? mhx_f64::api_run_order_statistics(R64(r), params, nparams, ranks, nranks, out)
+                   : mhx_f32::api_run_order_statistics(R32(r), params, nparams, ranks, nranks, out);
+}
+extern "C" int mhx_run_select_histogram(mhx_run* r, const int32_t* params, int32_t nparams, const uint64_t* prefixes, const int32_t* ngroups,
+                                        int32_t gstride, int32_t shift, int32_t digit_bits, uint64_t* hist)
+{
+    NEED(r, "mhx_run_select_histogram");
+    return is64(r) ? mhx_f64::api_run_select_histogram(R64(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist)
+                   : mhx_f32::api_run_select_histogram(R32(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist);
+}
 extern "C" int mhx_emcee_half_step(mhx_run* r, int half, int begin, int count)
 {
     NEED(r, "mhx_emcee_half_step");

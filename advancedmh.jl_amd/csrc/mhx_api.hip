@@ -41,6 +41,7 @@
 #include "mhx_jit_embed.inc"         // generated (embed_headers.py --release): the same text without its MHX_TOOLS_BUILD blocks
 #endif
 #include "mhx_jit_ext.h"        // run-time kernels through the installation's clang++ (pure host code)
+#include "mhx_select.h"         // bucket scan and pass loop of the exact order statistics (pure host code, shared likewise)
 #include "mhx_host_expand.h"    // the host threads of the accept-compacted return path (pure host code, shared by both instantiations)
 #include "mhx_impl.h"           // the prototypes of this instantiation (api_*), shared with the dispatcher mhx_abi.cpp
 
@@ -225,8 +226,14 @@ struct mhx_ctx : mhx_handle_hdr {
     mhx_compact_hdr* hdr_pinned = nullptr;
     mhx_expander* expander = nullptr;
     int expander_threads = 0, expander_chunk = 0, expander_numa = -1;   // the options / memory node the expander was created with
+    void* select_scratch = nullptr;                 // histograms, prefixes and group counts of the order-statistics passes (grown on demand)
+    size_t select_bytes = 0;
+    uint64_t* select_landing = nullptr;             // ... and their page-locked landing place on the host (grown on demand)
+    size_t select_landing_words = 0;
     ~mhx_ctx()
     {
+        if (select_scratch) (void)hipFree(select_scratch);
+        if (select_landing) (void)hipHostFree(select_landing);
         if (expander) mhx_expander_destroy(expander);
         for (compact_pair& P : cpair) {
             if (P.dev_fixed) (void)hipFree(P.dev_fixed);
@@ -279,7 +286,7 @@ static const opt_name k_opt_names[] = {
     {"EMCEE_MFMA", 0}, {"EMCEE_MFMA_WAVES", 0}, {"EMCEE_SCALAR", 0}, {"EMCEE_SCAL_MODE", 0}, {"EMCEE_SCAL_WPB", 0}, {"EMCEE_SCAL_REC", 0},
     {"EMCEE_FUSED", 0}, {"EMCEE_PERSIST", 0}, {"EMCEE_PRELOAD", 0}, {"EMCEE_DEFER", 0}, {"EMCEE_SWEEP_DEFER", 0}, {"EMCEE_WAVES", 0},
     {"EMCEE_REC_STORE", 0}, {"EMCEE_ROW_STORE", 0}, {"EMCEE_COOP_REC", 0},
-    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0},
+    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0},
 #ifdef MHX_TOOLS_BUILD
     {"ZIG_PROBE", 1}, {"ZIG_FORCE_FAIL", 1}, {"JIT_DEFS", 1}, {"JIT_FLAGS", 1}, {"EMCEE_PROBE", 1}, {"EMCEE_STAMPS", 1}, {"EMCEE_STAMPS_FILE", 1},
     {"FAULT_SLAB", 1}, {"RAM_PROF", 1},

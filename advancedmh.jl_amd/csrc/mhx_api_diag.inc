@@ -204,3 +204,157 @@ int api_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* pa
     for (void* q : ptrs) if (q) (void)hipFree(q);
     return rc;
 }
+
+// ---- exact order statistics: histogram radix select on the tensor in place (DESIGN.md section 6.5) ----
+// Three pre-built (digit width, groups per launch) forms; a pass of d digit bits runs on the narrowest that holds it.  LDS per
+// block: groups << width counters of 4 bytes = 16, 64 and 64 KiB.
+template <int BITS, int G>
+__global__ void __launch_bounds__(MHX_SELECT_THREADS)
+k_select_hist(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const int* __restrict__ params,
+              const unsigned long long* __restrict__ prefixes, const int* __restrict__ ngroups, const int gstride, const int first,
+              const int shift, const int digit_bits, const int top, const unsigned long long chunk, unsigned long long* __restrict__ hist)
+{
+    __shared__ unsigned lds[G << BITS];
+    mhx_select_hist_body<BITS, G>(samples, N, d1, C, params, prefixes, ngroups, gstride, first, shift, digit_bits, top, chunk, hist, lds);
+}
+
+struct select_source {
+    mhx_ctx* ctx;
+    const mhx_real* tensor;
+    long N, C;
+    int d1;
+    const int32_t* params;
+    int32_t nparams;
+    const char* who;
+};
+
+// one pass over one tensor: mhx_select_hist_fn of mhx_select.h (hist is host memory)
+static int select_hist_pass(void* user, const uint64_t* prefixes, const int32_t* ngroups, int32_t gstride, int32_t shift,
+                            int32_t digit_bits, uint64_t* hist)
+{
+    const select_source* s = (const select_source*)user;
+    mhx_ctx* ctx = s->ctx;
+    const int P = s->nparams;
+    if (digit_bits < 1 || digit_bits > MHX_SELECT_MAX_DIGIT_BITS || shift < 0 || shift + digit_bits > MHX_KEY_BITS || gstride < 1)
+        return mhx_fail(MHX_EINVAL, "%s: digit of %d bits at bit %d of a %d-bit key", s->who, (int)digit_bits, (int)shift, MHX_KEY_BITS);
+    int gmax = 0;
+    for (int i = 0; i < P; ++i) {
+        if (ngroups[i] < 0 || ngroups[i] > gstride) return mhx_fail(MHX_EINVAL, "%s: %d groups in a stride of %d", s->who, (int)ngroups[i], (int)gstride);
+        gmax = std::max(gmax, (int)ngroups[i]);
+    }
+    if (!gmax) return MHX_OK;
+    if (shift + digit_bits == MHX_KEY_BITS && gmax > 1) return mhx_fail(MHX_EINVAL, "%s: the first pass has one group", s->who);
+    HIP_TRY(hipSetDevice(ctx->device));
+    // scratch of the context, grown on demand: histogram | prefixes | group counts | parameter rows
+    const size_t nh = ((size_t)P * gstride) << digit_bits, npf = (size_t)P * gstride;
+    const size_t bytes = (nh + npf) * sizeof(uint64_t) + 2 * (size_t)P * sizeof(int32_t);
+    if (bytes > ctx->select_bytes) {
+        if (ctx->select_scratch) (void)hipFree(ctx->select_scratch);
+        ctx->select_scratch = nullptr; ctx->select_bytes = 0;
+        if (hipMalloc(&ctx->select_scratch, bytes) != hipSuccess) return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of histogram scratch", s->who, bytes);
+        ctx->select_bytes = bytes;
+    }
+    unsigned long long* d_hist = (unsigned long long*)ctx->select_scratch;
+    unsigned long long* d_pf = d_hist + nh;
+    int* d_ng = (int*)(d_pf + npf);
+    int* d_par = d_ng + P;
+    HIP_TRY(hipMemsetAsync(d_hist, 0, nh * sizeof(uint64_t), ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_pf, prefixes, npf * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_ng, ngroups, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_par, s->params, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    // blocks per parameter: enough blocks for the whole chip, chunks of at least one unrolled block sweep and below 2^31 draws
+    const unsigned long long S = (unsigned long long)s->N * (unsigned long long)s->C;
+    const unsigned long long sweep = (unsigned long long)MHX_SELECT_THREADS * MHX_SELECT_UNROLL;
+    unsigned long long nblk = std::min<unsigned long long>((2048 + P - 1) / P, (S + sweep - 1) / sweep);
+    nblk = std::max<unsigned long long>(std::max<unsigned long long>(nblk, 1), (S + (1ull << 31) - 1) >> 31);
+    const unsigned long long chunk = (S + nblk - 1) / nblk;
+    const int top = shift + digit_bits == MHX_KEY_BITS;
+    const dim3 grid((unsigned)nblk, (unsigned)P), block(MHX_SELECT_THREADS);
+#define MHX_SELECT_LAUNCH(BITS, G)                                                                                        \
+    for (int first = 0; first < gmax; first += G)                                                                         \
+        hipLaunchKernelGGL((k_select_hist<BITS, G>), grid, block, 0, ctx->stream, s->tensor, s->N, s->d1, s->C, d_par, d_pf, d_ng, \
+                           (int)gstride, first, (int)shift, (int)digit_bits, top, chunk, d_hist)
+    if (digit_bits <= 8) { MHX_SELECT_LAUNCH(8, 16); }
+    else if (digit_bits <= 10) { MHX_SELECT_LAUNCH(10, 16); }
+    else { MHX_SELECT_LAUNCH(11, 8); }
+#undef MHX_SELECT_LAUNCH
+    if (hipGetLastError() != hipSuccess) return mhx_fail(MHX_EHIP, "%s: k_select_hist failed to launch", s->who);
+    // only the groups in use travel: rows of gmax << digit_bits counters out of a pitch of gstride << digit_bits
+    const size_t pitch = ((size_t)gstride << digit_bits) * sizeof(uint64_t), width = ((size_t)gmax << digit_bits) * sizeof(uint64_t);
+    HIP_TRY(hipMemcpy2DAsync(hist, pitch, d_hist, pitch, width, (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MHX_OK;
+}
+
+static int select_check_params(const char* who, const int32_t* params, int32_t nparams, int d1)
+{
+    if (!params || nparams <= 0) return mhx_fail(MHX_EINVAL, "%s: no parameters", who);
+    for (int i = 0; i < nparams; ++i)
+        if (params[i] < 0 || params[i] >= d1) return mhx_fail(MHX_EINVAL, "%s: parameter %d out of range [0, %d)", who, (int)params[i], d1);
+    return MHX_OK;
+}
+
+// the context's page-locked landing buffer for the histograms of a call (they arrive by DMA once per pass): kept from call to
+// call, grown on demand.  A host that cannot lock that much leaves the call to pageable memory.
+static void select_landing(mhx_ctx* ctx, int digit, int32_t nparams, int32_t nranks)
+{
+    const size_t words = mhx_select_hist_words(digit, nparams, nranks);
+    if (words <= ctx->select_landing_words) return;
+    if (ctx->select_landing) (void)hipHostFree(ctx->select_landing);
+    ctx->select_landing = nullptr; ctx->select_landing_words = 0;
+    void* q = nullptr;
+    if (hipSetDevice(ctx->device) == hipSuccess && mhx_host_alloc(words * sizeof(uint64_t), &q) == MHX_OK && q) {
+        ctx->select_landing = (uint64_t*)q;
+        ctx->select_landing_words = words;
+    } else (void)hipGetLastError();
+}
+
+int api_ctx_order_statistics(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                             const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
+{
+    const char* who = "mhx_ctx_order_statistics";
+    if (!ctx || !d_tensor || !out || !ranks || nranks <= 0) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
+    int rc = select_check_params(who, params, nparams, dim1);
+    if (rc) return rc;
+    select_source src{ctx, d_tensor, (long)n_samples, (long)nchains, dim1, params, nparams, who};
+    const int digit = opt_int(ctx, "SELECT_BITS", MHX_SELECT_DIGIT_BITS);
+    select_landing(ctx, digit, nparams, nranks);
+    return mhx_select_drive(who, MHX_KEY_BITS, digit, nparams, ranks, nranks, (uint64_t)n_samples * (uint64_t)nchains, select_hist_pass,
+                            &src, out, ctx->select_landing, ctx->select_landing_words);
+}
+
+static int select_need_tensor(const mhx_run* r, const char* who)
+{
+    if (!r) return mhx_fail(MHX_EINVAL, "%s: run is NULL", who);
+    if (r->moments_mode || r->n_saved < 1 || !r->d_samples)
+        return mhx_fail(MHX_ESTATE, "%s: the run holds no device sample tensor (moments mode, save_samples = 0 or a host-streamed run)", who);
+    return MHX_OK;
+}
+
+int api_run_order_statistics(mhx_run* r, const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
+{
+    const char* who = "mhx_run_order_statistics";
+    int rc = select_need_tensor(r, who);
+    if (rc) return rc;
+    if (!out || !ranks || nranks <= 0) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    if ((rc = select_check_params(who, params, nparams, r->dim + 1))) return rc;
+    select_source src{r->ctx, r->d_samples, (long)r->n_saved, (long)r->n, r->dim + 1, params, nparams, who};
+    const int digit = opt_int(r->ctx, "SELECT_BITS", MHX_SELECT_DIGIT_BITS);
+    select_landing(r->ctx, digit, nparams, nranks);
+    return mhx_select_drive(who, MHX_KEY_BITS, digit, nparams, ranks, nranks, (uint64_t)r->n_saved * (uint64_t)r->n, select_hist_pass,
+                            &src, out, r->ctx->select_landing, r->ctx->select_landing_words);
+}
+
+// the per-pass building block of the group form (mhx_group_order_statistics adds the members' histograms and scans once)
+int api_run_select_histogram(mhx_run* r, const int32_t* params, int32_t nparams, const uint64_t* prefixes, const int32_t* ngroups,
+                             int32_t gstride, int32_t shift, int32_t digit_bits, uint64_t* hist)
+{
+    const char* who = "mhx_run_select_histogram";
+    int rc = select_need_tensor(r, who);
+    if (rc) return rc;
+    if (!prefixes || !ngroups || !hist) return mhx_fail(MHX_EINVAL, "%s: NULL argument", who);
+    if ((rc = select_check_params(who, params, nparams, r->dim + 1))) return rc;
+    select_source src{r->ctx, r->d_samples, (long)r->n_saved, (long)r->n, r->dim + 1, params, nparams, who};
+    return select_hist_pass(&src, prefixes, ngroups, gstride, shift, digit_bits, hist);
+}

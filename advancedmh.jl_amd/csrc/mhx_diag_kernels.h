@@ -94,4 +94,117 @@ MHX_DEV void mhx_diag_from_moments_body(const mhx_real* __restrict__ mom_mean, c
         atomicAdd(&sums[(long)threadIdx.x * d1 + p], x);
     }
 }
+
+// ---- exact order statistics: one pass of a histogram radix SELECT over the strided tensor ----
+// A draw becomes an unsigned key of its own width whose unsigned order is the numeric order (sign set: all bits inverted;
+// sign clear: sign bit set); every NaN becomes the all-ones key, so NaNs come last as in numpy.sort.  -0.0 < +0.0 as keys.
+#if MHX_REAL64
+typedef unsigned long long mhx_key;
+#define MHX_KEY_BITS 64
+MHX_DEV mhx_key mhx_order_key(const double x)
+{
+    const mhx_key b = (mhx_key)__double_as_longlong(x);
+    if (x != x) return ~0ull;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+#else
+typedef unsigned int mhx_key;
+#define MHX_KEY_BITS 32
+MHX_DEV mhx_key mhx_order_key(const float x)
+{
+    const mhx_key b = __float_as_uint(x);
+    if (x != x) return ~0u;
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+#endif
+
+#define MHX_SELECT_THREADS 512
+// loads in flight per thread: 32 bytes per thread either way (16 KiB per block, up to 64 KiB per CU)
+#if MHX_REAL64
+#define MHX_SELECT_UNROLL 4
+#else
+#define MHX_SELECT_UNROLL 8
+#endif
+
+// one draw into the block's histograms.  The prefixes of a parameter's groups are distinct, so at most one matches: the slot is
+// picked by compares and selects and ONE LDS atomic follows (unused slots repeat prefix 0 and are visited first, so they never win)
+template <int BITS, int G>
+MHX_DEV void mhx_select_count(const mhx_key key, const mhx_key (&pf)[G], const int top, const int shift, const int hshift,
+                              const mhx_key dmask, unsigned* lds)
+{
+    const unsigned digit = (unsigned)((key >> shift) & dmask);
+    if (top) { atomicAdd(&lds[digit], 1u); return; }       // the first pass: one group of all draws
+    const mhx_key hi = (mhx_key)(key >> hshift);
+    int slot = -1;
+#pragma unroll
+    for (int g = G - 1; g >= 0; --g) slot = hi == pf[g] ? g : slot;
+    if (slot >= 0) atomicAdd(&lds[(slot << BITS) + digit], 1u);
+}
+
+// grid (blocks per parameter, parameters), block MHX_SELECT_THREADS.  Block (b, i) owns elements [b chunk, (b+1) chunk) of the
+// flattened (t, c) index space of row params[i]: element e is draw t = e / C of chain c = e - t C, so consecutive lanes read
+// consecutive chains (one division per thread, then a running offset).  A draw whose key has, above the current digit, the
+// prefix of group g (groups first .. first + ng - 1 of this parameter; `top`: the first pass, where every draw belongs to the
+// one group) counts in bin `digit` of that group's histogram in LDS (uint32: chunk < 2^32); the non-zero bins are then added to
+// the global uint64 histogram hist[i][gstride][1 << digit_bits] with integer atomics (sums independent of the order of
+// arrival).  LDS: G << BITS words whatever the number of ranks asked for.
+template <int BITS, int G>
+MHX_DEV void mhx_select_hist_body(const mhx_real* __restrict__ samples, const long N, const int d1, const long C,
+                                  const int* __restrict__ params, const unsigned long long* __restrict__ prefixes,
+                                  const int* __restrict__ ngroups, const int gstride, const int first, const int shift,
+                                  const int digit_bits, const int top, const unsigned long long chunk,
+                                  unsigned long long* __restrict__ hist, unsigned* lds)
+{
+    const int i = blockIdx.y;
+    int ng = ngroups[i] - first;
+    if (ng <= 0) return;                                   // uniform over the block
+    if (ng > G) ng = G;
+    const long p = params[i];
+    const unsigned long long S = (unsigned long long)N * (unsigned long long)C;
+    const unsigned long long e0 = (unsigned long long)blockIdx.x * chunk;
+    if (e0 >= S) return;
+    const unsigned long long e1 = e0 + chunk < S ? e0 + chunk : S;
+    for (int k = threadIdx.x; k < (ng << BITS); k += MHX_SELECT_THREADS) lds[k] = 0u;
+    mhx_key pf[G];
+    const unsigned long long* mine = prefixes + (long)i * gstride + first;
+#pragma unroll
+    for (int g = 0; g < G; ++g) pf[g] = (mhx_key)mine[g < ng ? g : 0];
+    __syncthreads();
+    const mhx_key dmask = (mhx_key)((1u << digit_bits) - 1u);
+    const int hshift = top ? 0 : shift + digit_bits;       // top: shift + digit_bits is the key width, not a legal shift count
+    // this thread's element e0 + tid + k THREADS: offset t ld + c into the row, advanced by the block width
+    const unsigned long long ef = e0 + threadIdx.x;
+    const long t0 = (long)(ef / (unsigned long long)C);
+    long c = (long)(ef - (unsigned long long)t0 * (unsigned long long)C);
+    const long ld = (long)d1 * C;
+    const long qt = MHX_SELECT_THREADS / C, qc = MHX_SELECT_THREADS - qt * C, step = qt * ld + qc, wrap = ld - C;
+    const mhx_real* src = samples + p * C + t0 * ld + c;
+    // whole sweeps of UNROLL elements per thread: every load is in bounds, none is predicated, all are issued before the first is used
+    const unsigned long long sweeps = (e1 - e0) / ((unsigned long long)MHX_SELECT_THREADS * MHX_SELECT_UNROLL);
+    for (unsigned long long it = 0; it < sweeps; ++it) {
+        mhx_real x[MHX_SELECT_UNROLL];
+#pragma unroll
+        for (int u = 0; u < MHX_SELECT_UNROLL; ++u) {
+            x[u] = *src;
+            src += step; c += qc;
+            if (c >= C) { c -= C; src += wrap; }
+        }
+#pragma unroll
+        for (int u = 0; u < MHX_SELECT_UNROLL; ++u) mhx_select_count<BITS, G>(mhx_order_key(x[u]), pf, top, shift, hshift, dmask, lds);
+    }
+    // the rest of the chunk, one element at a time
+    for (unsigned long long e = ef + sweeps * MHX_SELECT_THREADS * MHX_SELECT_UNROLL; e < e1; e += MHX_SELECT_THREADS) {
+        const mhx_real x = *src;
+        src += step; c += qc;
+        if (c >= C) { c -= C; src += wrap; }
+        mhx_select_count<BITS, G>(mhx_order_key(x), pf, top, shift, hshift, dmask, lds);
+    }
+    __syncthreads();
+    // bins at or above 1 << digit_bits stay zero (the digit is masked), so only legal bins of the global histogram are touched
+    unsigned long long* out = hist + (((long)i * gstride + first) << digit_bits);
+    for (int k = threadIdx.x; k < (ng << BITS); k += MHX_SELECT_THREADS) {
+        const unsigned v = lds[k];
+        if (v) atomicAdd(&out[((long)(k >> BITS) << digit_bits) + (k & ((1 << BITS) - 1))], (unsigned long long)v);
+    }
+}
 MHX_NS_END

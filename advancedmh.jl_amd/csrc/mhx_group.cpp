@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include "mhx_host_expand.h"    // mhx_host_usable_cpus
+#include "mhx_select.h"         // the bucket scan of the order statistics: the one a single run uses
 
 #include <chrono>
 #include <cmath>
@@ -333,4 +334,64 @@ extern "C" int mhx_group_ess_bulk_tail(mhx_group* g, const mhx_diag_cfg* cfg, co
         }
     }
     return MHX_OK;
+}
+
+// Exact order statistics of the union of all members' draws.  Per pass every member histograms its own shard (concurrently, each
+// on its own thread and device); integer histograms add, so the sum over the members is the histogram of the whole run and the
+// scan that serves a single run (mhx_select_drive) picks the next prefixes for all of them.
+namespace {
+struct group_select {
+    mhx_group* g;
+    const int32_t* params;
+    int32_t nparams;
+    std::vector<std::vector<uint64_t>> part;        // one landing buffer per member after the first (member 0 writes into `hist`)
+};
+int group_select_pass(void* user, const uint64_t* prefixes, const int32_t* ngroups, int32_t gstride, int32_t shift, int32_t digit_bits,
+                      uint64_t* hist)
+{
+    group_select* s = (group_select*)user;
+    const size_t n = ((size_t)s->nparams * gstride) << digit_bits;
+    for (auto& v : s->part) if (v.size() < n) v.resize(n);
+    int rc = for_all(s->g, "mhx_group_order_statistics", [s, prefixes, ngroups, gstride, shift, digit_bits, hist](int i) {
+        return mhx_run_select_histogram(s->g->mem[i]->run, s->params, s->nparams, prefixes, ngroups, gstride, shift, digit_bits,
+                                        i ? s->part[(size_t)i - 1].data() : hist);
+    });
+    if (rc) return rc;
+    for (int32_t p = 0; p < s->nparams; ++p)
+        for (int32_t k = 0; k < ngroups[p]; ++k) {
+            uint64_t* dst = hist + (((size_t)p * gstride + k) << digit_bits);
+            for (const auto& v : s->part) {
+                const uint64_t* src = v.data() + (((size_t)p * gstride + k) << digit_bits);
+                for (size_t b = 0; b < ((size_t)1 << digit_bits); ++b) dst[b] += src[b];
+            }
+        }
+    return MHX_OK;
+}
+}  // namespace
+
+extern "C" int mhx_group_order_statistics(mhx_group* g, const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
+{
+    const char* who = "mhx_group_order_statistics";
+    int rc = need_runs(g, who);
+    if (rc) return rc;
+    if (!params || nparams <= 0 || !ranks || nranks <= 0 || !out) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    const int d1 = g->mem[0]->dim + 1;
+    for (int32_t i = 0; i < nparams; ++i)
+        if (params[i] < 0 || params[i] >= d1) return mhx_fail(MHX_EINVAL, "%s: parameter %d out of range [0, %d)", who, (int)params[i], d1);
+    int64_t n_saved = 0, chains = 0;
+    for (auto& m : g->mem) {
+        int64_t ns = 0;
+        if ((rc = mhx_run_device_samples(m->run, nullptr, nullptr, &ns))) return rc;
+        if (&m != &g->mem.front() && ns != n_saved) return mhx_fail(MHX_ESTATE, "%s: the members hold different numbers of draws", who);
+        n_saved = ns;
+        chains += m->nchains;
+    }
+    if (n_saved < 1) return mhx_fail(MHX_ESTATE, "%s: the runs hold no device sample tensor", who);
+    // the digit width the members' contexts are set to (option SELECT_BITS of member 0), else the default
+    char buf[16] = {0};
+    int digit = MHX_SELECT_DIGIT_BITS;
+    if (mhx_ctx_get_option(g->mem[0]->ctx, "SELECT_BITS", buf, sizeof buf) == MHX_OK && buf[0]) digit = atoi(buf);
+    group_select s{g, params, nparams, std::vector<std::vector<uint64_t>>(g->mem.size() - 1)};
+    return mhx_select_drive(who, g->dtype == MHX_F64 ? 64 : 32, digit, nparams, ranks, nranks, (uint64_t)n_saved * (uint64_t)chains,
+                            group_select_pass, &s, out, nullptr, 0);
 }

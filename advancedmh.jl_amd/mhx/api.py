@@ -736,6 +736,44 @@ class MALA:
 # chains container (the part of MCMCChains.Chains the reference tests touch)
 
 
+DEFAULT_QUANTILE_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)        # the columns of MCMCChains' "Quantiles" table (README.md:65-71)
+
+
+def quantile_ranks(S, probs):
+    """(j, j1, g) of Julia's `quantile` / numpy's default ("type 7"): h = (S - 1) p, j = floor(h), j1 = min(j + 1, S - 1),
+    g = h - j; the quantile lies between the order statistics x_(j) and x_(j1).  p outside [0, 1] (or NaN) is refused."""
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if int(S) < 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "quantiles: no draws")
+    if probs.ndim != 1 or probs.size == 0 or not np.all((probs >= 0.0) & (probs <= 1.0)):
+        raise L.ArgumentError(L.MHX_EINVAL, "quantiles: probs must lie in [0, 1]")
+    h = (float(int(S)) - 1.0) * probs
+    j = np.floor(h)
+    g = h - j
+    j = j.astype(np.int64)
+    return j, np.minimum(j + 1, int(S) - 1), g
+
+
+def quantiles_from_order_statistics(lo, hi, g, top=None):
+    """Quantiles [..., nprobs] from the order statistics lo = x_(j), hi = x_(j1) and the weights g of quantile_ranks, in float64:
+    lo where lo == hi (no arithmetic: infinities stay, no NaN), else lo + g (hi - lo).  `top` [...]: the largest draw x_(S-1);
+    where it is NaN (NaNs order last, so the parameter holds one) every quantile of that row is NaN, as numpy's."""
+    lo, hi, g = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.where(lo == hi, lo, lo + g * (hi - lo))
+    if top is not None:
+        q = np.where(np.isnan(np.asarray(top, dtype=np.float64))[..., None], np.nan, q)
+    return q
+
+
+def _quantiles(order_statistics, S, probs, params):
+    """quantiles through ONE order_statistics call: the ranks j and j + 1 of every prob and the top rank"""
+    j, j1, g = quantile_ranks(S, probs)
+    x = order_statistics(np.concatenate([j, j1, [int(S) - 1]]), params)
+    n = len(j)
+    return quantiles_from_order_statistics(x[:, :n], x[:, n:2 * n], g, top=x[:, 2 * n])
+
+
 class Chains:
     """value[iteration, parameter, chain]; the last parameter is the internal `lp`
     (ext/AdvancedMHMCMCChainsExt.jl:36, :96-118)."""
@@ -786,10 +824,44 @@ class Chains:
                     ess_bulk=et["ess_bulk"], ess_tail=et["ess_tail"],
                     rhat=dg["rhat"][idx] if "rhat" in dg else np.full(len(idx), np.nan))
 
-    def __repr__(self):
-        head = "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
+    def quantile(self, probs=DEFAULT_QUANTILE_PROBS):
+        """The "Quantiles" table MCMCChains prints for the reference's chains (README.md:65-71): exact quantiles (Julia's and
+        numpy's default definition) of every parameter over all draws of all chains, selected on the device from the run's
+        sample buffer (mhx_run_order_statistics); internals (lp) are left out as in summarystats.
+        dict(parameters, probs, quantiles [nparams][nprobs])."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "quantile needs the live run (chain.state)")
+        idx = [i for i, n in enumerate(self.names) if n not in self.internals]
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        return dict(parameters=[self.names[i] for i in idx], probs=probs, quantiles=self.state.quantiles(probs, params=idx))
+
+    def _header(self):
+        """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
+        return "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
             self.value.shape[0], self.value.shape[1], self.value.shape[2],
             "Float64" if self.value.dtype == np.float64 else "Float32", self.start, self.thin, self.range()[-1])
+
+    def describe(self, probs=DEFAULT_QUANTILE_PROBS, max_lag=0):
+        """The two tables MCMCChains prints for the reference's chains (README.md:57-71) as text: "Summary Statistics" -- the columns
+        of summarystats() with naive_se = std / sqrt(S) and mcse = std / sqrt(ess_bulk), S the draws of all chains -- and
+        "Quantiles" below it."""
+        st, qt = self.summarystats(max_lag=max_lag), self.quantile(probs)
+        S = float(self.value.shape[0] * self.value.shape[2])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            naive_se, mcse = st["std"] / np.sqrt(S), st["std"] / np.sqrt(st["ess_bulk"])
+        head = self._header()
+        lines = [head, "", "Summary Statistics",
+                 "  parameters        mean       std  naive_se      mcse   ess_bulk   ess_tail      rhat"]
+        for i, n in enumerate(st["parameters"]):
+            lines.append("  %-12s %9.4f %9.4f %9.4f %9.4f %10.1f %10.1f %9.4f" % (
+                n, st["mean"][i], st["std"][i], naive_se[i], mcse[i], st["ess_bulk"][i], st["ess_tail"][i], st["rhat"][i]))
+        lines += ["", "Quantiles", "  parameters   " + " ".join("%9s" % ("%.1f%%" % (100.0 * p)) for p in qt["probs"])]
+        for i, n in enumerate(qt["parameters"]):
+            lines.append("  %-12s " % n + " ".join("%9.4f" % q for q in qt["quantiles"][i]))
+        return "\n".join(lines)
+
+    def __repr__(self):
+        head = self._header()
         try:
             st = self.summarystats()
         except Exception:
@@ -1132,6 +1204,28 @@ class Run:
         L.check(L.lib().mhx_run_ess_bulk_tail(self.h, C.byref(cfg), idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
                                               bulk.ctypes.data_as(dp), tail.ctypes.data_as(dp)))
         return dict(params=idx, ess_bulk=np.abs(bulk), ess_tail=np.abs(tail), bulk_truncated=bulk < 0, tail_truncated=tail < 0)
+
+    def order_statistics(self, ranks, params=None):
+        """Exact order statistics of the last sample buffer, selected on the device without a sort (mhx_run_order_statistics):
+        [nparams][nranks] float64, the draws at the 0-based positions `ranks` (any order, repeats allowed) of the ascending order
+        of the n_saved x nchains draws of each parameter row (default: all, lp included).  NaNs order last."""
+        idx = np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        out = np.empty((len(idx), len(rk)), dtype=np.float64)
+        L.check(L.lib().mhx_run_order_statistics(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
+                                                 rk.ctypes.data_as(C.POINTER(C.c_int64)), len(rk),
+                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def quantiles(self, probs=DEFAULT_QUANTILE_PROBS, params=None):
+        """[nparams][nprobs] float64: the quantiles (Julia's `quantile` / numpy's default definition) of the given parameter rows
+        over all draws of all chains of the last sample buffer -- two order statistics per prob, one order_statistics call."""
+        quantile_ranks(1, probs)                            # refuse bad probs before anything else
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
+        if n_saved.value < 1:
+            return self.order_statistics([0], params)       # raises the library's refusal (no device sample tensor)
+        return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
 
     def close(self):
         if self.h:

@@ -159,6 +159,31 @@ class Group:
         out.update(combine_diagnostics(out["sum_m"], out["sum_m2"], out["sum_v"], out["n_chains"], max(ns, 1)))
         return out
 
+    def order_statistics(self, ranks, params=None):
+        """Run.order_statistics over the UNION of all members' draws (mhx_group_order_statistics): ranks index the
+        n_saved x (all chains of the group) draws of a parameter; the members' integer histograms are added on the host, so the
+        answer is exact and equals the unsharded run's."""
+        from . import _lib as L
+        idx = np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        out = np.empty((len(idx), len(rk)), dtype=np.float64)
+        L.check(L.lib().mhx_group_order_statistics(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
+                                                   rk.ctypes.data_as(C.POINTER(C.c_int64)), len(rk),
+                                                   out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def quantiles(self, probs=None, params=None):
+        """Run.quantiles over all chains of all members: [nparams][nprobs] float64"""
+        from . import _lib as L
+        from .api import DEFAULT_QUANTILE_PROBS, _quantiles, quantile_ranks
+        probs = DEFAULT_QUANTILE_PROBS if probs is None else probs
+        quantile_ranks(1, probs)
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.runs[0].h, None, None, C.byref(n_saved)))
+        if n_saved.value < 1:
+            return self.order_statistics([0], params)       # raises the library's refusal
+        return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
+
     def close_runs(self):
         for r in self.runs:
             r.close()

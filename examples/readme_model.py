@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's README example (README.md:18-63) on the GPU engine: a Normal(mu, sigma) model of 30 data
 points, RWMH with an identity-covariance proposal, 100 000 draws -- here from 256 chains of 400 draws after
-200 discarded each, all advanced together on one MI355X -- and the MCMCChains-style summary.
+200 discarded each, all advanced together on one MI355X -- and the MCMCChains-style summary: the "Summary Statistics" and "Quantiles" tables.
 
     python examples/readme_model.py
 """
@@ -26,6 +26,9 @@ spl = mhx.RWMH(mhx.MvNormal(mhx.zeros(2), mhx.I))
 chain = mhx.sample(model, spl, 400, 256, param_names=["mu", "sigma"], chain_type=mhx.Chains, discard_initial=200,
                    initial_params=np.array([0.0, 1.0]), seed=1234)
 print(chain)
+# ... and the two tables MCMCChains prints under it (README.md:57-71): summary statistics with naive_se / mcse, and the quantiles,
+# selected exactly on the device from all 102 400 draws (mhx_run_order_statistics)
+print(chain.describe())
 print("data: mean %.4f std %.4f;  acceptance rate %.3f;  kernel variant %d" % (
     data.mean(), data.std(), chain.accepted[1:].mean(), chain.stats["kernel_variant"]))
 

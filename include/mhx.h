@@ -84,6 +84,7 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   form -- hence a summation order -- from the chain count (reduce_lanes = 0), it picks for that count, so a shard
  *                   runs what the unsharded run runs; mhx_group_shard sets it on the member's context, a process of a
  *                   multi-process run sets it itself)
+ *   summary         SELECT_BITS (digit width of a pass of mhx_*_order_statistics, 1..11; default 11; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
  * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
@@ -580,6 +581,17 @@ int mhx_emcee_exchange_plan(mhx_run *run, int half, int world, size_t *stride, v
 int mhx_emcee_exchange_pack(mhx_run *run, int half, int rank, int world, void *part);
 int mhx_emcee_exchange_unpack(mhx_run *run, int half, int rank, int world, const void *stage, size_t stride);
 
+/* ---- building block of the order statistics of ONE set of draws sharded over several GPUs (mhx_group_order_statistics; a host
+ * that brings its own transport adds the histograms of its ranks the same way).  One pass of the radix select described at
+ * mhx_run_order_statistics below over this run's sample tensor: for parameter slot i (row params[i]) and group g < ngroups[i],
+ *   hist[((i * gstride + g) << digit_bits) + b] = number of draws whose key has the prefix prefixes[i * gstride + g] above bit
+ *   shift + digit_bits (right-aligned) and the digit (key >> shift) & (2^digit_bits - 1) == b
+ * (shift + digit_bits == key width, 32 or 64: the first pass, one group holding every draw, its prefix ignored).  1 <= digit_bits
+ * <= 11.  hist is HOST memory of (nparams * gstride) << digit_bits counters; those of the groups in use are overwritten.  Counts
+ * are integers: the histograms of shards add, in any order, to the histogram of the whole.  Blocking. */
+int mhx_run_select_histogram(mhx_run *run, const int32_t *params, int32_t nparams, const uint64_t *prefixes, const int32_t *ngroups,
+                             int32_t gstride, int32_t shift, int32_t digit_bits, uint64_t *hist);
+
 /* ---------------------------------------------------------------------------------------------
  * Collectives (RCCL over xGMI; one process per GPU).  Chains shard by global id with no data-path collective; these
  * carry the acceptance totals and the R-hat / ESS sums of a sharded run (ONE all-reduce of 3(dim+1)+3 doubles per
@@ -614,6 +626,26 @@ int mhx_comm_allgather_walkers(mhx_comm *comm, mhx_run *run, int half);
  * (cfg.max_lag, cfg.ess_chains, cfg.split) is taken of those series.  Negated values: as for ess[] above. */
 int mhx_run_ess_bulk_tail(mhx_run *run, const mhx_diag_cfg *cfg, const int32_t *params, int32_t nparams,
                           double *ess_bulk, double *ess_tail /* each [nparams], either may be NULL */);
+
+/* Exact order statistics (and with them quantiles, medians, credible intervals: what MCMCChains prints as its "Quantiles" table,
+ * README.md:65-71) of the parameters params[0..nparams) (indices into the dim+1 rows, lp = dim) of the sample buffer, without a
+ * sort and without a copy of the draws: a histogram radix SELECT that reads the [n_saved][dim+1][nchains] tensor in place.
+ *   ranks[0..nranks)   0-based positions in the ascending order of a parameter's S = n_saved * nchains draws; any order, repeats
+ *                      allowed; NaNs order last (as numpy.sort); there is no 2^32 limit on S
+ *   out[nparams][nranks]  the draws at those positions as double (an fp32 draw is widened exactly); -0.0 and +0.0 are equal
+ *                      draws: either may be returned
+ * A draw is mapped to an unsigned key of its own width whose order is the numeric order; a pass histograms one digit (11 bits;
+ * option SELECT_BITS: 1..11) of the keys that match the prefix selected so far -- all parameters and all ranks in ONE sweep
+ * over the tensor, per-block histograms in LDS added to uint64 counters with integer atomics, so results are reproducible bit
+ * for bit -- and the host picks the bin that holds each rank.  6 passes for fp64, 3 for fp32; ranks are served in batches of 32,
+ * so scratch is nparams x 32 x 2048 counters at most, whatever S.
+ * MHX_EINVAL: a rank outside [0, S), a parameter outside [0, dim]; MHX_ESTATE: the run holds no device sample tensor (moments
+ * mode, save_samples = 0, a host-streamed run that kept nothing).  Nothing is written to `out` unless the call succeeds. */
+int mhx_run_order_statistics(mhx_run *run, const int32_t *params, int32_t nparams, const int64_t *ranks, int32_t nranks, double *out);
+/* the same select on a caller's device tensor [n_samples][dim1][nchains] (chain fastest: the engine's layout, what
+ * mhx_run_device_samples hands out) of the context's dtype; work queued on other streams must have completed */
+int mhx_ctx_order_statistics(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                             const int32_t *params, int32_t nparams, const int64_t *ranks, int32_t nranks, double *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
@@ -650,6 +682,10 @@ int mhx_group_diagnostics(mhx_group *g, const mhx_diag_cfg *cfg, double *sum_m, 
                           int64_t *n_chains);
 /* bulk / tail ESS of every member (ranks pooled within a member's shard) added over the members */
 int mhx_group_ess_bulk_tail(mhx_group *g, const mhx_diag_cfg *cfg, const int32_t *params, int32_t nparams, double *ess_bulk, double *ess_tail);
+/* mhx_run_order_statistics over the UNION of all members' draws: ranks index S = n_saved x (the sum of the members' chains).  Per
+ * pass every member histograms its own shard concurrently (mhx_run_select_histogram), the group adds the integer histograms on the
+ * host and scans once: exact, and equal to the unsharded run's answer */
+int mhx_group_order_statistics(mhx_group *g, const int32_t *params, int32_t nparams, const int64_t *ranks, int32_t nranks, double *out);
 
 #ifdef __cplusplus
 }
