@@ -188,9 +188,13 @@ MHX_DEV double  mhx_fma(double a, double b, double c) { return __builtin_fma(a, 
 #define MHX_INF    __builtin_inf()
 #define MHX_NAN    __builtin_nan("")
 
-// a / b for finite normal operands whose quotient is normal (or a == 0): the correctly rounded sequence hipcc emits for an
-// fp64 division -- reciprocal estimate, two Newton steps, quotient, residual, final fma -- without its range scaling
-// (v_div_scale x 2) and special-case fix-up (v_div_fixup), which are the identity in that range: 8 instead of 11 instructions
+// a / b for normal operands with |b| < 2^1022 (1 / b is normal) and |a| >= 2^-968 (the residual a - b q, a multiple of
+// ulp(b) ulp(q), is exact) whose quotient is normal, or a == +0: the correctly rounded sequence hipcc emits for an fp64 division
+// -- reciprocal estimate, two Newton steps, quotient, residual, final fma -- without its range scaling (v_div_scale x 2) and
+// special-case fix-up (v_div_fixup), which are the identity in that range: 8 instead of 11 instructions.  Outside it the result
+// can be one ulp off (|a| < 2^-969, |b| >= 2^1023) and a == -0 gives +0.  The one caller, mhx_log_core, sends b in [1.7, 2.42]
+// and a == +0 or 2^-53 <= |a| < 0.42.  Verified bit for bit on near-midpoint quotients across that domain and on the caller's
+// ranges: tests/test_gpu_primitives.py (test_div_normal_is_correctly_rounded, test_log_core_division_is_correctly_rounded)
 MHX_DEV double mhx_div_normal(const double a, const double b)
 {
     double y = __builtin_amdgcn_rcp(b);
@@ -289,7 +293,9 @@ MHX_DEV double mhx_sqrt(double x) { return __builtin_sqrt(x); }   // correctly r
 MHX_DEV double mhx_abs(double x) { return __builtin_fabs(x); }
 // Correctly rounded sqrt for a NORMAL positive x away from the ends of the exponent range (the Box-Muller radius argument
 // -2 ln u lies in [2.2e-16, 74]): the sequence hipcc emits -- v_rsq_f64, one coupled Goldschmidt step, two residual
-// corrections -- without its pre/post scaling for x < 2^-767 and its class test for 0 / inf: 10 instead of 17 instructions
+// corrections -- without its pre/post scaling for x < 2^-767 and its class test for 0 / inf: 10 instead of 17 instructions.
+// Verified bit for bit on [2^-52, 74] -- near-midpoint arguments of both exponent parities, the ends, 2^22 random arguments:
+// tests/test_gpu_primitives.py (test_sqrt_normal_is_correctly_rounded)
 MHX_DEV double mhx_sqrt_normal(const double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
@@ -641,9 +647,12 @@ MHX_DEV float mhx_exp(float x)
 MHX_DEV float mhx_sqrt(float x) { return __builtin_sqrtf(x); }   // correctly rounded (default HIP lowering)
 MHX_DEV float mhx_abs(float x) { return __builtin_fabsf(x); }
 
-// Correctly rounded sqrt for x that is +-0 or a NORMAL positive number: the hardware estimate (1 ulp) and
+// Correctly rounded sqrt for x that is +-0 or a normal positive number in [2^-80, 2^122): the hardware estimate (1 ulp) and
 // the same two-residual fix-up hipcc emits, without its denormal pre-scaling and class test (7 of 17
-// instructions).  The Box-Muller radius argument -2 ln u is 0 or >= 1.19e-7.
+// instructions).  The Box-Muller radius argument -2 ln u is 0 or >= 1.19e-7.  Near the bottom of the exponent range the
+// residuals x - s' s (multiples of ulp(s)^2) underflow and the result can be one ulp low: sqrt(FLT_MIN) is.  Verified bit for
+// bit on every float of [1, 4) -- all mantissas, both exponent parities -- and on near-midpoint arguments from 2^-80 to 2^122:
+// tests/test_gpu_primitives.py (test_sqrt_normal_fp32_is_correctly_rounded_on_every_mantissa, test_sqrt_normal_is_correctly_rounded)
 MHX_DEV float mhx_sqrt_normal(float x)
 {
     const float s = __builtin_amdgcn_sqrtf(x);
