@@ -326,6 +326,12 @@ extern "C" int mhx_run_stats(mhx_run* r, mhx_stats* out)
     NEED(r, "mhx_run_stats");
     return is64(r) ? mhx_f64::api_run_stats(R64(r), out) : mhx_f32::api_run_stats(R32(r), out);
 }
+extern "C" const char* mhx_run_form_name(const mhx_run* r)
+{
+    if (!r) return "";
+    return is64(r) ? mhx_f64::api_run_form_name(reinterpret_cast<const mhx_f64::mhx_run*>(r))
+                   : mhx_f32::api_run_form_name(reinterpret_cast<const mhx_f32::mhx_run*>(r));
+}
 extern "C" int mhx_run_shape(const mhx_run* r, int32_t* dim, int32_t* nchains)
 {
     NEED(r, "mhx_run_shape");

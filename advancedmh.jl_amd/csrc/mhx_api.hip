@@ -124,6 +124,15 @@ k_rwmh_coop(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const m
 {
     mhx_rwmh_coop_body<L, NBL, TK, PK, MOM, MHX_WALK_PLAIN, GEN>(a, tparams, pvec);
 }
+#if MHX_REAL64
+// the same shape as generator / consumer wave pairs (mhx_rwmh_coop_pairs_body): 512 threads, two waves per SIMD
+template <int L, int NBL, int TK, int PK>
+__global__ void __launch_bounds__(512)
+k_rwmh_coop_pairs(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ pvec)
+{
+    mhx_rwmh_coop_pairs_body<L, NBL, TK, PK>(a, tparams, pvec);
+}
+#endif
 __global__ void __launch_bounds__(256)
 k_moments_first(const mhx_real* __restrict__ x, const mhx_real* __restrict__ lp, mhx_real* mean, mhx_real* m2, const int n,
                 const long ld, const int d)
@@ -137,6 +146,7 @@ struct prebuilt_coop {
     void (*fn)(const mhx_rwmh_args, const mhx_real*, const mhx_real*);
     void (*fn_mom)(const mhx_rwmh_args, const mhx_real*, const mhx_real*);
     int gen;                             // MHX_GEN_*: the normal generator the kernel was built with
+    void (*fn_pairs)(const mhx_rwmh_args, const mhx_real*, const mhx_real*);   // `fn` as generator / consumer wave pairs, or null
 };
 // the BASELINE shapes: C2 (65 536 chains x d = 100) and C5 (32 768 chains per GPU x d = 1000); a double takes two VGPRs,
 // so the fp64 engine spreads a chain over more lanes
@@ -159,7 +169,13 @@ static const prebuilt_coop k_prebuilt_coop[] = {
      k_rwmh_coop<MHX_C5_L, MHX_C5_NBL, MHX_TARGET_BANANA, MHX_PROP_ISO, true>},
     // the same shapes with the ziggurat generator (MHX_FLAG_ZIGGURAT; both widths since round 6)
     {MHX_C2_L, MHX_C2_NBL, MHX_TARGET_ISO_GAUSS, MHX_PROP_ISO,
-     k_rwmh_coop<MHX_C2_L, MHX_C2_NBL, MHX_TARGET_ISO_GAUSS, MHX_PROP_ISO, false, MHX_GEN_ZIGGURAT>, nullptr, MHX_GEN_ZIGGURAT},
+     k_rwmh_coop<MHX_C2_L, MHX_C2_NBL, MHX_TARGET_ISO_GAUSS, MHX_PROP_ISO, false, MHX_GEN_ZIGGURAT>, nullptr, MHX_GEN_ZIGGURAT,
+#if MHX_REAL64
+     k_rwmh_coop_pairs<MHX_C2_L, MHX_C2_NBL, MHX_TARGET_ISO_GAUSS, MHX_PROP_ISO>
+#else
+     nullptr
+#endif
+    },
     {MHX_C5_L, MHX_C5_NBL, MHX_TARGET_FUNNEL, MHX_PROP_ISO,
      k_rwmh_coop<MHX_C5_L, MHX_C5_NBL, MHX_TARGET_FUNNEL, MHX_PROP_ISO, false, MHX_GEN_ZIGGURAT>,
      k_rwmh_coop<MHX_C5_L, MHX_C5_NBL, MHX_TARGET_FUNNEL, MHX_PROP_ISO, true, MHX_GEN_ZIGGURAT>, MHX_GEN_ZIGGURAT},
@@ -281,7 +297,7 @@ int api_ctx_device(const mhx_ctx* ctx) { return ctx->device; }
 // taint the context; the release library does not even carry their names.
 struct opt_name { const char* name; int probe; };
 static const opt_name k_opt_names[] = {
-    {"NO_PREBUILT", 0}, {"NO_MFMA", 0}, {"MFMA_WAVES", 0}, {"REG_MAX_DIM", 0}, {"REG_XR", 0}, {"REG_UNROLL", 0}, {"REG_WAVES", 0}, {"REG_ZSLAB", 0}, {"COOP_WAVES", 0},
+    {"NO_PREBUILT", 0}, {"NO_MFMA", 0}, {"MFMA_WAVES", 0}, {"REG_MAX_DIM", 0}, {"REG_XR", 0}, {"REG_UNROLL", 0}, {"REG_WAVES", 0}, {"REG_ZSLAB", 0}, {"COOP_WAVES", 0}, {"COOP_PAIRS", 0},
     {"MALA_XR", 0}, {"RAM_G", 0}, {"RAM_LDS_PAD", 0}, {"WAVE_K", 0},
     {"EMCEE_MFMA", 0}, {"EMCEE_MFMA_WAVES", 0}, {"EMCEE_SCALAR", 0}, {"EMCEE_SCAL_MODE", 0}, {"EMCEE_SCAL_WPB", 0}, {"EMCEE_SCAL_REC", 0},
     {"EMCEE_FUSED", 0}, {"EMCEE_PERSIST", 0}, {"EMCEE_PRELOAD", 0}, {"EMCEE_DEFER", 0}, {"EMCEE_SWEEP_DEFER", 0}, {"EMCEE_WAVES", 0},
@@ -887,6 +903,11 @@ struct mhx_run : mhx_handle_hdr {
     uint32_t* d_acc = nullptr;
     unsigned char* d_last = nullptr;
     unsigned long long* d_acc_total = nullptr;
+    // mhx_run_sample reads d_acc_total ONCE per call: `acc_total_host` is the total the previous call read (valid until the counter
+    // is reset or a call fails half way), the new one lands in the page-locked `acc_total_pin` by a copy ahead of the call's one sync
+    unsigned long long acc_total_host = 0;
+    bool acc_total_known = false;
+    unsigned long long* acc_total_pin = nullptr;
     // sample buffer of the last mhx_run_sample
     mhx_real* d_samples = nullptr;
     unsigned char* d_accepted = nullptr;
@@ -903,6 +924,7 @@ struct mhx_run : mhx_handle_hdr {
     // kernel choice
     int normal_gen = MHX_GEN_BOX_MULLER; // how stream bits become standard normals (MHX_FLAG_ZIGGURAT: the table ziggurat, fp64)
     size_t reg_lds = 0;                  // dynamic LDS of the register kernel: the tail of a state that does not fit beside the candidate
+    bool coop_pairs = false;             // the cooperative kernel as generator / consumer wave pairs: 512-thread blocks (not the moments twin)
     size_t coop_lds = 0;                 // dynamic LDS of the cooperative kernel (ziggurat: layer table + the step's normals)
     int coop_tr = 0;                     // ... and whether it holds the row-transposition buffer of the one / two-chains-per-wave shapes
     int coop_L = 1;                      // lanes per chain (reduction shape of the separable targets)
@@ -930,6 +952,7 @@ struct mhx_run : mhx_handle_hdr {
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
                         d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab};
         for (void* p : ptrs) if (p) (void)hipFree(p);
+        if (acc_total_pin) (void)hipHostFree(acc_total_pin);
     }
 };
 
@@ -941,6 +964,7 @@ static int run_alloc_state(mhx_run* r)
     HIP_TRY(hipMalloc(&r->d_acc, n * sizeof(uint32_t)));
     HIP_TRY(hipMalloc(&r->d_last, n));
     HIP_TRY(hipMalloc(&r->d_acc_total, sizeof(unsigned long long)));
+    HIP_TRY(hipHostMalloc((void**)&r->acc_total_pin, sizeof(unsigned long long), hipHostMallocDefault));
     HIP_TRY(hipMemsetAsync(r->d_acc, 0, n * sizeof(uint32_t), r->ctx->stream));
     HIP_TRY(hipMemsetAsync(r->d_last, 0, n, r->ctx->stream));
     HIP_TRY(hipMemsetAsync(r->d_acc_total, 0, sizeof(unsigned long long), r->ctx->stream));
@@ -1256,11 +1280,19 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: %d blocks per lane need %d bytes of LDS per block (limit %d); use more lanes per chain",
                             NBL, (int)MHX_ZIG_LDS_BYTES(NBL), (int)MHX_LDS_PER_BLOCK);
         if (zig) r->coop_lds = MHX_ZIG_LDS_BYTES(NBL);
+        // Generator / consumer wave pairs (mhx_rwmh_coop_pairs_body): where the fp64 ziggurat form runs ONE wave per SIMD, a plain walk
+        // with one scale, one step per fix-up group (10 to 13 blocks per lane).  Option COOP_PAIRS: 0 = the one-wave body, 1 = pairs,
+        // unset = the library's choice (MHX_COOP_PAIRS_DEFAULT); a shape outside the rule keeps the one-wave body whatever the option
+        // says.  Same chains bit for bit either way.
+        const bool pairs_fit = MHX_REAL64 && zig && !walk && pk == MHX_PROP_ISO && MHX_COOP_WAVES(NBL) == 1 && MHX_ZIG_KS(NBL) == 1 && L < 32 &&
+                               !waves_override;      // (8 or 9 blocks per lane: two steps per fix-up group, the one-wave body's own gain)
+        const bool pairs = pairs_fit && opt_int(ctx, "COOP_PAIRS", MHX_COOP_PAIRS_DEFAULT) != 0;
         if (!opt_on(ctx, "NO_PREBUILT") && !waves_override && !walk)
             for (const auto& pb : k_prebuilt_coop)
                 if (pb.L == L && pb.NBL == NBL && pb.TK == tk && pb.PK == pk && pb.gen == (zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER)) {
                     r->reg_fn = pb.fn; r->reg_fn_mom = pb.fn_mom; r->variant = KF_COOP; r->normal_gen = pb.gen;
-                    for (auto f : {pb.fn, pb.fn_mom})
+                    if (pairs && pb.fn_pairs) { r->reg_fn = pb.fn_pairs; r->coop_pairs = true; }
+                    for (auto f : {r->reg_fn, pb.fn_mom})
                         if (f && (rc = kernel_lds_limit((const void*)f, r->coop_lds, "cooperative kernel (ziggurat)"))) return rc;
                 }
         // the kernel's defines; its running-moments twin (mhx_run_sample, MHX_SAVE_MOMENTS) is built from this list with MHX_JIT_MOM=1
@@ -1271,6 +1303,7 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             jit_module* m = nullptr;
             std::vector<std::string> defs = r->coop_defs;
             if (waves_override > 0) defs.push_back("MHX_JIT_WAVES=" + std::to_string(waves_override));
+            if (pairs) defs.push_back("MHX_JIT_PAIRS=1");
 #ifdef MHX_TOOLS_BUILD
             if (const int zf = opt_int(ctx, "ZIG_FORCE_FAIL", 0); zf > 0)          // test hook: see mhx_rwmh_kernels.h (the chains stay valid)
                 defs.push_back("MHX_ZIG_FORCE_FAIL=" + std::to_string(zf));
@@ -1280,7 +1313,8 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             }
 #endif
             rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_kernels.h"), defs, &m);
-            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_coop", &r->jit_step, r->coop_lds, "cooperative kernel (ziggurat)");
+            if (rc == MHX_OK) rc = jit_kernel(m, pairs ? "mhx_jit_rwmh_coop_pairs" : "mhx_jit_rwmh_coop", &r->jit_step, r->coop_lds, "cooperative kernel (ziggurat)");
+            if (rc == MHX_OK) r->coop_pairs = pairs;
             if (rc == MHX_OK) { r->variant = KF_COOP_JIT; r->normal_gen = zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER; }
             else if (cfg->reduce_lanes > 1 || zig) return rc;      // the caller asked for this shape explicitly
         }
@@ -1588,10 +1622,11 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
                 void* params[] = {&a, &tp, &pv};
                 HIP_TRY(hipModuleLaunchKernel(r->jit_step_mom, grid, 1, 1, 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
             } else if (r->variant == KF_COOP) {
-                hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(256), r->coop_lds, ctx->stream, a, tp, pv);
+                // (wave pairs: the same grid -- a block's 4 pairs serve the chains of the one-wave body's 4 waves)
+                hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(r->coop_pairs ? 512 : 256), r->coop_lds, ctx->stream, a, tp, pv);
             } else {
                 void* params[] = {&a, &tp, &pv};
-                HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
+                HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, r->coop_pairs ? 512 : 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
             }
         } else if (r->variant == KF_MFMA && r->mfma_stream) {
             const unsigned grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
@@ -1662,6 +1697,7 @@ int api_run_init(mhx_run* r, const mhx_real* initial_params)
     if (rc) return rc;
     r->initialised = true;
     r->tau = 0;
+    r->acc_total_known = false;
     HIP_TRY(hipMemsetAsync(r->d_acc_total, 0, sizeof(unsigned long long), r->ctx->stream));
     return MHX_OK;
 }
@@ -1721,8 +1757,13 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->stats.normal_gen = r->normal_gen;
     r->stats.factor_band = r->kind == RUN_EMCEE ? r->emcee_band : -1;
     auto total_accepts = [&](unsigned long long* out) -> int { return run_total_accepts(r, out); };
-    unsigned long long acc_before = 0;
-    { int rc0 = total_accepts(&acc_before); if (rc0) return rc0; }
+    // One synchronisation per call: the total before this call is what the previous call read (the counter moves in mhx_run_sample /
+    // mhx_run_sample_to_host only, and both leave their reading here); the total after it is copied to a page-locked word on the
+    // stream, ahead of the single hipStreamSynchronize.  An ensemble sums its per-walker counts on demand (run_total_accepts).
+    const bool one_sync = r->kind != RUN_EMCEE;
+    unsigned long long acc_before = r->acc_total_host;
+    if (!one_sync || !r->acc_total_known) { int rc0 = total_accepts(&acc_before); if (rc0) return rc0; }
+    r->acc_total_known = false;          // (until this call has read the new total: an error return leaves the counter unknown)
 
     uint32_t save_next = MHX_NO_SAVE;
     int save_slot = 0;
@@ -1806,11 +1847,15 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     }
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    if (one_sync) HIP_TRY(hipMemcpyAsync(r->acc_total_pin, r->d_acc_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     unsigned long long acc_after = 0;
-    { int rc1 = total_accepts(&acc_after); if (rc1) return rc1; }
+    if (one_sync) acc_after = *r->acc_total_pin;
+    else { int rc1 = total_accepts(&acc_after); if (rc1) return rc1; }
+    r->acc_total_host = acc_after;
+    r->acc_total_known = one_sync;
     r->stats.kernel_ms = ms;
     r->stats.transitions = nT * (uint64_t)r->n;
     r->stats.accepted = acc_after - acc_before;
@@ -1981,6 +2026,7 @@ int api_run_load_state(mhx_run* r, const void* blob, size_t bytes)
     r->seed = h.seed; r->first_id = h.first_id; r->tau = h.tau; r->last_eta = h.last_eta;
     r->initialised = true;
     r->n_saved = 0;
+    r->acc_total_known = false;
     HIP_TRY(hipMemsetAsync(r->d_acc_total, 0, sizeof(unsigned long long), r->ctx->stream));
     if (r->kind == RUN_EMCEE) { int rc = emcee_sync_state(r, 0); if (rc) return rc; }      // ABI layout -> walker-major
     HIP_TRY(hipStreamSynchronize(r->ctx->stream));
@@ -1994,6 +2040,31 @@ int api_run_stats(mhx_run* r, mhx_stats* out)
     out->tainted = r->ctx->tainted ? 1 : 0;
     out->register_form = r->fam_reg ? 1 : 0;
     return MHX_OK;
+}
+
+// the name of the run's kernel form (enum kernel_form), with the body it was compiled as where a form has two
+const char* api_run_form_name(const mhx_run* r)
+{
+    if (!r) return "";
+    switch (r->variant) {
+    case KF_GENERIC: return "generic";
+    case KF_REG: return "reg";
+    case KF_REG_JIT: return "reg_jit";
+    case KF_COOP: return r->coop_pairs ? "coop_pairs" : "coop";
+    case KF_COOP_JIT: return r->coop_pairs ? "coop_jit_pairs" : "coop_jit";
+    case KF_DENSE_COOP: return "dense_coop";
+    case KF_EMCEE_PERSIST: return "emcee_persist";
+    case KF_EMCEE_SEQ: return "emcee_seq";
+    case KF_MFMA: return "mfma";
+    case KF_EMCEE_SCAL: return "emcee_scal";
+    case KF_EMCEE_MFMA: return "emcee_mfma";
+    case KF_WAVE: return "wave";
+    case KF_RAM_DEFER: return "ram_defer";
+    case KF_FAMILY: return "family";
+    case KF_COND: return "cond";
+    case KF_COMPOSITE: return "composite";
+    }
+    return "";
 }
 
 int api_run_host_stats(mhx_run* r, mhx_host_stats* out)

@@ -293,6 +293,7 @@ int api_run_sample_to_host(mhx_run* r, const mhx_schedule* s, mhx_real* host_sam
     unsigned long long acc_before = 0, acc_after = 0;
     rc = run_total_accepts(r, &acc_before);
     if (rc) return rc;
+    r->acc_total_known = false;          // (mhx_run_sample's copy of the counter: this call moves it)
     r->n_saved = 0;                      // the device buffer holds slabs, not the tensor: diagnostics need mhx_run_sample
     r->moments_mode = false;
     r->rec_n = 0;
@@ -420,6 +421,8 @@ int api_run_sample_to_host(mhx_run* r, const mhx_schedule* s, mhx_real* host_sam
     HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     rc = run_total_accepts(r, &acc_after);
     if (rc) return rc;
+    r->acc_total_host = acc_after;
+    r->acc_total_known = r->kind != RUN_EMCEE;
     r->stats.kernel_ms = ms;             // the sampler kernels INCLUDING their waits for a free slab
     r->stats.transitions = nT * (uint64_t)r->n;
     r->stats.accepted = acc_after - acc_before;

@@ -37,6 +37,11 @@ MHX_NS_BEGIN
 #define MHX_COOP_NBL_MAX 16
 #define MHX_COOP_WAVES(NBL) ((NBL) <= 5 ? 4 : ((NBL) <= 13 ? 2 : 1))
 #endif
+// the library's choice between the one-wave body and generator / consumer wave pairs where both exist (context option COOP_PAIRS):
+// pairs -- C2 fp64 2.63 against 3.01 ms per launch on one box, five runs each, ranges apart (profiles/pairs_c2_f64_ab.txt)
+#ifndef MHX_COOP_PAIRS_DEFAULT
+#define MHX_COOP_PAIRS_DEFAULT 1
+#endif
 
 struct mhx_rwmh_args {
     mhx_real* x;                 // [dim][ld]   chain state
@@ -1394,6 +1399,298 @@ MHX_DEV void mhx_rwmh_coop_body(const mhx_rwmh_args& a, const mhx_real* __restri
     if (lane == 0) atomicAdd(a.acc_total, (mhx_u64)wave_acc);
 }
 
+#if MHX_REAL64
+// The cooperative kernel as generator / consumer wave PAIRS (fp64, ziggurat, plain walk, one scale, a record or none): where the body
+// above runs ONE wave per SIMD (MHX_COOP_WAVES(NBL) == 1) the wave issues an instruction every ~7 cycles and is short of both the
+// memory and the compute limit.  The normals of a step depend on (chain, step) only, never on the state -- so a block of 512 threads
+// splits the step by role: waves 0-3 GENERATE (phase A + mhx_zig_fixup, the text of the body above) the normals of step t + 1 into
+// the slab of their pair while waves 4-7 CONSUME step t (slab -> registers, candidate, target, accept, state update, record).  Wave
+// w and wave w + 4 serve the chains of the body's wave w: same chain ids, same grid, same Philox counters, same expressions in the
+// same order -- the chains are bit for bit the body's.
+// Registers: the consumer holds x and the normals (2 x 8 NBL VGPRs) and no Philox pipeline, the generator the pipeline and neither
+// array: both under the 256 a wave of a 512-thread block gets.  LDS: ONE slab per pair, MHX_ZIG_LDS_BYTES(NBL) as above.
+// Hand-over: block-wide barriers only, two per step -- generate | barrier | slab -> registers | barrier | consume; the consume part
+// runs beside the generate part of the next step.  (The generator meets the second barrier inside the next step's first block, just
+// ahead of its first write to the slab: a twelfth of its phase A covers the consumer's read-back.)  Each role runs its own loop of a.nsteps iterations with exactly two barriers per
+// iteration (one loop with `if (role)` parts was built first: x then counts as live through the generator's code and the kernel
+// spills 250 registers), so every wave executes the same number of barriers whatever its role, whether its chains exist and whether
+// the step is saved; no wave leaves before its loop ends; nothing is polled, no wave sleeps.
+template <int L, int NBL, int TK, int PK>
+MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __restrict__ tparams,
+                                      const mhx_real* __restrict__ pvec)
+{
+    constexpr int CPW = 64 / L;                    // chains per pair
+    static_assert(CPW > 2, "one / two chains per wave move their rows through LDS (tr_io): today's body");
+    static_assert(PK == MHX_PROP_ISO, "one scale for all dimensions (the registers keep the normal, not the candidate)");
+    static_assert(MHX_ZIG_KS(NBL) == 1 && NBL <= 16, "one step per fix-up group, 16-bit fields of failure bits");
+    extern __shared__ double mhx_coop_lds[];
+    typedef double mhx_d2 __attribute__((ext_vector_type(2)));
+    const double* zt = mhx_coop_lds;
+    constexpr int SLABD = NBL * 4 * 64;                            // doubles of one step's normals
+    const int pair = (int)(threadIdx.x >> 6) & 3;
+    const bool gen = __builtin_amdgcn_readfirstlane((int)threadIdx.x) < 256;   // wave-uniform: waves 0-3 generate, waves 4-7 consume
+    double* zn0 = mhx_coop_lds + MHX_ZIG_TABLE_BYTES / 8 + pair * (MHX_ZIG_WAVE_BYTES(NBL) / 8);
+    unsigned short* zq = (unsigned short*)(zn0 + SLABD);
+    mhx_u64* zfm = (mhx_u64*)(zn0 + SLABD + 16);
+    for (int e = threadIdx.x; e <= MHX_ZIG_N; e += blockDim.x) mhx_coop_lds[e] = mhx_zig_x[e];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * 4 + pair;                 // the wave of the one-wave body whose chains this pair serves
+    const int cw = lane & (CPW - 1);
+    const int l = lane / CPW;
+    const long c_raw = wave * CPW + cw;
+    const bool valid = c_raw < a.nchains;
+    const long c = valid ? c_raw : (long)a.nchains - 1;      // idle lanes shadow the last chain (loads only)
+    const mhx_philox_key ks = mhx_philox_schedule(a.seed);    // (the chain's id: formed by each role where it draws)
+    const long ld = a.ld;
+    const int d = a.dim;
+    const mhx_u32 lane_off = ((mhx_u32)(4 * l) * (mhx_u32)ld + (mhx_u32)c) * MHX_RB;     // bytes
+    const int k_last = 4 * (l + L * (NBL - 1));               // first dimension of the last block
+
+    if (gen) {
+        // ---- a generator wave: the normals of step `it` into the pair's slab, then the two barriers of the hand-over
+        // (its own copies of the lane's coordinates, from an opaque lane number: shared with the consumer's they would stay live across
+        // the consumer's loop, where every register is taken)
+        int gl = (int)(threadIdx.x & 63);
+        asm volatile("" : "+v"(gl));
+        const int lane = gl;
+        const int l = lane / CPW;
+        const long gc_raw = wave * CPW + (lane & (CPW - 1));
+        const mhx_u64 id = a.first_chain + (mhx_u64)(gc_raw < a.nchains ? gc_raw : (long)a.nchains - 1);
+        const mhx_u32 id_lo = (mhx_u32)id, id_hi = (mhx_u32)(id >> 32);
+        const int k_last = 4 * (l + L * (NBL - 1));
+#pragma unroll 1
+        for (int it = 0; it < a.nsteps; ++it) {
+            const mhx_u32 step = a.step0 + (mhx_u32)it;
+            // phase A of the body above, one step: every slot's candidate by the fast path into the pair's slab, the failures noted
+            mhx_u64 fm = 0ull;
+            constexpr bool ZADDC = (MHX_ZADDC == 2 || (MHX_ZADDC == 1 && NBL > 4)) && NBL <= 16;
+            mhx_u32 m4[4] = {0u, 0u, 0u, 0u};
+            mhx_u32 khi[4], klo[4];                                 // the candidates' raw words (hi:lo) of the block in flight
+            auto draw = [&](const int i, mhx_u32 (&hi)[4], mhx_u32 (&lo)[4]) {
+                const mhx_u32 b = (mhx_u32)(l + L * i);
+                const mhx_u32x4 w0 = mhx_philox(ks, id_lo, id_hi, step, (MHX_STREAM_PROPOSAL << 28) | (2u * b));
+                const mhx_u32x4 w1 = mhx_philox(ks, id_lo, id_hi, step, (MHX_STREAM_PROPOSAL << 28) | (2u * b + 1u));
+                hi[0] = w0.x; lo[0] = w0.y; hi[1] = w0.z; lo[1] = w0.w;
+                hi[2] = w1.x; lo[2] = w1.y; hi[3] = w1.z; lo[3] = w1.w;
+            };
+            draw(0, khi, klo);
+            mhx_u32 zsign = 0x80000000u;                            // (opaque: see mhx_zig_signed)
+            asm volatile("" : "+s"(zsign));
+#pragma unroll
+            for (int i = 0; i < NBL; ++i) {
+                mhx_d2 xe[4];                                       // x[layer], x[layer + 1] of the block's candidates
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const mhx_u32 ly = klo[e] & (mhx_u32)(MHX_ZIG_N - 1);
+                    xe[e].x = zt[ly]; xe[e].y = zt[ly + 1];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                mhx_u32 nhi[4], nlo[4];
+                if (i + 1 < NBL) draw(i + 1, nhi, nlo);
+                __builtin_amdgcn_sched_barrier(0);
+                double nn[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double ax = mhx_zig_ax(khi[j], klo[j], xe[j].x);
+                    nn[j] = mhx_zig_signed(ax, klo[j], zsign);
+                    if (ZADDC) { MHX_ZIG_NOTE64(m4[j], ax, xe[j].y, 4 * i + j); continue; }
+                    bool fail = !(ax < xe[j].y);
+#ifdef MHX_TOOLS_BUILD
+#ifdef MHX_ZIG_FORCE_FAIL
+                    fail = fail || ((4 * i + j + lane) % (MHX_ZIG_FORCE_FAIL) == 0);
+#endif
+#endif
+                    if (i == NBL - 1) fail = fail && (k_last + j < d);   // padding dimensions past the end of the vector need no normal
+                    fm |= (fail ? 1ull : 0ull) << (4 * i + j);
+                }
+                // the second barrier of the PREVIOUS step stands here, ahead of this step's first write to the slab: the first block's
+                // Philox rounds, look-ups and fast path run while the consumer is still taking the previous step's normals
+                if (i == 0 && it > 0) __syncthreads();      // the consumer has taken them: the slab is the generator's again
+                mhx_d2 v2;
+                v2.x = nn[0]; v2.y = nn[1];
+                *(mhx_d2*)(zn0 + (((i * 2) * 64 + lane) << 1)) = v2;
+                v2.x = nn[2]; v2.y = nn[3];
+                *(mhx_d2*)(zn0 + (((i * 2 + 1) * 64 + lane) << 1)) = v2;
+                if (i + 1 < NBL) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { khi[e] = nhi[e]; klo[e] = nlo[e]; }
+                }
+            }
+            if (ZADDC) {
+                fm = (mhx_u64)(m4[0] | (m4[1] << 16)) | ((mhx_u64)(m4[2] | (m4[3] << 16)) << 32);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k_last + j >= d) fm &= ~(1ull << (16 * j));      // padding dimensions past the end of the vector need no normal
+            }
+#ifdef MHX_TOOLS_BUILD
+#ifndef MHX_ZIG_PROBE
+#define MHX_ZIG_PROBE 0
+#endif
+            if (MHX_ZIG_PROBE != 1 && __ballot(fm != 0ull))
+#else
+            if (__ballot(fm != 0ull))
+#endif
+                mhx_zig_fixup<L>(ks, zt, zn0, zq, zfm, 1, SLABD, lane, wave, a.first_chain, a.nchains, step, MHX_STREAM_PROPOSAL,
+                                 true, fm, ZADDC ? NBL - 1 : -1);
+            __syncthreads();                     // the slab holds the step's normals, final
+        }
+        if (a.nsteps > 0) __syncthreads();       // the second barrier of the last step
+        return;                                  // (after the loop: every barrier of the block has been executed)
+    }
+    // ---- the consumer's state
+    mhx_real x[NBL][4], y[NBL][4];
+#pragma unroll
+    for (int i = 0; i < NBL; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            x[i][j] = MHX_R(0.0);
+            y[i][j] = MHX_R(0.0);
+        }
+    mhx_real lp = MHX_R(0.0);
+    mhx_u32 nacc = 0u;
+    mhx_u32 wave_acc = 0;
+    bool last = false;
+    {
+#pragma unroll
+        for (int i = 0; i < NBL; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const mhx_real* col = a.x + (long)(4 * L * i + j) * ld;
+                if (i < NBL - 1) x[i][j] = mhx_ld_off(col, lane_off);
+                else x[i][j] = (k_last + j < d) ? mhx_ld_off(col, lane_off) : MHX_R(0.0);
+            }
+        lp = a.lp[c];
+        nacc = a.acc_count[c];
+        last = a.last_acc[c] != 0;
+    }
+    // From here on the chain is known through ONE opaque 32-bit register: whatever hipcc can derive from the chain id ahead of the loop
+    // -- the first Philox round of the accept stream, the 64-bit addresses of the per-chain stores -- it hoists and keeps, a dozen
+    // registers this wave does not have (the narrative of round 3 describes the same trick for the generator of the one-wave body)
+    mhx_u32 cu = (mhx_u32)c;
+    asm volatile("" : "+v"(cu));
+    mhx_accept_cache ac;
+    ac.group = 0xffffffffu;
+    ac.w.x = ac.w.y = ac.w.z = ac.w.w = 0u;
+    mhx_u32 save_next = a.save_next;
+    long slot = a.save_slot;
+
+#pragma unroll 1
+    for (int it = 0; it < a.nsteps; ++it) {
+        const mhx_u32 step = a.step0 + (mhx_u32)it;
+        // log u depends on (chain, step) only: formed while the generator is still at work and before the normals occupy their registers
+        mhx_u32 cl = cu;
+        asm volatile("" : "+v"(cl));
+        const mhx_u64 idc = a.first_chain + (mhx_u64)cl;
+        const mhx_real logu = mhx_accept_logu(ks, (mhx_u32)idc, (mhx_u32)(idc >> 32), step, ac);
+        __syncthreads();                         // the slab holds the step's normals, final
+        {
+#pragma unroll
+            for (int i = 0; i < NBL; ++i) {
+                const mhx_d2 v0 = *(const mhx_d2*)(zn0 + (((i * 2) * 64 + lane) << 1));
+                const mhx_d2 v1 = *(const mhx_d2*)(zn0 + (((i * 2 + 1) * 64 + lane) << 1));
+                y[i][0] = v0.x; y[i][1] = v0.y; y[i][2] = v1.x; y[i][3] = v1.y;
+            }
+        }
+        __syncthreads();                         // taken: the generator writes the next step's normals beside what follows
+        {
+            // the state-dependent part of the body above, the same expressions in the same order
+            mhx_real q = MHX_R(0.0), y00 = MHX_R(0.0);
+#pragma unroll
+            for (int i = 0; i < NBL; ++i) {
+                // (no instruction: block i's candidates wait for the sum over block i - 1.  Left alone hipcc forms the candidates of
+                // the later blocks first and keeps them -- two more registers each, and the wave has 256, not 512)
+                asm volatile("" : "+v"(q), "+v"(y[i][0]), "+v"(y[i][1]), "+v"(y[i][2]), "+v"(y[i][3]));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    mhx_real yk = mhx_fma(a.pscale, y[i][j], x[i][j]);
+                    if (i == NBL - 1) yk = (k_last + j < d) ? yk : MHX_R(0.0);
+                    // (the registers keep the NORMAL: the accepted state is re-formed as fma(s_acc, n, x); a padding dimension keeps n = 0)
+                    if (i == NBL - 1 && !(k_last + j < d)) y[i][j] = MHX_R(0.0);
+                    if (i == 0 && j == 0) y00 = yk;
+                    const mhx_real sq = mhx_fma(yk, yk, q);
+                    if (TK == MHX_TARGET_BANANA && i == 0 && j == 0) {
+                        q = l == 0 ? (yk * yk) * MHX_R(0.01) : sq;           // x1 ~ N(0, 100)
+                    } else if (TK == MHX_TARGET_BANANA && i == 0 && j == 1) {
+                        const mhx_real y0 = y00;
+                        const mhx_real u = mhx_fma(tparams[0], mhx_fma(y0, y0, -MHX_R(100.0)), yk);
+                        q = l == 0 ? mhx_fma(u, u, q) : sq;
+                    } else if (TK == MHX_TARGET_FUNNEL && i == 0 && j == 0) {
+                        q = l == 0 ? q : sq;                           // x1 is the funnel's scale, not a summand
+                    } else {
+                        q = sq;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            q = mhx_butterfly<L>(q);
+            mhx_real lpy;
+            if (TK == MHX_TARGET_FUNNEL) {
+                const mhx_real v = __shfl(y00, cw, 64);               // x1 lives in lane l == 0 of the chain
+                const mhx_real ev = mhx_exp(-v);
+                mhx_real r = (v * v) * MHX_ONE_18;
+                r = mhx_fma(MHX_R(0.5) * (mhx_real)(d - 1), v, r);
+                r = mhx_fma(MHX_R(0.5) * ev, q, r);
+                lpy = a.tconst - r;
+            } else {
+                lpy = mhx_fma(-MHX_R(0.5), q, a.tconst);
+            }
+            const mhx_real loga = lpy - lp;
+            const bool acc = logu < loga;
+            const mhx_real s_acc = acc ? a.pscale : MHX_R(0.0);
+#pragma unroll
+            for (int i = 0; i < NBL; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[i][j] = mhx_fma(s_acc, y[i][j], x[i][j]);
+            lp = acc ? lpy : lp;
+            nacc += acc ? 1u : 0u;
+            last = acc;
+            wave_acc += (mhx_u32)__popcll(__ballot(acc && valid && l == 0));
+            if (step == save_next) {
+                if (valid) {
+                    mhx_real* slotp = a.samples + slot * (long)(d + 1) * ld;
+                    const mhx_srd srd = mhx_make_srd(slotp, (mhx_u32)(d + 1) * (mhx_u32)ld * MHX_RB);
+                    const mhx_u32 ldb = (mhx_u32)ld * MHX_RB;
+                    mhx_u32 roff = 0u;                             // (a running scalar sum behind an opaque asm: see the body above)
+                    asm volatile("" : "+s"(roff));
+#pragma unroll
+                    for (int i = 0; i < NBL; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const mhx_u32 rowb = roff;                                                 // wave-uniform -> soffset
+                            roff += (j < 3 ? 1u : (mhx_u32)(4 * L - 3)) * ldb;
+                            if (i < NBL - 1) mhx_srd_store<MHX_REC_STORE_AUX>(srd, lane_off, rowb, x[i][j]);
+                            else if (k_last + j < d) mhx_srd_store<MHX_REC_STORE_AUX>(srd, lane_off, rowb, x[i][j]);
+                        }
+                    if (l == 0) {
+                        slotp[(long)d * ld + (long)cl] = lp;
+                        a.accepted[slot * ld + (long)cl] = acc ? 1 : 0;
+                    }
+                }
+                save_next += (mhx_u32)a.thinning;
+                ++slot;
+            }
+        }
+    }
+    if (valid) {
+#pragma unroll
+        for (int i = 0; i < NBL; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mhx_real* col = a.x + (long)(4 * L * i + j) * ld;
+                if (i < NBL - 1) mhx_st_off(col, lane_off, x[i][j]);
+                else if (k_last + j < d) mhx_st_off(col, lane_off, x[i][j]);
+            }
+        if (l == 0) {
+            a.lp[cu] = lp;
+            a.acc_count[cu] = nacc;
+            a.last_acc[cu] = last ? 1 : 0;
+        }
+    }
+    if (lane == 0) atomicAdd(a.acc_total, (mhx_u64)wave_acc);
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // initial state (src/mh-core.jl:83-84): x0 = initial_params, or a bare proposal draw
 // (src/proposal.jl:41-47) from Philox stream INIT; lp0 = logdensity(model, x0).
@@ -1673,15 +1970,23 @@ mhx_jit_rwmh_reg(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, co
 #ifndef MHX_JIT_WAVES
 #define MHX_JIT_WAVES MHX_COOP_WAVES(MHX_JIT_NBL)
 #endif
-extern "C" __global__ void __launch_bounds__(256, MHX_JIT_WAVES)
-mhx_jit_rwmh_coop(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ pvec)
-{
 #ifndef MHX_JIT_WALK
 #define MHX_JIT_WALK 0
 #endif
 #ifndef MHX_JIT_GEN
 #define MHX_JIT_GEN MHX_GEN_BOX_MULLER
 #endif
+#if defined(MHX_JIT_PAIRS) && MHX_JIT_PAIRS && MHX_REAL64
+// the generator / consumer pairs form of the same shape (512 threads; the host launches it where it compiled it)
+extern "C" __global__ void __launch_bounds__(512)
+mhx_jit_rwmh_coop_pairs(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ pvec)
+{
+    mhx_rwmh_coop_pairs_body<MHX_JIT_L, MHX_JIT_NBL, MHX_JIT_TK, MHX_JIT_PK>(a, tparams, pvec);
+}
+#endif
+extern "C" __global__ void __launch_bounds__(256, MHX_JIT_WAVES)
+mhx_jit_rwmh_coop(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ pvec)
+{
     mhx_rwmh_coop_body<MHX_JIT_L, MHX_JIT_NBL, MHX_JIT_TK, MHX_JIT_PK, (MHX_JIT_MOM != 0), MHX_JIT_WALK, MHX_JIT_GEN>(a, tparams, pvec);
 }
 #endif

@@ -117,7 +117,7 @@ EXPORTS = [
     "mhx_target_from_hip_source", "mhx_target_destroy", "mhx_target_eval", "mhx_rwmh_create",
     "mhx_emcee_create", "mhx_ram_create", "mhx_mala_create", "mhx_ram_set_factor", "mhx_ram_get_factor",
     "mhx_ram_get_diag_range", "mhx_run_init", "mhx_run_sample", "mhx_run_get_samples",
-    "mhx_run_get_state", "mhx_run_set_state", "mhx_run_stats", "mhx_run_device_samples",
+    "mhx_run_get_state", "mhx_run_set_state", "mhx_run_stats", "mhx_run_form_name", "mhx_run_device_samples",
     "mhx_run_destroy", "mhx_run_diagnostics", "mhx_run_ess_bulk_tail", "mhx_emcee_half_step", "mhx_emcee_end_sweep",
     "mhx_emcee_device_state", "mhx_run_state_size", "mhx_run_save_state", "mhx_run_load_state",
     "mhx_ctx_dtype", "mhx_ctx_device", "mhx_ram_set_factor_all", "mhx_ram_get_adapt_state", "mhx_emcee_exchange_plan", "mhx_emcee_exchange_pack",
@@ -220,6 +220,8 @@ def lib():
         L.mhx_run_get_state.argtypes = [vp, rp, rp, u32p]
         L.mhx_run_set_state.argtypes = [vp, rp]
         L.mhx_run_stats.argtypes = [vp, C.POINTER(Stats)]
+        L.mhx_run_form_name.argtypes = [vp]
+        L.mhx_run_form_name.restype = C.c_char_p
         L.mhx_run_device_samples.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
         L.mhx_run_destroy.argtypes = [vp]
         L.mhx_run_diagnostics.argtypes = [vp, C.POINTER(DiagCfg), dp, dp, dp, dp]

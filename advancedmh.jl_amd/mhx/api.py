@@ -1153,6 +1153,10 @@ class Run:
                     dtype="f64" if st.dtype == L.MHX_F64 else "f32", normal_gen=st.normal_gen, factor_band=st.factor_band,
                     tainted=st.tainted, register_form=st.register_form)
 
+    def form_name(self):
+        """The name of the run's kernel form (include/mhx.h, mhx_run_form_name): "coop", "coop_pairs", "coop_jit", ..."""
+        return L.lib().mhx_run_form_name(self.h).decode()
+
     def diagnostics(self, max_lag=0, ess_chains=256, split=False):
         """Sums for R-hat / between-chain ESS (all chains) and, if max_lag > 0, the Geyer ESS from the multi-chain
         autocorrelations.  split=True: every chain counts as two half-chains (split R-hat).  See include/mhx.h

@@ -71,7 +71,8 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  * Every option below yields the SAME chain law and, for a given reduction shape, the same bits (each form is held to the oracle
  * in tests/): they exist so that every form can be reached at every size, and for A/B measurements.
  *   kernel form     NO_PREBUILT NO_MFMA EMCEE_MFMA EMCEE_SCALAR EMCEE_FUSED EMCEE_PERSIST EMCEE_DEFER EMCEE_SWEEP_DEFER
- *                   EMCEE_PRELOAD RAM_G
+ *                   EMCEE_PRELOAD RAM_G COOP_PAIRS (fp64 ziggurat cooperative kernel at one wave per SIMD: 1 = generator / consumer
+ *                   wave pairs, 0 = the one-wave body, unset = the library's choice; mhx_run_form_name tells which)
  *   tuning          COOP_WAVES MFMA_WAVES REG_MAX_DIM REG_XR REG_UNROLL REG_WAVES REG_ZSLAB MALA_XR EMCEE_WAVES EMCEE_MFMA_WAVES
  *                   EMCEE_SCAL_WPB EMCEE_SCAL_MODE EMCEE_SCAL_REC EMCEE_REC_STORE EMCEE_ROW_STORE EMCEE_COOP_REC RAM_LDS_PAD
  *                   WAVE_K (4 | 8 speculative candidates per round of the wave-per-chain kernel; default: by the last call's acceptance)
@@ -527,6 +528,10 @@ typedef struct {
                                   the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
+/* The name of the run's kernel form -- kernel_variant spelled out ("generic", "reg", "coop", "coop_jit", "wave", ...) -- with the body
+   it was compiled as where a form has two: "coop_pairs" / "coop_jit_pairs" is the cooperative kernel as generator / consumer wave
+   pairs (option COOP_PAIRS; same chains, kernel_variant stays 3 / 4).  A static string; "" for a NULL run. */
+const char *mhx_run_form_name(const mhx_run *run);
 /* dimension and number of chains (walkers) of a run; either pointer may be NULL */
 int mhx_run_shape(const mhx_run *run, int32_t *dim, int32_t *nchains);
 
