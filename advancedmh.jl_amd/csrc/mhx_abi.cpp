@@ -374,6 +374,20 @@ extern "C" int mhx_run_select_histogram(mhx_run* r, const int32_t* params, int32
     return is64(r) ? mhx_f64::api_run_select_histogram(R64(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist)
                    : mhx_f32::api_run_select_histogram(R32(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist);
 }
+extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                                     const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
+{
+    NEED(ctx, "mhx_ctx_cross_moments");
+    return is64(ctx) ? mhx_f64::api_ctx_cross_moments(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, shift, sum, cross)
+                     : mhx_f32::api_ctx_cross_moments(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, shift, sum, cross);
+}
+extern "C" int mhx_run_cross_moments(mhx_run* r, const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross,
+                                     int64_t* n_draws)
+{
+    NEED(r, "mhx_run_cross_moments");
+    return is64(r) ? mhx_f64::api_run_cross_moments(R64(r), params, nparams, shift, sum, cross, n_draws)
+                   : mhx_f32::api_run_cross_moments(R32(r), params, nparams, shift, sum, cross, n_draws);
+}
 extern "C" int mhx_emcee_half_step(mhx_run* r, int half, int begin, int count)
 {
     NEED(r, "mhx_emcee_half_step");

@@ -35,6 +35,7 @@
 #include "mhx_rwmh_mfma_kernels.h"
 #include "mhx_mala_mfma_kernels.h"
 #include "mhx_diag_kernels.h"
+#include "mhx_cross_kernels.h"
 #ifdef MHX_TOOLS_BUILD
 #include "mhx_jit_embed_tools.inc"   // generated: the device headers as string literals for hiprtc, probes included
 #else
@@ -246,8 +247,11 @@ struct mhx_ctx : mhx_handle_hdr {
     size_t select_bytes = 0;
     uint64_t* select_landing = nullptr;             // ... and their page-locked landing place on the host (grown on demand)
     size_t select_landing_words = 0;
+    void* cross_scratch = nullptr;                  // partial tiles, tables and results of the cross moments (grown on demand)
+    size_t cross_bytes = 0;
     ~mhx_ctx()
     {
+        if (cross_scratch) (void)hipFree(cross_scratch);
         if (select_scratch) (void)hipFree(select_scratch);
         if (select_landing) (void)hipHostFree(select_landing);
         if (expander) mhx_expander_destroy(expander);
@@ -2093,5 +2097,6 @@ int api_run_destroy(mhx_run* r)
 #include "mhx_api_ram.inc"
 #include "mhx_api_mala.inc"
 #include "mhx_api_diag.inc"
+#include "mhx_api_moments.inc"
 
 }  // namespace MHX_NS

@@ -395,3 +395,37 @@ extern "C" int mhx_group_order_statistics(mhx_group* g, const int32_t* params, i
     return mhx_select_drive(who, g->dtype == MHX_F64 ? 64 : 32, digit, nparams, ranks, nranks, (uint64_t)n_saved * (uint64_t)chains,
                             group_select_pass, &s, out, nullptr, 0);
 }
+
+// The cross moments of the UNION of all members' draws: every member computes the moments of its own shard about the SAME shift
+// (concurrently, each on its own thread and device); sums about a common shift add, here in member order.
+extern "C" int mhx_group_cross_moments(mhx_group* g, const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross,
+                                       int64_t* n_draws)
+{
+    const char* who = "mhx_group_cross_moments";
+    int rc = need_runs(g, who);
+    if (rc) return rc;
+    if (!params || nparams <= 0 || !sum || !cross) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    const int d1 = g->mem[0]->dim + 1;
+    for (int32_t i = 0; i < nparams; ++i)
+        if (params[i] < 0 || params[i] >= d1) return mhx_fail(MHX_EINVAL, "%s: parameter %d out of range [0, %d)", who, (int)params[i], d1);
+    if (shift)
+        for (int32_t i = 0; i < nparams; ++i)
+            if (!std::isfinite(shift[i])) return mhx_fail(MHX_EINVAL, "%s: shift %d is not finite", who, (int)i);
+    const size_t n = g->mem.size(), m = (size_t)nparams, stride = m * m + m;
+    std::vector<double> buf(n * stride, 0.0);
+    std::vector<int64_t> nd(n, 0);
+    rc = for_all(g, who, [g, params, nparams, shift, m, stride, &buf, &nd](int i) {
+        double* b = buf.data() + (size_t)i * stride;
+        return mhx_run_cross_moments(g->mem[i]->run, params, nparams, shift, b + m * m, b, &nd[(size_t)i]);
+    });
+    if (rc) return rc;
+    int64_t total = 0;
+    for (size_t k = 0; k < stride; ++k) {
+        double a = 0.0;
+        for (size_t i = 0; i < n; ++i) a += buf[i * stride + k];
+        (k < m * m ? cross[k] : sum[k - m * m]) = a;
+    }
+    for (size_t i = 0; i < n; ++i) total += nd[i];
+    if (n_draws) *n_draws = total;
+    return MHX_OK;
+}

@@ -129,7 +129,7 @@ EXPORTS = [
     "mhx_group_init", "mhx_group_sample", "mhx_group_sample_to_host", "mhx_group_stats", "mhx_group_diagnostics", "mhx_group_ess_bulk_tail",
     "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components", "mhx_rwmh_create_conditional",
     "mhx_rwmh_create_composite", "mhx_run_order_statistics", "mhx_ctx_order_statistics", "mhx_group_order_statistics",
-    "mhx_run_select_histogram",
+    "mhx_run_select_histogram", "mhx_run_cross_moments", "mhx_ctx_cross_moments", "mhx_group_cross_moments",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -267,6 +267,9 @@ def lib():
         L.mhx_ctx_order_statistics.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, i64p, C.c_int32, dp]
         L.mhx_group_order_statistics.argtypes = [vp, i32p, C.c_int32, i64p, C.c_int32, dp]
         L.mhx_run_select_histogram.argtypes = [vp, i32p, C.c_int32, u64p, i32p, C.c_int32, C.c_int32, C.c_int32, u64p]
+        L.mhx_run_cross_moments.argtypes = [vp, i32p, C.c_int32, dp, dp, dp, i64p]
+        L.mhx_ctx_cross_moments.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, dp, dp, dp]
+        L.mhx_group_cross_moments.argtypes = [vp, i32p, C.c_int32, dp, dp, dp, i64p]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -774,6 +774,72 @@ def _quantiles(order_statistics, S, probs, params):
     return quantiles_from_order_statistics(x[:, :n], x[:, n:2 * n], g, top=x[:, 2 * n])
 
 
+def covariance_from_moments(n, sum, cross):
+    """The covariance matrix of n pooled draws from their moments about ANY common shift (Run.cross_moments): sum[i] = sum_k y_ik,
+    cross[i][j] = sum_k y_ik y_jk  ->  (cross - sum sum^T / n) / (n - 1), in float64 on the host; what `np.cov` of the flattened
+    chains gives.  Moments of shards taken about the same shift add before this call."""
+    n = int(n)
+    if n < 2:
+        raise L.ArgumentError(L.MHX_EINVAL, "covariance_from_moments: a covariance needs n >= 2 draws, got %d" % n)
+    s, x = np.asarray(sum, dtype=np.float64), np.asarray(cross, dtype=np.float64)
+    if s.ndim != 1 or x.shape != (s.size, s.size):
+        raise L.ArgumentError(L.MHX_EINVAL, "covariance_from_moments: sum must be [m] and cross [m][m]")
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (x - np.outer(s, s) / float(n)) / float(n - 1)
+
+
+def correlation_from_covariance(cov):
+    """cov[i][j] / (sd_i sd_j) with the diagonal set to exactly 1 and the rest clamped to [-1, 1], as Julia's `cor` (cov2cor!) does;
+    a row whose variance is not a positive finite number is NaN."""
+    cov = np.asarray(cov, dtype=np.float64)
+    var = np.diagonal(cov)
+    ok = np.isfinite(var) & (var > 0.0)
+    sd = np.sqrt(np.where(ok, var, np.nan))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        cor = np.clip(cov / np.outer(sd, sd), -1.0, 1.0)        # (one division by a symmetric product: symmetric bit for bit)
+    cor[np.diag_indices_from(cor)] = np.where(ok, 1.0, np.nan)
+    return cor
+
+
+def _check_moments(rc):
+    """check() for the cross moments: asking a run that kept no sample tensor for them is an ArgumentError here (the C ABI says
+    MHX_ESTATE, as for the order statistics)"""
+    if rc == L.MHX_ESTATE:
+        raise L.ArgumentError(rc, L.lib().mhx_last_error().decode("utf-8", "replace"))
+    L.check(rc)
+
+
+def _first_sample_mean(sums, nchains):
+    """the default shift of the cross moments: the mean over the chains of saved sample 0 of each row, 0 where that is not finite"""
+    with np.errstate(invalid="ignore", over="ignore"):
+        mean = np.asarray(sums, dtype=np.float64) / float(nchains)
+    return np.where(np.isfinite(mean), mean, 0.0)
+
+
+class CorrelationMatrix(np.ndarray):
+    """what Chains.cor returns: the [d][d] float64 matrix (an ndarray in every respect) that prints with the parameter names"""
+
+    def __new__(cls, cor, names):
+        obj = np.asarray(cor, dtype=np.float64).view(cls)
+        obj.names = list(names)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.names = getattr(obj, "names", None)
+
+    def __str__(self):
+        names = self.names
+        if names is None or self.ndim != 2 or self.shape != (len(names), len(names)):
+            return np.ndarray.__str__(self)
+        w = max([12] + [len(n) for n in names])
+        lines = ["Correlation", "  %-*s " % (w, "parameters") + " ".join("%*s" % (max(9, len(n)), n) for n in names)]
+        for i, n in enumerate(names):
+            lines.append("  %-*s " % (w, n) + " ".join("%*.4f" % (max(9, len(c)), self[i, j]) for j, c in enumerate(names)))
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
 class Chains:
     """value[iteration, parameter, chain]; the last parameter is the internal `lp`
     (ext/AdvancedMHMCMCChainsExt.jl:36, :96-118)."""
@@ -834,6 +900,21 @@ class Chains:
         idx = [i for i, n in enumerate(self.names) if n not in self.internals]
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
         return dict(parameters=[self.names[i] for i in idx], probs=probs, quantiles=self.state.quantiles(probs, params=idx))
+
+    def _moment_rows(self, include_lp, what):
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s needs the live run (chain.state)" % what)
+        return [i for i, n in enumerate(self.names) if include_lp or n not in self.internals]
+
+    def cov(self, include_lp=False):
+        """[d][d] float64 covariance matrix of the parameters over all draws of all chains (np.cov of the flattened chains), from
+        cross moments taken on the device (mhx_run_cross_moments); internals (lp) are left out unless include_lp."""
+        return self.state.cov(params=self._moment_rows(include_lp, "cov"))
+
+    def cor(self, include_lp=False):
+        """the correlation matrix of the same rows (MCMCChains' `cor(chain)`); prints with the parameter names"""
+        idx = self._moment_rows(include_lp, "cor")
+        return CorrelationMatrix(self.state.cor(params=idx), [self.names[i] for i in idx])
 
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
@@ -1230,6 +1311,51 @@ class Run:
         if n_saved.value < 1:
             return self.order_statistics([0], params)       # raises the library's refusal (no device sample tensor)
         return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
+
+    def _rows(self, params):
+        return np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+
+    def first_sample_sums(self, idx):
+        """per-row sums over the chains of saved sample 0 (mhx_ctx_cross_moments on that one sample), or None without a tensor"""
+        ptr, n_saved = C.c_void_p(), C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.h, C.byref(ptr), None, C.byref(n_saved)))
+        if n_saved.value < 1 or not ptr.value:
+            return None
+        dp = C.POINTER(C.c_double)
+        s, x = np.empty(len(idx)), np.empty((len(idx), len(idx)))
+        L.check(L.lib().mhx_ctx_cross_moments(self.ctx.h, ptr, 1, self.dim + 1, self.n, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
+                                              None, s.ctypes.data_as(dp), x.ctypes.data_as(dp)))
+        return s
+
+    def cross_moments(self, params=None, shift=None):
+        """(n, shift, sum [m], cross [m][m]) of the given parameter rows (default: all, lp included) of the last sample buffer, taken
+        on the device's fp64 matrix cores from the tensor in place (mhx_run_cross_moments): with y = x - shift,
+        sum[i] = sum_k y_ik and cross[i][j] = sum_k y_ik y_jk over all n = n_saved x nchains draws, float64 in both widths.
+        shift None: the mean over the chains of saved sample 0 of each row (0 where that is not finite) -- near enough to the mean
+        to take the cancellation out of covariance_from_moments without a second pass over the tensor."""
+        idx = self._rows(params)
+        m = len(idx)
+        if shift is None:
+            s0 = self.first_sample_sums(idx) if m and np.all((idx >= 0) & (idx <= self.dim)) else None
+            sh = None if s0 is None else _first_sample_mean(s0, self.n)      # None: the call below raises the library's refusal
+        else:
+            sh = np.ascontiguousarray(shift, dtype=np.float64).reshape(-1)
+            if sh.size != m:
+                raise L.ArgumentError(L.MHX_EINVAL, "cross_moments: %d shifts for %d rows" % (sh.size, m))
+        dp = C.POINTER(C.c_double)
+        s, x, n = np.empty(m), np.empty((m, m)), C.c_int64()
+        _check_moments(L.lib().mhx_run_cross_moments(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), m, None if sh is None else sh.ctypes.data_as(dp),
+                                                     s.ctypes.data_as(dp), x.ctypes.data_as(dp), C.byref(n)))
+        return int(n.value), (np.zeros(m) if sh is None else sh), s, x
+
+    def cov(self, params=None):
+        """[m][m] float64 covariance matrix of the rows over all draws of all chains (np.cov of the flattened chains)"""
+        n, _, s, x = self.cross_moments(params)
+        return covariance_from_moments(n, s, x)
+
+    def cor(self, params=None):
+        """the correlation matrix of the same rows"""
+        return correlation_from_covariance(self.cov(params))
 
     def close(self):
         if self.h:

@@ -184,6 +184,40 @@ class Group:
             return self.order_statistics([0], params)       # raises the library's refusal
         return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
 
+    def cross_moments(self, params=None, shift=None):
+        """Run.cross_moments over the UNION of all members' draws (mhx_group_cross_moments): every member takes the moments of its
+        shard about the same shift, and the group adds them in member order.  shift None: the mean of saved sample 0 over the chains
+        of all members."""
+        from . import _lib as L
+        from .api import _check_moments, _first_sample_mean
+        idx = np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+        m = len(idx)
+        if shift is None:
+            sh = None
+            if m and np.all((idx >= 0) & (idx <= self.dim)):
+                parts = [r.first_sample_sums(idx) for r in self.runs]
+                if all(p is not None for p in parts):
+                    sh = _first_sample_mean(np.sum(parts, axis=0), self.n)
+        else:
+            sh = np.ascontiguousarray(shift, dtype=np.float64).reshape(-1)
+            if sh.size != m:
+                raise L.ArgumentError(L.MHX_EINVAL, "cross_moments: %d shifts for %d rows" % (sh.size, m))
+        dp = C.POINTER(C.c_double)
+        s, x, n = np.empty(m), np.empty((m, m)), C.c_int64()
+        _check_moments(L.lib().mhx_group_cross_moments(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), m, None if sh is None else sh.ctypes.data_as(dp),
+                                                       s.ctypes.data_as(dp), x.ctypes.data_as(dp), C.byref(n)))
+        return int(n.value), (np.zeros(m) if sh is None else sh), s, x
+
+    def cov(self, params=None):
+        """Run.cov over all chains of all members"""
+        from .api import covariance_from_moments
+        n, _, s, x = self.cross_moments(params)
+        return covariance_from_moments(n, s, x)
+
+    def cor(self, params=None):
+        from .api import correlation_from_covariance
+        return correlation_from_covariance(self.cov(params))
+
     def close_runs(self):
         for r in self.runs:
             r.close()

@@ -652,6 +652,24 @@ int mhx_run_order_statistics(mhx_run *run, const int32_t *params, int32_t nparam
 int mhx_ctx_order_statistics(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                              const int32_t *params, int32_t nparams, const int64_t *ranks, int32_t nranks, double *out);
 
+/* First and second cross moments of the parameters params[0..nparams) (indices into the dim+1 rows, lp = dim; a row may repeat)
+ * over all K = n_saved * nchains draws of the sample buffer, on the fp64 matrix cores, reading the [n_saved][dim+1][nchains] tensor
+ * in place.  With y[i][k] = x[params[i]][k] - shift[i] rounded once to double (shift NULL: 0; an fp32 draw
+ * is widened exactly):
+ *   sum[i]       = sum over k of y[i][k]
+ *   cross[i][j]  = sum over k of y[i][k] * y[j][k]      [nparams][nparams], exactly symmetric, both halves written
+ * in double whatever the context's dtype.  Covariance of the pooled draws: (cross - sum sum^T / K) / (K - 1) -- a shift near the
+ * mean takes the cancellation out of that formula.  No floating-point atomics: partial tiles are added in a fixed order, so two
+ * calls on the same tensor return the same bits.  A NaN or an infinity among the draws of row params[i] reaches sum[i], row i and
+ * column i of cross and nothing else.  *n_draws = K.
+ * MHX_EINVAL: a parameter outside [0, dim], a shift that is not finite; MHX_ESTATE: the run holds no device sample tensor.  Nothing
+ * is written to sum / cross unless the call succeeds. */
+int mhx_run_cross_moments(mhx_run *run, const int32_t *params, int32_t nparams, const double *shift, double *sum, double *cross,
+                          int64_t *n_draws);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics) */
+int mhx_ctx_cross_moments(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                          const int32_t *params, int32_t nparams, const double *shift, double *sum, double *cross);
+
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
  * (README.md:135-148: one task per chain) -- here one host thread per GPU behind the ABI.  A group is N member contexts (one
@@ -691,6 +709,10 @@ int mhx_group_ess_bulk_tail(mhx_group *g, const mhx_diag_cfg *cfg, const int32_t
  * pass every member histograms its own shard concurrently (mhx_run_select_histogram), the group adds the integer histograms on the
  * host and scans once: exact, and equal to the unsharded run's answer */
 int mhx_group_order_statistics(mhx_group *g, const int32_t *params, int32_t nparams, const int64_t *ranks, int32_t nranks, double *out);
+/* mhx_run_cross_moments over the UNION of all members' draws: every member takes the moments of its shard about the same shift
+ * (concurrently), and sums about a common shift add -- here on the host, in member order.  *n_draws = the draws of all members. */
+int mhx_group_cross_moments(mhx_group *g, const int32_t *params, int32_t nparams, const double *shift, double *sum, double *cross,
+                            int64_t *n_draws);
 
 #ifdef __cplusplus
 }
