@@ -374,6 +374,19 @@ extern "C" int mhx_run_select_histogram(mhx_run* r, const int32_t* params, int32
     return is64(r) ? mhx_f64::api_run_select_histogram(R64(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist)
                    : mhx_f32::api_run_select_histogram(R32(r), params, nparams, prefixes, ngroups, gstride, shift, digit_bits, hist);
 }
+extern "C" int mhx_ctx_hpd(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
+                           int32_t nparams, double alpha, double* lower, double* upper)
+{
+    NEED(ctx, "mhx_ctx_hpd");
+    return is64(ctx) ? mhx_f64::api_ctx_hpd(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, alpha, lower, upper)
+                     : mhx_f32::api_ctx_hpd(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, alpha, lower, upper);
+}
+extern "C" int mhx_run_hpd(mhx_run* r, const int32_t* params, int32_t nparams, double alpha, double* lower, double* upper)
+{
+    NEED(r, "mhx_run_hpd");
+    return is64(r) ? mhx_f64::api_run_hpd(R64(r), params, nparams, alpha, lower, upper)
+                   : mhx_f32::api_run_hpd(R32(r), params, nparams, alpha, lower, upper);
+}
 extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                      const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
 {

@@ -36,6 +36,7 @@
 #include "mhx_mala_mfma_kernels.h"
 #include "mhx_diag_kernels.h"
 #include "mhx_cross_kernels.h"
+#include "mhx_hpd_kernels.h"
 #ifdef MHX_TOOLS_BUILD
 #include "mhx_jit_embed_tools.inc"   // generated: the device headers as string literals for hiprtc, probes included
 #else
@@ -249,8 +250,11 @@ struct mhx_ctx : mhx_handle_hdr {
     size_t select_landing_words = 0;
     void* cross_scratch = nullptr;                  // partial tiles, tables and results of the cross moments (grown on demand)
     size_t cross_bytes = 0;
+    void* hpd_scratch = nullptr;                    // tail keys, their sort and the partial minima of the HPD intervals (grown on demand, bounded by HPD_SCRATCH_MB)
+    size_t hpd_bytes = 0;
     ~mhx_ctx()
     {
+        if (hpd_scratch) (void)hipFree(hpd_scratch);
         if (cross_scratch) (void)hipFree(cross_scratch);
         if (select_scratch) (void)hipFree(select_scratch);
         if (select_landing) (void)hipHostFree(select_landing);
@@ -306,10 +310,10 @@ static const opt_name k_opt_names[] = {
     {"EMCEE_MFMA", 0}, {"EMCEE_MFMA_WAVES", 0}, {"EMCEE_SCALAR", 0}, {"EMCEE_SCAL_MODE", 0}, {"EMCEE_SCAL_WPB", 0}, {"EMCEE_SCAL_REC", 0},
     {"EMCEE_FUSED", 0}, {"EMCEE_PERSIST", 0}, {"EMCEE_PRELOAD", 0}, {"EMCEE_DEFER", 0}, {"EMCEE_SWEEP_DEFER", 0}, {"EMCEE_WAVES", 0},
     {"EMCEE_REC_STORE", 0}, {"EMCEE_ROW_STORE", 0}, {"EMCEE_COOP_REC", 0},
-    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0},
+    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0}, {"HPD_SCRATCH_MB", 0},
 #ifdef MHX_TOOLS_BUILD
     {"ZIG_PROBE", 1}, {"ZIG_FORCE_FAIL", 1}, {"JIT_DEFS", 1}, {"JIT_FLAGS", 1}, {"EMCEE_PROBE", 1}, {"EMCEE_STAMPS", 1}, {"EMCEE_STAMPS_FILE", 1},
-    {"FAULT_SLAB", 1}, {"RAM_PROF", 1},
+    {"FAULT_SLAB", 1}, {"RAM_PROF", 1}, {"HPD_STOP_AFTER", 1},
 #endif
 };
 static const opt_name* opt_find(const char* name)
@@ -2098,5 +2102,6 @@ int api_run_destroy(mhx_run* r)
 #include "mhx_api_mala.inc"
 #include "mhx_api_diag.inc"
 #include "mhx_api_moments.inc"
+#include "mhx_api_hpd.inc"
 
 }  // namespace MHX_NS

@@ -91,6 +91,9 @@ void mhx_jit_unlock();
                               const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross);  \
     int api_run_cross_moments(mhx_run* r, const int32_t* params, int32_t nparams, const double* shift, double* sum,    \
                               double* cross, int64_t* n_draws);                                                        \
+    int api_ctx_hpd(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,              \
+                    const int32_t* params, int32_t nparams, double alpha, double* lower, double* upper);               \
+    int api_run_hpd(mhx_run* r, const int32_t* params, int32_t nparams, double alpha, double* lower, double* upper);   \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \
     int api_emcee_device_state(mhx_run* r, REAL** xw, int32_t* pitch, REAL** lp, uint32_t** acc_count,                 \

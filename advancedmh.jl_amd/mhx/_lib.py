@@ -130,6 +130,7 @@ EXPORTS = [
     "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components", "mhx_rwmh_create_conditional",
     "mhx_rwmh_create_composite", "mhx_run_order_statistics", "mhx_ctx_order_statistics", "mhx_group_order_statistics",
     "mhx_run_select_histogram", "mhx_run_cross_moments", "mhx_ctx_cross_moments", "mhx_group_cross_moments",
+    "mhx_run_hpd", "mhx_ctx_hpd",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -270,6 +271,8 @@ def lib():
         L.mhx_run_cross_moments.argtypes = [vp, i32p, C.c_int32, dp, dp, dp, i64p]
         L.mhx_ctx_cross_moments.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, dp, dp, dp]
         L.mhx_group_cross_moments.argtypes = [vp, i32p, C.c_int32, dp, dp, dp, i64p]
+        L.mhx_run_hpd.argtypes = [vp, i32p, C.c_int32, C.c_double, dp, dp]
+        L.mhx_ctx_hpd.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_double, dp, dp]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -774,6 +774,29 @@ def _quantiles(order_statistics, S, probs, params):
     return quantiles_from_order_statistics(x[:, :n], x[:, n:2 * n], g, top=x[:, 2 * n])
 
 
+def hpd_ranks(S, alpha):
+    """m = max(1, ceil(alpha S)), in float64 as the C side computes it (include/mhx.h: mhx_run_hpd): the HPD interval of S pooled
+    draws is the narrowest [y[i], y[S - m + i]], i < m, of their ascending order y.  alpha outside (0, 1) (or NaN) is refused."""
+    alpha = float(alpha)
+    if int(S) < 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "hpd: no draws")
+    if not (0.0 < alpha < 1.0):
+        raise L.ArgumentError(L.MHX_EINVAL, "hpd: alpha must lie in (0, 1)")
+    return max(1, int(math.ceil(alpha * float(int(S)))))
+
+
+class HPDTable(dict):
+    """what Chains.hpd returns: dict(parameters, alpha, lower [nparams], upper [nparams]) that prints in the style of the Quantiles table"""
+
+    def __str__(self):
+        lines = ["HPD (%g%%)" % (100.0 * (1.0 - self["alpha"])), "  parameters   " + " ".join("%9s" % c for c in ("lower", "upper"))]
+        for i, n in enumerate(self["parameters"]):
+            lines.append("  %-12s " % n + " ".join("%9.4f" % v for v in (self["lower"][i], self["upper"][i])))
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
 def covariance_from_moments(n, sum, cross):
     """The covariance matrix of n pooled draws from their moments about ANY common shift (Run.cross_moments): sum[i] = sum_k y_ik,
     cross[i][j] = sum_k y_ik y_jk  ->  (cross - sum sum^T / n) / (n - 1), in float64 on the host; what `np.cov` of the flattened
@@ -900,6 +923,16 @@ class Chains:
         idx = [i for i, n in enumerate(self.names) if n not in self.internals]
         probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
         return dict(parameters=[self.names[i] for i in idx], probs=probs, quantiles=self.state.quantiles(probs, params=idx))
+
+    def hpd(self, alpha=0.05):
+        """MCMCChains' `hpd(chain; alpha)`: the highest-posterior-density interval of mass 1 - alpha of every parameter over all draws of
+        all chains (the Chen-Shao interval), taken on the device from the run's sample buffer (mhx_run_hpd); internals (lp) are left
+        out as in quantile.  An HPDTable: dict(parameters, alpha, lower [nparams], upper [nparams]) that prints as a table."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "hpd needs the live run (chain.state)")
+        idx = [i for i, n in enumerate(self.names) if n not in self.internals]
+        lower, upper = self.state.hpd(alpha, params=idx)
+        return HPDTable(parameters=[self.names[i] for i in idx], alpha=float(alpha), lower=lower, upper=upper)
 
     def _moment_rows(self, include_lp, what):
         if self.state is None:
@@ -1311,6 +1344,18 @@ class Run:
         if n_saved.value < 1:
             return self.order_statistics([0], params)       # raises the library's refusal (no device sample tensor)
         return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
+
+    def hpd(self, alpha=0.05, params=None):
+        """(lower, upper), float64 [nparams] each: the highest-posterior-density interval of mass 1 - alpha of the given parameter rows
+        (default: all, lp included, as quantiles) over all draws of all chains of the last sample buffer -- the narrowest
+        [y[i], y[S - m + i]], i < m = hpd_ranks(S, alpha), of the ascending order y (the first of equally narrow ones), found on the
+        device without a full sort (mhx_run_hpd).  A row that holds a NaN gives (NaN, NaN)."""
+        idx = self._rows(params)
+        lower, upper = np.empty(len(idx), dtype=np.float64), np.empty(len(idx), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().mhx_run_hpd(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx), float(alpha),
+                                    lower.ctypes.data_as(dp), upper.ctypes.data_as(dp)))
+        return lower, upper
 
     def _rows(self, params):
         return np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)

@@ -86,8 +86,10 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   runs what the unsharded run runs; mhx_group_shard sets it on the member's context, a process of a
  *                   multi-process run sets it itself)
  *   summary         SELECT_BITS (digit width of a pass of mhx_*_order_statistics, 1..11; default 11; read at every call)
+ *                   HPD_SCRATCH_MB (bound, in MiB, on the device scratch of a call of mhx_*_hpd: the rows go in batches that fit;
+ *                   default 1024; a positive number, fractions allowed; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
- * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF): setting one
+ * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
  * such a run.  In libmhx.so those names do not exist. */
 int mhx_ctx_set_option(mhx_ctx *ctx, const char *name, const char *value);
@@ -669,6 +671,36 @@ int mhx_run_cross_moments(mhx_run *run, const int32_t *params, int32_t nparams, 
 /* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics) */
 int mhx_ctx_cross_moments(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                           const int32_t *params, int32_t nparams, const double *shift, double *sum, double *cross);
+
+/* Highest-posterior-density intervals (what MCMCChains offers as `hpd(chain; alpha = 0.05)`: the Chen-Shao interval, the shortest of
+ * the intervals that span S - m + 1 consecutive order statistics) of the parameters params[0..nparams) (indices into the dim+1 rows,
+ * lp = dim; any order, a row may repeat) over the S = n_saved * nchains draws of ALL chains pooled, as the quantiles are.  With y the
+ * ascending order of a row's draws (NaNs last) and m = max(1, (int64)ceil(alpha * (double)S)), computed in double:
+ *   a = y[0:m], b = y[S-m:S], i = the first argmin of b - a, lower = a[i], upper = b[i]      (double; an fp32 draw is widened exactly)
+ * No full sort and no copy of the draws: the radix select above finds y[m-1], y[S-m] and the NaN check y[S-1]; one more sweep of the
+ * tensor in place gathers the keys strictly outside the two thresholds (2 alpha of the draws; draws EQUAL to a threshold -- the
+ * repeats of rejected transitions -- are counted, never stored); only those tails are sorted; a reduction finds the first minimum.
+ *   width         b[i] - a[i] in fp64 of the widened values in BOTH engine widths (the reference, on a Float32 array, rounds the
+ *                 width to Float32: a deviation -- two fp32 widths that differ below a Float32 ulp of their size tie there, not here)
+ *   comparison    as numpy.argmin and Julia's findmin: a NaN width (inf - inf) is smaller than every number; among equal widths the
+ *                 lowest i wins
+ *   reproducible  integer atomics only reserve slots in buffers that are sorted before they are read, and the minimum is taken under
+ *                 a total order on (width, i): the result depends on neither the launch geometry nor the order of arrival, two calls
+ *                 return the same bits
+ *   NaN rows      a row whose top order statistic is NaN (it holds a NaN) has lower = upper = NaN; other rows are untouched (the rule
+ *                 of the quantiles)
+ *   signed zeros  -0.0 and +0.0 are equal draws: either may be returned
+ *   2m > S        (alpha > 0.5) the two tails overlap: legal, and the same definition
+ * Scratch: 4 x (m - 1) keys per row in flight plus the sort's own space, bounded by option HPD_SCRATCH_MB; rows are served in batches
+ * that fit and the context keeps the buffer from call to call.
+ * MHX_EINVAL: alpha not in (0, 1) (NaN included), a parameter outside [0, dim], a single row whose tails do not fit HPD_SCRATCH_MB
+ * (the message names the option); MHX_ESTATE: the run holds no device sample tensor; MHX_EHIP: more draws beyond a threshold than its
+ * rank allows (the tensor changed during the call) -- never a write out of bounds.  Nothing is written to lower / upper unless the call
+ * succeeds.  Blocking. */
+int mhx_run_hpd(mhx_run *run, const int32_t *params, int32_t nparams, double alpha, double *lower, double *upper);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics) */
+int mhx_ctx_hpd(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                const int32_t *params, int32_t nparams, double alpha, double *lower, double *upper);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
