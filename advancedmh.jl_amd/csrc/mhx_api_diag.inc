@@ -8,10 +8,17 @@ k_diag_moments(const mhx_real* __restrict__ samples, const long N, const int d1,
     mhx_diag_moments_body(samples, N, d1, C, mean, sums, red);
 }
 __global__ void __launch_bounds__(64)
-k_diag_autocov(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const long nc,
+k_diag_autocov(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const long nc, const long k0,
                const double* __restrict__ mean, double* __restrict__ acov)
 {
-    mhx_diag_autocov_body(samples, N, d1, C, nc, mean, acov);
+    mhx_diag_autocov_body(samples, N, d1, C, nc, k0, mean, acov);
+}
+__global__ void __launch_bounds__(256)
+k_diag_between(const double* __restrict__ mean, const double* __restrict__ sums, const int d1, const long C, const double M,
+               double* __restrict__ between)
+{
+    __shared__ double red[4];
+    mhx_diag_between_body(mean, sums, d1, C, M, between, red);
 }
 
 __global__ void __launch_bounds__(256)
@@ -25,11 +32,12 @@ k_diag_from_moments(const mhx_real* __restrict__ mom_mean, const mhx_real* __res
 // Geyer's initial positive (monotone) sequence on the multi-chain autocorrelations
 //   rho_t = 1 - (W - A_t) / var+     (A_t: chain-averaged autocovariance, W = A_0; Vehtari et al. 2021, eq. 10)
 // which is A_t / A_0 for a single chain (var+ == W)
+// A row without variance (a parameter that never moved) or with a non-finite draw has no autocorrelation: NaN, not tau = 1.
 static double geyer_tau(const double* acov, long nlag, long stride, double varp, bool* truncated)
 {
     const double g0 = acov[0];
+    if (!(g0 > 0.0) || !(varp > 0.0)) { *truncated = false; return std::nan(""); }
     *truncated = true;
-    if (!(g0 > 0.0) || !(varp > 0.0)) return 1.0;
     double tau = -1.0, prev = 1e300;
     for (long m = 0; 2 * m + 1 < nlag; ++m) {
         double pm = (1.0 - (g0 - acov[(2 * m) * stride]) / varp) + (1.0 - (g0 - acov[(2 * m + 1) * stride]) / varp);
@@ -79,20 +87,29 @@ static int diag_compute(mhx_ctx* ctx, const mhx_real* d_samples, long Nsaved, in
             nlag &= ~1L;                                    // pairs
             long nc = cfg->ess_chains <= 0 ? C : (cfg->ess_chains < C ? cfg->ess_chains : C);
             if (nlag < 2) { for (int p = 0; p < d1; ++p) ess[p] = std::nan(""); break; }
-            if (hipMalloc(&d_acov, (size_t)nlag * d1 * sizeof(double)) != hipSuccess) { rc = mhx_fail(MHX_ENOMEM, "autocov scratch"); break; }
-            (void)hipMemsetAsync(d_acov, 0, (size_t)nlag * d1 * sizeof(double), ctx->stream);
-            for (int part = 0; part < nparts; ++part)
-                hipLaunchKernelGGL(k_diag_autocov, dim3((unsigned)((nc + 63) / 64), d1, (unsigned)nlag), dim3(64), 0, ctx->stream,
-                                   d_samples + (size_t)part * N * d1 * C, N, d1, C, nc, d_mean + (size_t)part * d1 * C, d_acov);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "k_diag_autocov failed"); break; }
-            std::vector<double> ac((size_t)nlag * d1);
-            if (hipMemcpyAsync(ac.data(), d_acov, ac.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "D2H"); break; }
+            // d_acov: nlag rows of autocovariance sums, then one row of sum_c (m_c - mean of the m_c)^2
+            if (hipMalloc(&d_acov, (size_t)(nlag + 1) * d1 * sizeof(double)) != hipSuccess) { rc = mhx_fail(MHX_ENOMEM, "autocov scratch"); break; }
+            (void)hipMemsetAsync(d_acov, 0, (size_t)(nlag + 1) * d1 * sizeof(double), ctx->stream);
             const double M = (double)C * nparts, Mnc = (double)nc * nparts;
+            for (int part = 0; part < nparts; ++part)
+                hipLaunchKernelGGL(k_diag_between, dim3((unsigned)((C + 255) / 256), d1), dim3(256), 0, ctx->stream,
+                                   d_mean + (size_t)part * d1 * C, d_sums, d1, C, M, d_acov + (size_t)nlag * d1);
+            // grid.z holds the lags: long chains (max_lag of half a chain) need more lags than one launch may have
+            int zmax = 0;
+            if (hipDeviceGetAttribute(&zmax, hipDeviceAttributeMaxGridDimZ, ctx->device) != hipSuccess || zmax < 1) zmax = 65535;
+            for (int part = 0; part < nparts; ++part)
+                for (long k0 = 0; k0 < nlag; k0 += zmax)
+                    hipLaunchKernelGGL(k_diag_autocov, dim3((unsigned)((nc + 63) / 64), d1, (unsigned)std::min<long>(nlag - k0, zmax)), dim3(64),
+                                       0, ctx->stream, d_samples + (size_t)part * N * d1 * C, N, d1, C, nc, k0,
+                                       d_mean + (size_t)part * d1 * C, d_acov);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "k_diag_autocov failed"); break; }
+            std::vector<double> ac((size_t)(nlag + 1) * d1);
+            if (hipMemcpyAsync(ac.data(), d_acov, ac.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "D2H"); break; }
             for (int p = 0; p < d1; ++p) {
                 // chain-averaged autocovariances with the N/(N-1) factor that makes lag 0 the within variance
                 for (long k = 0; k < nlag; ++k) ac[(size_t)k * d1 + p] /= Mnc * (double)(N - 1);
                 const double W = h[2 * (size_t)d1 + p] / M;
-                const double Vm = M > 1.0 ? std::max((h[d1 + p] - h[p] * h[p] / M) / (M - 1.0), 0.0) : 0.0;
+                const double Vm = M > 1.0 ? ac[(size_t)nlag * d1 + p] / (M - 1.0) : 0.0;
                 const double varp = (double)(N - 1) / (double)N * W + Vm;
                 // the subset's own within variance stands in for W, so that rho_0 = 1 - (A_0 - A_0)/var+ = 1
                 bool trunc = false;
@@ -183,11 +200,20 @@ int api_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* pa
         for (int i = 0; i < nparams && rc == MHX_OK; ++i) {
             hipLaunchKernelGGL(k_diag_gather_param, dim3(grid), dim3(256), 0, ctx->stream, r->d_samples, N, d1, C, params[i], k0, p0);
             if (rocprim::radix_sort_pairs(tmp, tmp_bytes, k0, k1, p0, p1, (size_t)S, 0, 8 * (unsigned)sizeof(mhx_real), ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "radix sort failed"); break; }
-            mhx_real q[2];
+            mhx_real q[4];
             const long i05 = (long)(0.05 * (double)(S - 1)), i95 = (long)(0.95 * (double)(S - 1));
             if (hipMemcpyAsync(&q[0], k1 + i05, sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                 hipMemcpyAsync(&q[1], k1 + i95, sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(&q[2], k1, sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipMemcpyAsync(&q[3], k1 + (S - 1), sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
                 hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = mhx_fail(MHX_EHIP, "quantile copy failed"); break; }
+            // the bit order of the sort puts a NaN at an end (sign set: first, sign clear: last): such a row has no ranks, and the
+            // searches of k_diag_rank_scores are not run on it
+            if (q[2] != q[2] || q[3] != q[3]) {
+                if (ess_bulk) ess_bulk[i] = std::nan("");
+                if (ess_tail) ess_tail[i] = std::nan("");
+                continue;
+            }
             hipLaunchKernelGGL(k_diag_rank_scores, dim3(grid), dim3(256), 0, ctx->stream, k1, p1, S, q[0], q[1],
                                series, series + S, series + 2 * S);
             if (hipGetLastError() != hipSuccess) { rc = mhx_fail(MHX_EHIP, "k_diag_rank_scores failed"); break; }
@@ -197,7 +223,8 @@ int api_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* pa
             if (rc) break;
             if (ess_bulk) ess_bulk[i] = e[0];
             // the smaller of the two quantile ESS values; a truncated (negated) one keeps its sign
-            if (ess_tail) ess_tail[i] = std::fabs(e[1]) < std::fabs(e[2]) ? e[1] : e[2];
+            // (an indicator that is constant has no ESS: NaN, whichever of the two it is)
+            if (ess_tail) ess_tail[i] = e[1] != e[1] || e[2] != e[2] ? std::nan("") : std::fabs(e[1]) < std::fabs(e[2]) ? e[1] : e[2];
         }
     } while (0);
     void* ptrs[] = {k0, k1, p0, p1, series, tmp};

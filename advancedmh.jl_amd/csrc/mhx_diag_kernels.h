@@ -20,12 +20,16 @@ MHX_DEV void mhx_diag_moments_body(const mhx_real* __restrict__ samples, const l
     if (c < C) {
         const mhx_real* s = samples + (long)p * C + c;
         const long stride = (long)d1 * C;
+        // the mean about the first draw: a chain that never moved has m == x_0 and v == 0 exactly, whatever x_0 is
+        const double x0 = (double)s[0];
         double sum = 0.0;
-        for (long t = 0; t < N; ++t) sum += (double)s[t * stride];
-        m = sum / (double)N;
+        for (long t = 0; t < N; ++t) sum += (double)s[t * stride] - x0;
+        m = x0 + sum / (double)N;
         double ss = 0.0;
         for (long t = 0; t < N; ++t) { const double e = (double)s[t * stride] - m; ss += e * e; }
         v = N > 1 ? ss / (double)(N - 1) : 0.0;
+        // a non-finite draw: the chain's mean, and with it every sum and autocovariance of the row, is NaN (never +-inf)
+        if (!(fabs(m) <= 1.7976931348623157e308) || v != v) m = v = __longlong_as_double(0x7ff8000000000000ll);
         mean[(long)p * C + c] = m;
     }
     // block reduction of (m, m^2, v) then one fp64 atomic each
@@ -43,13 +47,14 @@ MHX_DEV void mhx_diag_moments_body(const mhx_real* __restrict__ samples, const l
     }
 }
 
-// grid (ceil(nc/64), dim+1, max_lag+1), block 64: acov[k][p] += sum_{c<nc} sum_t (x_t-m_c)(x_{t+k}-m_c)
+// grid (ceil(nc/64), dim+1, lags of this launch), block 64: acov[k][p] += sum_{c<nc} sum_t (x_t-m_c)(x_{t+k}-m_c), k = k0 + blockIdx.z
+// (the host slices the lags so that grid.z stays within the device's limit)
 MHX_DEV void mhx_diag_autocov_body(const mhx_real* __restrict__ samples, const long N, const int d1, const long C,
-                                   const long nc, const double* __restrict__ mean, double* __restrict__ acov)
+                                   const long nc, const long k0, const double* __restrict__ mean, double* __restrict__ acov)
 {
     const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int p = blockIdx.y;
-    const long k = blockIdx.z;
+    const long k = k0 + blockIdx.z;
     double acc = 0.0;
     if (c < nc && k < N) {
         const mhx_real* s = samples + (long)p * C + c;
@@ -67,6 +72,22 @@ MHX_DEV void mhx_diag_autocov_body(const mhx_real* __restrict__ samples, const l
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
     if (threadIdx.x == 0) atomicAdd(&acov[k * d1 + p], acc);
+}
+
+// grid (ceil(C/256), dim+1) per half: between[p] += sum_c (m_c - sum_m[p] / M)^2 -- the between-chain variance of the ESS about the
+// mean of the chain means.  (sum_m2 - sum_m^2 / M, which the un-normalised sums leave to the caller, cancels |mean|^2 / Vm of the
+// digits: 1e-3 of var+ is lost to it in fp64 for a parameter at 1e4 +- 0.01.)
+MHX_DEV void mhx_diag_between_body(const double* __restrict__ mean, const double* __restrict__ sums, const int d1, const long C,
+                                   const double M, double* __restrict__ between, double* red)
+{
+    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int p = blockIdx.y;
+    double x = 0.0;
+    if (c < C) { const double e = mean[(long)p * C + c] - sums[p] / M; x = e * e; }
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&between[p], red[0] + red[1] + red[2] + red[3]);
 }
 
 // the same three sums from running moments (runs that kept no sample tensor): m_c = mean, s2_c = M2/(n-1)

@@ -1273,7 +1273,8 @@ class Run:
 
     def diagnostics(self, max_lag=0, ess_chains=256, split=False):
         """Sums for R-hat / between-chain ESS (all chains) and, if max_lag > 0, the Geyer ESS from the multi-chain
-        autocorrelations.  split=True: every chain counts as two half-chains (split R-hat).  See include/mhx.h
+        autocorrelations.  split=True: every chain counts as two half-chains (split R-hat).  A row that never moved, or that
+        holds a non-finite draw, has ess_geyer = NaN (never the n_chains x n_samples of a perfect sampler).  See include/mhx.h
         (mhx_run_diagnostics)."""
         d1 = self.dim + 1
         arrs = [np.zeros(d1, dtype=np.float64) for _ in range(4)]
@@ -1309,7 +1310,8 @@ class Run:
     def ess_bulk_tail(self, params=None, max_lag=0, ess_chains=256, split=True):
         """Rank-normalised bulk ESS and tail ESS (Vehtari et al. 2021; MCMCChains' ess_bulk / ess_tail) of the given
         parameter rows (default: all, lp included) of the last sample buffer, sorted and scored on the device.
-        max_lag = 0: half the draws of a (half-)chain.  Negative values: upper bounds (see include/mhx.h)."""
+        max_lag = 0: half the draws of a (half-)chain.  Negative values: upper bounds; a constant row or one that holds a NaN
+        gives NaN, +-inf draws are ranked like any other (see include/mhx.h)."""
         n_saved = C.c_int64()
         L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
         N = int(n_saved.value) // (2 if split else 1)

@@ -556,7 +556,18 @@ int mhx_run_destroy(mhx_run *run);
  * autocorrelations rho_t = 1 - (W' - A_t)/var+ (Vehtari et al. 2021, eq. 10: A_t the lag-t autocovariance
  * averaged over the first `ess_chains` chains, W' = A_0, var+ from all chains; one chain: A_t/A_0), lags
  * 0..max_lag; it is returned NEGATED when the sequence was still positive at max_lag (|ess| is then an upper
- * bound).  With cfg.split every chain is two half-chains: C -> 2C, N -> floor(N/2) in all of the above. */
+ * bound).  With cfg.split every chain is two half-chains: C -> 2C, N -> floor(N/2) in all of the above (the last draw of an odd N
+ * is not read).  Lags: nlag = min(max_lag + 1, N) rounded down to even, summed in pairs P_m = rho_2m + rho_2m+1 up to the first
+ * P_m <= 0, each pair no larger than the one before; tau = -1 + 2 sum P_m, never below 1e-3.  Any max_lag is served: the lags are
+ * launched in slices of the device's grid limit (hipDeviceProp_t::maxGridSize[2]).
+ * Rows without an answer say so -- they never report the C N draws of a perfect sampler:
+ *   - a row without variance in the chains read (a parameter that never moved: A_0 == 0; or var+ == 0): ess = NaN.  The mean of
+ *     a chain is taken about its first draw, so a chain that repeats ANY value has m_c equal to it and s2_c == 0 exactly.  Its
+ *     R-hat (from the sums, W == 0) is NaN when all chains share the constant and Vm comes out 0 (exact when the constant and its
+ *     square times C are representable), +inf when they differ (Vm > 0);
+ *   - a row that holds a non-finite draw (NaN of either sign, +inf, -inf -- the lp row of a chain outside the support) among the
+ *     draws read: sum_m, sum_m2, sum_v and ess are all NaN (never +-inf), and so are R-hat and the between-chain ESS;
+ *   - no such row changes the numbers of any other row. */
 typedef struct {
     int32_t max_lag;    /* 0: skip the autocovariance ESS (ess[] = NaN) */
     int32_t ess_chains; /* chains used for the autocovariances, 0 = all */
@@ -630,7 +641,14 @@ int mhx_comm_allgather_walkers(mhx_comm *comm, mhx_run *run, int half);
  * ess_bulk, ess_tail) of the parameters params[0..nparams) (indices into the dim+1 rows, lp = dim) of the sample
  * buffer: the draws of one parameter are sorted on the device, replaced by the normal scores of their ranks (bulk)
  * and by the indicators of the 5 % / 95 % quantiles (tail: the smaller of the two), and the multi-chain ESS above
- * (cfg.max_lag, cfg.ess_chains, cfg.split) is taken of those series.  Negated values: as for ess[] above. */
+ * (cfg.max_lag, cfg.ess_chains, cfg.split) is taken of those series.  Negated values: as for ess[] above.
+ * Equal draws share the average of their ranks.  All n_saved x nchains draws are ranked; with cfg.split and an odd n_saved the
+ * series of the last draw is then not read.  Rows without an answer, as above:
+ *   - a row that holds a NaN of either sign (found at the ends of the sorted draws: the sort's bit order puts a NaN with the sign
+ *     set first and one with it clear last; no rank is computed): ess_bulk = ess_tail = NaN;
+ *   - +inf / -inf draws have ranks like any other: both values are finite (where mhx_run_diagnostics gives NaN for the row);
+ *   - a constant row, or one whose 5 % or 95 % indicator is constant within every (half-)chain read: NaN for the value built on the
+ *     series without variance (ess_tail is NaN when either indicator's is). */
 int mhx_run_ess_bulk_tail(mhx_run *run, const mhx_diag_cfg *cfg, const int32_t *params, int32_t nparams,
                           double *ess_bulk, double *ess_tail /* each [nparams], either may be NULL */);
 
