@@ -354,6 +354,19 @@ extern "C" int mhx_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const 
     return is64(r) ? mhx_f64::api_run_ess_bulk_tail(R64(r), cfg, params, nparams, ess_bulk, ess_tail)
                    : mhx_f32::api_run_ess_bulk_tail(R32(r), cfg, params, nparams, ess_bulk, ess_tail);
 }
+extern "C" int mhx_run_rank_diagnostics(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* params, int32_t nparams, double* ess_bulk,
+                                        double* ess_tail, double* rhat_bulk, double* rhat_tail)
+{
+    NEED(r, "mhx_run_rank_diagnostics");
+    return is64(r) ? mhx_f64::api_run_rank_diagnostics(R64(r), cfg, params, nparams, ess_bulk, ess_tail, rhat_bulk, rhat_tail)
+                   : mhx_f32::api_run_rank_diagnostics(R32(r), cfg, params, nparams, ess_bulk, ess_tail, rhat_bulk, rhat_tail);
+}
+extern "C" int mhx_run_rank_scores(mhx_run* r, int32_t param, int32_t folded, void* out_host)
+{
+    NEED(r, "mhx_run_rank_scores");
+    return is64(r) ? mhx_f64::api_run_rank_scores(R64(r), param, folded, static_cast<double*>(out_host))
+                   : mhx_f32::api_run_rank_scores(R32(r), param, folded, static_cast<float*>(out_host));
+}
 extern "C" int mhx_ctx_order_statistics(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                         const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks, double* out)
 {

@@ -232,6 +232,215 @@ int api_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* pa
     return rc;
 }
 
+// ---- rank-normalised split R-hat, bulk and folded (Vehtari et al. 2021, section 4.1), from the same one sort ----
+// mhx_run_ess_bulk_tail above stays as it is (its results are pinned bit for bit by its own test, and it is the yardstick of
+// tools/bench_rank_diag.py); what follows repeats its steps per row -- gather, sort, tie searches and indicators -- scores both
+// series with diag_normal_score (a few ulp of fp64 at every rank) and adds the folded scores by search in the sorted array
+// (mhx_diag_fold_rank: no second sort).
+// The normal score of a tie-averaged rank, z = Phi^-1((rank - 3/8) / (S + 1/4)), to a few ulp of fp64 over the whole range.
+// k_diag_rank_scores forms p in double and inverts it: p carries an ABSOLUTE rounding error of 2^-54 near 1/2 and 2^-53 near 1, which
+// Phi^-1 returns magnified by 1 / phi(z) -- thousands of ulp of a score near zero, hundreds at the top score.  Here the argument is
+// always a quotient of two exactly representable numbers (rank is a multiple of 1/2, S < 2^32) and small where z is small:
+//   |p - 1/2| <= 1/4   z = sqrt2 erfinv(2 q),  q = p - 1/2 = (rank - (S + 1) / 2) / (S + 1/4)
+//   else               z = -+ sqrt2 erfcinv(2 t), t = the tail probability (rank - 3/8) / (S + 1/4) or (S - rank + 5/8) / (S + 1/4)
+// Both inverses are well conditioned on their range (relative condition number below 1.2).
+MHX_DEV double diag_normal_score(const double rank, const long S)
+{
+    const double den = (double)S + 0.25, a = rank - 0.5 * ((double)S + 1.0);
+    const double sqrt2 = 1.4142135623730951;
+    if (fabs(a) <= 0.25 * den) return sqrt2 * erfinv(2.0 * (a / den));
+    const double t = (a < 0.0 ? rank - 0.375 : (double)S - rank + 0.625) / den;
+    const double z = sqrt2 * erfcinv(2.0 * t);
+    return a < 0.0 ? -z : z;
+}
+
+// k_diag_rank_scores with the score above (that kernel stays as it is: mhx_run_ess_bulk_tail keeps its bits)
+__global__ void __launch_bounds__(256)
+k_diag_rank_scores_wc(const mhx_real* __restrict__ sorted, const unsigned* __restrict__ pos, const long S, const mhx_real q05,
+                      const mhx_real q95, mhx_real* __restrict__ z, mhx_real* __restrict__ lo, mhx_real* __restrict__ hi)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= S) return;
+    const unsigned e = pos[r];
+    const mhx_real key = sorted[r];
+    long a0 = 0, a1 = r;                                   // first index with sorted[i] == key
+    while (a0 < a1) { const long mid = (a0 + a1) >> 1; if (sorted[mid] < key) a0 = mid + 1; else a1 = mid; }
+    const long first = a0;
+    a0 = r; a1 = S - 1;                                    // last index with sorted[i] == key
+    while (a0 < a1) { const long mid = (a0 + a1 + 1) >> 1; if (sorted[mid] > key) a1 = mid - 1; else a0 = mid; }
+    z[e] = (mhx_real)diag_normal_score(0.5 * ((double)first + (double)a0) + 1.0, S);
+    lo[e] = key <= q05 ? MHX_R(1.0) : MHX_R(0.0);
+    hi[e] = key <= q95 ? MHX_R(1.0) : MHX_R(0.0);
+}
+
+__global__ void __launch_bounds__(256)
+k_diag_fold_scores(const mhx_real* __restrict__ sorted, const unsigned* __restrict__ pos, const long S, const mhx_real m,
+                   mhx_real* __restrict__ z)
+{
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= S) return;
+    const double rank = mhx_diag_fold_rank(sorted, S, m, r);
+    z[pos[r]] = (mhx_real)diag_normal_score(rank, S);
+}
+
+struct rank_scratch {
+    mhx_real *k0 = nullptr, *k1 = nullptr, *series = nullptr;   // series: bulk scores | 5 % indicator | 95 % indicator | folded scores
+    unsigned *p0 = nullptr, *p1 = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+    ~rank_scratch()
+    {
+        void* ptrs[] = {k0, k1, p0, p1, series, tmp};
+        for (void* q : ptrs) if (q) (void)hipFree(q);
+    }
+};
+
+static int rank_check(const mhx_run* r, const char* who)
+{
+    if (r->moments_mode || r->n_saved < 4) return mhx_fail(MHX_ESTATE, "%s: needs a sample buffer with >= 4 draws", who);
+    if ((long)r->n_saved * (long)r->n >= (1L << 32)) return mhx_fail(MHX_EINVAL, "%s: more than 2^32 draws per parameter", who);
+    return MHX_OK;
+}
+
+static int rank_scratch_alloc(mhx_ctx* ctx, long S, rank_scratch* w)
+{
+    if (hipMalloc(&w->k0, S * sizeof(mhx_real)) != hipSuccess || hipMalloc(&w->k1, S * sizeof(mhx_real)) != hipSuccess ||
+        hipMalloc(&w->p0, S * sizeof(unsigned)) != hipSuccess || hipMalloc(&w->p1, S * sizeof(unsigned)) != hipSuccess ||
+        hipMalloc(&w->series, 4 * S * sizeof(mhx_real)) != hipSuccess) return mhx_fail(MHX_ENOMEM, "rank diagnostics scratch");
+    if (rocprim::radix_sort_pairs(nullptr, w->tmp_bytes, w->k0, w->k1, w->p0, w->p1, (size_t)S, 0, 8 * (unsigned)sizeof(mhx_real), ctx->stream) != hipSuccess ||
+        hipMalloc(&w->tmp, w->tmp_bytes ? w->tmp_bytes : 1) != hipSuccess) return mhx_fail(MHX_ENOMEM, "radix sort scratch");
+    return MHX_OK;
+}
+
+// what the host reads of a sorted row, in ONE synchronisation: the 5 % and 95 % order statistics, the two ends, the middle pair
+struct rank_row {
+    mhx_real q05, q95, first, last, median;
+    bool has_nan;
+};
+
+// gather row p, sort it (k1 / p1: ascending keys and their [t][c] positions) and fetch rank_row
+static int rank_sort_row(mhx_run* r, rank_scratch* w, int p, rank_row* out)
+{
+    mhx_ctx* ctx = r->ctx;
+    const long N = r->n_saved, C = r->n, S = N * C;
+    hipLaunchKernelGGL(k_diag_gather_param, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, r->d_samples, N, r->dim + 1, C, p,
+                       w->k0, w->p0);
+    if (rocprim::radix_sort_pairs(w->tmp, w->tmp_bytes, w->k0, w->k1, w->p0, w->p1, (size_t)S, 0, 8 * (unsigned)sizeof(mhx_real), ctx->stream) != hipSuccess)
+        return mhx_fail(MHX_EHIP, "radix sort failed");
+    const long at[6] = {(long)(0.05 * (double)(S - 1)), (long)(0.95 * (double)(S - 1)), 0, S - 1, (S - 1) / 2, S / 2};
+    mhx_real q[6];
+    for (int j = 0; j < 6; ++j)
+        if (hipMemcpyAsync(&q[j], w->k1 + at[j], sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+            return mhx_fail(MHX_EHIP, "quantile copy failed");
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return mhx_fail(MHX_EHIP, "quantile copy failed");
+    out->q05 = q[0]; out->q95 = q[1]; out->first = q[2]; out->last = q[3];
+    // Julia's middle(): the middle draw of an odd S, else half of each of the middle pair added in the run's width
+    out->median = (S & 1) ? q[4] : q[4] / MHX_R(2.0) + q[5] / MHX_R(2.0);
+    // the bit order of the sort puts a NaN at an end (sign set: first, sign clear: last)
+    out->has_nan = q[2] != q[2] || q[3] != q[3];
+    return MHX_OK;
+}
+
+static void rank_launch_bulk(mhx_ctx* ctx, rank_scratch* w, long S, const rank_row& row)
+{
+    hipLaunchKernelGGL(k_diag_rank_scores_wc, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, w->k1, w->p1, S, row.q05, row.q95,
+                       w->series, w->series + S, w->series + 2 * S);
+}
+static void rank_launch_fold(mhx_ctx* ctx, rank_scratch* w, long S, const rank_row& row)
+{
+    hipLaunchKernelGGL(k_diag_fold_scores, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, ctx->stream, w->k1, w->p1, S, row.median,
+                       w->series + 3 * S);
+}
+
+// R-hat = sqrt(var+ / W) from the three sums over M (half-)chains of n draws (include/mhx.h); W == 0: NaN (Vm == 0) or +inf
+static double rhat_from_sums(double sum_m, double sum_m2, double sum_v, double M, double n)
+{
+    if (!(M > 1.0)) return std::nan("");
+    const double W = sum_v / M;
+    const double Vm = std::fmax((sum_m2 - sum_m * sum_m / M) / (M - 1.0), 0.0);
+    return std::sqrt(((n - 1.0) / n * W + Vm) / W);
+}
+
+int api_run_rank_diagnostics(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* params, int32_t nparams, double* ess_bulk,
+                             double* ess_tail, double* rhat_bulk, double* rhat_tail)
+{
+    const char* who = "mhx_run_rank_diagnostics";
+    if (!r || !cfg || !params || nparams <= 0) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    int rc = rank_check(r, who);
+    if (rc) return rc;
+    mhx_ctx* ctx = r->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const long N = r->n_saved, C = r->n, S = N * C;
+    for (int i = 0; i < nparams; ++i)
+        if (params[i] < 0 || params[i] > r->dim) return mhx_fail(MHX_EINVAL, "%s: parameter %d out of range", who, params[i]);
+    const bool want_ess = ess_bulk || ess_tail;
+    const double nparts = cfg->split ? 2.0 : 1.0, M = (double)C * nparts, n = (double)(cfg->split ? N / 2 : N);
+    const double nan = std::nan("");
+    rank_scratch w;
+    if ((rc = rank_scratch_alloc(ctx, S, &w))) return rc;
+    for (int i = 0; i < nparams; ++i) {
+        rank_row row;
+        if ((rc = rank_sort_row(r, &w, params[i], &row))) return rc;
+        if (row.has_nan) {                                  // no ranks: no search is launched on the row
+            if (ess_bulk) ess_bulk[i] = nan;
+            if (ess_tail) ess_tail[i] = nan;
+            if (rhat_bulk) rhat_bulk[i] = nan;
+            if (rhat_tail) rhat_tail[i] = nan;
+            continue;
+        }
+        const bool fold = rhat_tail && std::isfinite(row.median);
+        rank_launch_bulk(ctx, &w, S, row);
+        if (fold) rank_launch_fold(ctx, &w, S, row);
+        if (hipGetLastError() != hipSuccess) return mhx_fail(MHX_EHIP, "%s: the score kernels failed to launch", who);
+        // the bulk scores: their moments come with the ESS call (the ESS itself as mhx_run_ess_bulk_tail takes it)
+        double e[3] = {nan, nan, nan}, sm = 0.0, sm2 = 0.0, sv = 0.0;
+        if (want_ess || rhat_bulk)
+            if ((rc = diag_compute(ctx, w.series, N, 1, C, cfg, nullptr, nullptr, &sm, &sm2, &sv, want_ess ? &e[0] : nullptr))) return rc;
+        if (rhat_bulk) rhat_bulk[i] = rhat_from_sums(sm, sm2, sv, M, n);
+        if (want_ess) {
+            for (int j = 1; j < 3; ++j)
+                if ((rc = diag_compute(ctx, w.series + (size_t)j * S, N, 1, C, cfg, nullptr, nullptr, nullptr, nullptr, nullptr, &e[j]))) return rc;
+            if (ess_bulk) ess_bulk[i] = e[0];
+            if (ess_tail) ess_tail[i] = e[1] != e[1] || e[2] != e[2] ? nan : std::fabs(e[1]) < std::fabs(e[2]) ? e[1] : e[2];
+        }
+        if (rhat_tail) {
+            rhat_tail[i] = nan;                             // a median that is not finite folds nothing
+            if (fold) {
+                if ((rc = diag_compute(ctx, w.series + 3 * (size_t)S, N, 1, C, cfg, nullptr, nullptr, &sm, &sm2, &sv, nullptr))) return rc;
+                rhat_tail[i] = rhat_from_sums(sm, sm2, sv, M, n);
+            }
+        }
+    }
+    return MHX_OK;
+}
+
+int api_run_rank_scores(mhx_run* r, int32_t param, int32_t folded, mhx_real* out_host)
+{
+    const char* who = "mhx_run_rank_scores";
+    if (!r || !out_host) return mhx_fail(MHX_EINVAL, "%s: NULL argument", who);
+    int rc = rank_check(r, who);
+    if (rc) return rc;
+    if (param < 0 || param > r->dim) return mhx_fail(MHX_EINVAL, "%s: parameter %d out of range", who, (int)param);
+    mhx_ctx* ctx = r->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const long S = (long)r->n_saved * (long)r->n;
+    rank_scratch w;
+    if ((rc = rank_scratch_alloc(ctx, S, &w))) return rc;
+    rank_row row;
+    if ((rc = rank_sort_row(r, &w, param, &row))) return rc;
+    if (row.has_nan || (folded && !std::isfinite(row.median))) {
+        const mhx_real nan = (mhx_real)std::nan("");
+        for (long e = 0; e < S; ++e) out_host[e] = nan;
+        return MHX_OK;
+    }
+    if (folded) rank_launch_fold(ctx, &w, S, row);
+    else rank_launch_bulk(ctx, &w, S, row);
+    if (hipGetLastError() != hipSuccess) return mhx_fail(MHX_EHIP, "%s: the score kernel failed to launch", who);
+    HIP_TRY(hipMemcpyAsync(out_host, w.series + (folded ? 3 * (size_t)S : 0), (size_t)S * sizeof(mhx_real), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return MHX_OK;
+}
+
 // ---- exact order statistics: histogram radix select on the tensor in place (DESIGN.md section 6.5) ----
 // Three pre-built (digit width, groups per launch) forms; a pass of d digit bits runs on the narrowest that holds it.  LDS per
 // block: groups << width counters of 4 bytes = 16, 64 and 64 KiB.

@@ -116,6 +116,42 @@ MHX_DEV void mhx_diag_from_moments_body(const mhx_real* __restrict__ mom_mean, c
     }
 }
 
+// ---- the rank of a draw among the FOLDED draws g = fl(|x - m|), from the one ascending array of the draws ----
+// x -> fl(x - m) is non-decreasing (rounding is monotone), so g is non-increasing over the draws below m and non-decreasing over
+// the rest.  With `left(i)` = sorted[i] < m, each of the four predicates
+//   !(left && g > f)    !(left && g >= f)    (!left && g >= f)    (!left && g > f)
+// is false on a prefix of the whole array and true behind it; the first true index of each, iL_leq <= iL_less <= iR_less <= iR_leq,
+// gives the number of draws with g < f (iR_less - iL_less) and with g <= f (iR_leq - iL_leq) without knowing where the sides meet.
+// The tie-averaged 1-based rank of the draw at sorted index r follows.  Exact where the subtraction collapses distinct draws onto
+// one g as well: only the order of g is used, never that of x within a side.
+// The searches run in pairs: the two loads of a step are independent, so the dependent chain is 2 log2 S loads, not 4.  A pair
+// keeps its loads unconditional (the probe of a finished search is clamped into the array and its result dropped).
+MHX_DEV double mhx_diag_fold_rank(const mhx_real* __restrict__ sorted, const long S, const mhx_real m, const long r)
+{
+    const mhx_real f = mhx_abs(sorted[r] - m);
+    // iL_less in [0, S], iR_less in [0, S]
+    long a0 = 0, a1 = S, b0 = 0, b1 = S;
+    while (a0 < a1 || b0 < b1) {
+        const long ma = (a0 + a1) >> 1, mb = (b0 + b1) >> 1;
+        const mhx_real ya = sorted[ma < S ? ma : S - 1], yb = sorted[mb < S ? mb : S - 1];
+        const bool pa = !(ya < m && mhx_abs(ya - m) >= f), pb = !(yb < m) && mhx_abs(yb - m) >= f;
+        if (a0 < a1) { if (pa) a1 = ma; else a0 = ma + 1; }
+        if (b0 < b1) { if (pb) b1 = mb; else b0 = mb + 1; }
+    }
+    const long il_less = a0, ir_less = b0;
+    // iL_leq in [0, iL_less], iR_leq in [iR_less, S]
+    a0 = 0; a1 = il_less; b0 = ir_less; b1 = S;
+    while (a0 < a1 || b0 < b1) {
+        const long ma = (a0 + a1) >> 1, mb = (b0 + b1) >> 1;
+        const mhx_real ya = sorted[ma < S ? ma : S - 1], yb = sorted[mb < S ? mb : S - 1];
+        const bool pa = !(ya < m && mhx_abs(ya - m) > f), pb = !(yb < m) && mhx_abs(yb - m) > f;
+        if (a0 < a1) { if (pa) a1 = ma; else a0 = ma + 1; }
+        if (b0 < b1) { if (pb) b1 = mb; else b0 = mb + 1; }
+    }
+    const long less = ir_less - il_less, leq = b0 - a0;
+    return 0.5 * ((double)less + (double)leq - 1.0) + 1.0;
+}
+
 // ---- exact order statistics: one pass of a histogram radix SELECT over the strided tensor ----
 // A draw becomes an unsigned key of its own width whose unsigned order is the numeric order (sign set: all bits inverted;
 // sign clear: sign bit set); every NaN becomes the all-ones key, so NaNs come last as in numpy.sort.  -0.0 < +0.0 as keys.

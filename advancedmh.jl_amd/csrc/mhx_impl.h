@@ -79,6 +79,9 @@ void mhx_jit_unlock();
                             double* ess);                                                                              \
     int api_run_ess_bulk_tail(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* params, int32_t nparams,             \
                               double* ess_bulk, double* ess_tail);                                                     \
+    int api_run_rank_diagnostics(mhx_run* r, const mhx_diag_cfg* cfg, const int32_t* params, int32_t nparams,          \
+                                 double* ess_bulk, double* ess_tail, double* rhat_bulk, double* rhat_tail);            \
+    int api_run_rank_scores(mhx_run* r, int32_t param, int32_t folded, REAL* out_host);                                \
     int api_ctx_order_statistics(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,   \
                                  const int32_t* params, int32_t nparams, const int64_t* ranks, int32_t nranks,         \
                                  double* out);                                                                         \

@@ -130,7 +130,7 @@ EXPORTS = [
     "mhx_compact_expand", "mhx_run_host_stats", "mhx_rwmh_create_components", "mhx_rwmh_create_conditional",
     "mhx_rwmh_create_composite", "mhx_run_order_statistics", "mhx_ctx_order_statistics", "mhx_group_order_statistics",
     "mhx_run_select_histogram", "mhx_run_cross_moments", "mhx_ctx_cross_moments", "mhx_group_cross_moments",
-    "mhx_run_hpd", "mhx_ctx_hpd",
+    "mhx_run_hpd", "mhx_ctx_hpd", "mhx_run_rank_diagnostics", "mhx_run_rank_scores",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -273,6 +273,8 @@ def lib():
         L.mhx_group_cross_moments.argtypes = [vp, i32p, C.c_int32, dp, dp, dp, i64p]
         L.mhx_run_hpd.argtypes = [vp, i32p, C.c_int32, C.c_double, dp, dp]
         L.mhx_ctx_hpd.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_double, dp, dp]
+        L.mhx_run_rank_diagnostics.argtypes = [vp, C.POINTER(DiagCfg), i32p, C.c_int32, dp, dp, dp, dp]
+        L.mhx_run_rank_scores.argtypes = [vp, C.c_int32, C.c_int32, rp]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -863,6 +863,16 @@ class CorrelationMatrix(np.ndarray):
     __repr__ = __str__
 
 
+RHAT_KINDS = {"rank": "rhat", "bulk": "rhat_bulk", "tail": "rhat_tail", "basic": None}
+
+
+def _rhat_column(kind):
+    """the key of Run.rank_diagnostics that holds an R-hat kind (MCMCDiagnosticTools' names); None: the split R-hat of diagnostics"""
+    if kind not in RHAT_KINDS:
+        raise L.ArgumentError(L.MHX_EINVAL, "rhat kind must be one of %s" % ", ".join(repr(k) for k in RHAT_KINDS))
+    return RHAT_KINDS[kind]
+
+
 class Chains:
     """value[iteration, parameter, chain]; the last parameter is the internal `lp`
     (ext/AdvancedMHMCMCChainsExt.jl:36, :96-118)."""
@@ -898,20 +908,42 @@ class Chains:
     def params(self):
         return [n for n in self.names if n not in self.internals]
 
-    def summarystats(self, max_lag=0):
+    def summarystats(self, max_lag=0, rhat_kind="basic"):
         """The table MCMCChains prints for the reference's chains (README.md:59-63): mean, std, ess_bulk, ess_tail
         and (split) rhat per parameter, computed on the device from the run's sample buffer (mhx_run_diagnostics,
-        mhx_run_ess_bulk_tail); internals (lp) are left out as MCMCChains does."""
+        mhx_run_ess_bulk_tail); internals (lp) are left out as MCMCChains does.  rhat_kind: as Chains.rhat; any kind but "basic"
+        takes the ESS columns and R-hat from one mhx_run_rank_diagnostics call."""
         if self.state is None:
             raise L.ArgumentError(L.MHX_EINVAL, "summarystats needs the live run (chain.state)")
+        col = _rhat_column(rhat_kind)
         idx = [i for i, n in enumerate(self.names) if n not in self.internals]
-        dg = self.state.diagnostics(max_lag=0, split=True)
-        et = self.state.ess_bulk_tail(params=idx, max_lag=max_lag, split=True)
+        if col is None:
+            dg = self.state.diagnostics(max_lag=0, split=True)
+            et = self.state.ess_bulk_tail(params=idx, max_lag=max_lag, split=True)
+            rhat = dg["rhat"][idx] if "rhat" in dg else np.full(len(idx), np.nan)
+        else:
+            et = self.state.rank_diagnostics(params=idx, max_lag=max_lag, split=True)
+            rhat = et[col]
         full = self.state.diagnostics(max_lag=0, split=False)
         std = np.sqrt(np.maximum(full.get("var_plus", full["W"]), 0.0))
         return dict(parameters=[self.names[i] for i in idx], mean=full["mean"][idx], std=std[idx],
-                    ess_bulk=et["ess_bulk"], ess_tail=et["ess_tail"],
-                    rhat=dg["rhat"][idx] if "rhat" in dg else np.full(len(idx), np.nan))
+                    ess_bulk=et["ess_bulk"], ess_tail=et["ess_tail"], rhat=rhat)
+
+    def rhat(self, kind="rank"):
+        """Split R-hat of every parameter (internals left out as in summarystats), by MCMCDiagnosticTools' kinds: "rank" (its
+        default: the larger of "bulk" and "tail"), "bulk" (of the normal scores of the ranks), "tail" (of the normal scores of the
+        ranks of |x - median|) -- all three from Run.rank_diagnostics -- and "basic", the classic split R-hat of the draws
+        themselves (mhx_run_diagnostics; what summarystats prints by default).  dict(parameters, kind, rhat [nparams])."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "rhat needs the live run (chain.state)")
+        col = _rhat_column(kind)
+        idx = [i for i, n in enumerate(self.names) if n not in self.internals]
+        if col is None:
+            dg = self.state.diagnostics(max_lag=0, split=True)
+            rhat = dg["rhat"][idx] if "rhat" in dg else np.full(len(idx), np.nan)
+        else:
+            rhat = self.state.rank_diagnostics(params=idx, split=True, ess=False)[col]
+        return dict(parameters=[self.names[i] for i in idx], kind=kind, rhat=rhat)
 
     def quantile(self, probs=DEFAULT_QUANTILE_PROBS):
         """The "Quantiles" table MCMCChains prints for the reference's chains (README.md:65-71): exact quantiles (Julia's and
@@ -955,11 +987,11 @@ class Chains:
             self.value.shape[0], self.value.shape[1], self.value.shape[2],
             "Float64" if self.value.dtype == np.float64 else "Float32", self.start, self.thin, self.range()[-1])
 
-    def describe(self, probs=DEFAULT_QUANTILE_PROBS, max_lag=0):
+    def describe(self, probs=DEFAULT_QUANTILE_PROBS, max_lag=0, rhat_kind="basic"):
         """The two tables MCMCChains prints for the reference's chains (README.md:57-71) as text: "Summary Statistics" -- the columns
         of summarystats() with naive_se = std / sqrt(S) and mcse = std / sqrt(ess_bulk), S the draws of all chains -- and
-        "Quantiles" below it."""
-        st, qt = self.summarystats(max_lag=max_lag), self.quantile(probs)
+        "Quantiles" below it.  rhat_kind: which R-hat the rhat column holds (Chains.rhat)."""
+        st, qt = self.summarystats(max_lag=max_lag, rhat_kind=rhat_kind), self.quantile(probs)
         S = float(self.value.shape[0] * self.value.shape[2])
         with np.errstate(divide="ignore", invalid="ignore"):
             naive_se, mcse = st["std"] / np.sqrt(S), st["std"] / np.sqrt(st["ess_bulk"])
@@ -974,10 +1006,11 @@ class Chains:
             lines.append("  %-12s " % n + " ".join("%9.4f" % q for q in qt["quantiles"][i]))
         return "\n".join(lines)
 
-    def __repr__(self):
+    def __repr__(self, rhat_kind="basic"):
         head = self._header()
+        _rhat_column(rhat_kind)
         try:
-            st = self.summarystats()
+            st = self.summarystats(rhat_kind=rhat_kind)
         except Exception:
             return head
         lines = [head, "  parameters        mean       std   ess_bulk   ess_tail      rhat"]
@@ -1324,6 +1357,40 @@ class Run:
         L.check(L.lib().mhx_run_ess_bulk_tail(self.h, C.byref(cfg), idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx),
                                               bulk.ctypes.data_as(dp), tail.ctypes.data_as(dp)))
         return dict(params=idx, ess_bulk=np.abs(bulk), ess_tail=np.abs(tail), bulk_truncated=bulk < 0, tail_truncated=tail < 0)
+
+    def rank_diagnostics(self, params=None, max_lag=0, ess_chains=256, split=True, ess=True, rhat=True):
+        """ess_bulk_tail and the rank-normalised split R-hat of the same rows from ONE sort per row (mhx_run_rank_diagnostics):
+        rhat_bulk of the normal scores of the draws, rhat_tail of those of the folded draws |x - median|, rhat = the larger of the
+        two (Vehtari et al. 2021; MCMCDiagnosticTools' kinds :bulk, :tail, :rank), NaN only if both are.  A row that holds a NaN
+        gives NaN everywhere, a median that is not finite rhat_tail = NaN (see include/mhx.h).  ess=False / rhat=False: that half is
+        neither computed nor returned."""
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
+        N = int(n_saved.value) // (2 if split else 1)
+        if max_lag <= 0:
+            max_lag = max(2, N // 2)
+        idx = self._rows(params)
+        bulk, tail, rb, rt = [np.zeros(len(idx)) for _ in range(4)]
+        cfg = L.DiagCfg(max_lag, ess_chains, 1 if split else 0)
+        dp = C.POINTER(C.c_double)
+        ptrs = [a.ctypes.data_as(dp) if on else None for a, on in ((bulk, ess), (tail, ess), (rb, rhat), (rt, rhat))]
+        L.check(L.lib().mhx_run_rank_diagnostics(self.h, C.byref(cfg), idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx), *ptrs))
+        out = dict(params=idx)
+        if ess:
+            out.update(ess_bulk=np.abs(bulk), ess_tail=np.abs(tail), bulk_truncated=bulk < 0, tail_truncated=tail < 0)
+        if rhat:
+            out.update(rhat_bulk=rb, rhat_tail=rt, rhat=np.fmax(rb, rt))
+        return out
+
+    def rank_scores(self, param, folded=False):
+        """[n_saved][nchains] in the run's width: the normal scores of the tie-averaged ranks of one parameter row over all draws of
+        all chains (folded: of |x - median|), as rank_diagnostics reads them (mhx_run_rank_scores) -- what the rank plots are made
+        of.  NaN throughout for a row that holds a NaN (folded: also for a median that is not finite)."""
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
+        out = np.empty((max(int(n_saved.value), 0), self.n), dtype=self.real)
+        L.check(L.lib().mhx_run_rank_scores(self.h, int(param), 1 if folded else 0, L.rptr(out)))
+        return out
 
     def order_statistics(self, ranks, params=None):
         """Exact order statistics of the last sample buffer, selected on the device without a sort (mhx_run_order_statistics):

@@ -29,6 +29,8 @@ print(chain)
 # ... and the two tables MCMCChains prints under it (README.md:57-71): summary statistics with naive_se / mcse, and the quantiles,
 # selected exactly on the device from all 102 400 draws (mhx_run_order_statistics)
 print(chain.describe())
+# the same tables with the rank-normalised R-hat (the larger of the bulk and the folded one: MCMCChains' `rhat(chain; kind = :rank)`)
+print(chain.describe(rhat_kind="rank"))
 # the correlation matrix MCMCChains' `cor(chain)` gives, from cross moments taken on the device's fp64 matrix cores (mhx_run_cross_moments)
 print(chain.cor())
 print("data: mean %.4f std %.4f;  acceptance rate %.3f;  kernel variant %d" % (

@@ -652,6 +652,41 @@ int mhx_comm_allgather_walkers(mhx_comm *comm, mhx_run *run, int half);
 int mhx_run_ess_bulk_tail(mhx_run *run, const mhx_diag_cfg *cfg, const int32_t *params, int32_t nparams,
                           double *ess_bulk, double *ess_tail /* each [nparams], either may be NULL */);
 
+/* Rank-normalised split R-hat (Vehtari et al. 2021, section 4.1; MCMCDiagnosticTools' rhat kinds :bulk, :tail and, as the larger of
+ * the two, :rank) next to the bulk / tail ESS above, from the SAME one sort per parameter.  With y the ascending order of a row's
+ * S = n_saved x nchains draws (all of them are ranked, as above):
+ *   median        m = y[S/2] for an odd S, else y[S/2-1]/2 + y[S/2]/2 added in the run's width (Julia's `middle`)
+ *   bulk scores   z  = Phi^-1((rank(x) - 3/8) / (S + 1/4)), equal draws sharing the average of their ranks: the series of ess_bulk.
+ *                 Evaluated to a few ulp of double at every rank, then rounded to the run's width: sqrt2 erfinv(2 (p - 1/2)) with
+ *                 p - 1/2 = (rank - (S+1)/2) / (S + 1/4) in the middle half, -+sqrt2 erfcinv(2 t) of the tail probability t outside
+ *                 it (numerators exact).  mhx_run_ess_bulk_tail keeps its own evaluation (p rounded in double, then inverted: off by
+ *                 up to 1e-13 absolute at the extremes, which its bounds cover), so the ESS of the two entries agree within those
+ *                 bounds, not bit for bit
+ *   folded scores zf = the same of the ranks of g = |x - m|, the subtraction rounded once to the run's width.  No second sort: g falls
+ *                 over the draws below m and rises over the rest (rounding is monotone), so the number of draws with g < f and with
+ *                 g <= f is found by binary searches in y with g evaluated on the fly, and rank = (less + leq - 1) / 2 + 1.  Draws that
+ *                 the rounding collapses onto one g tie, as they do in the definition.
+ *   rhat_bulk     R-hat = sqrt(var+ / W) of z, rhat_tail of zf, from the three sums of mhx_run_diagnostics over the M = nchains
+ *                 (cfg.split: 2 nchains half-chains of floor(n_saved/2) draws; the scores of the last draw of an odd n_saved are not
+ *                 read) chains: W = sum_v/M, Vm = max(0, (sum_m2 - sum_m^2/M)/(M-1)), var+ = (n-1)/n W + Vm
+ *   ess_bulk, ess_tail   as mhx_run_ess_bulk_tail gives them (cfg.max_lag, cfg.ess_chains), run only when one of the two is asked for
+ * Any of the four outputs may be NULL.  Rows without an answer:
+ *   - a row that holds a NaN of either sign (found at the ends of the sort; no search is run on it): NaN in all four;
+ *   - a median that is not finite (half of the draws or more infinite, or -inf and +inf as the middle pair): rhat_tail = NaN, the
+ *     other three untouched by it;
+ *   - +inf / -inf draws with a finite median are ranked like any other (g = +inf for them);
+ *   - scores without variance within every (half-)chain (W == 0: a constant row has z == zf == 0): NaN when Vm == 0, +inf when Vm > 0;
+ *   - one (half-)chain (M == 1): both R-hat values are NaN.
+ * Not here: the mhx_group_* twin (ranks pooled over the members need the histograms of the select, not a sort per member) and the
+ * Julia glue.  MHX_ESTATE: fewer than 4 saved draws or no sample tensor; MHX_EINVAL: a parameter outside [0, dim], 2^32 draws or
+ * more per parameter.  Blocking. */
+int mhx_run_rank_diagnostics(mhx_run *run, const mhx_diag_cfg *cfg, const int32_t *params, int32_t nparams,
+                             double *ess_bulk, double *ess_tail, double *rhat_bulk, double *rhat_tail /* each [nparams] or NULL */);
+/* The scores themselves, for the rank plots of the same paper: out_host [n_saved][nchains] in the run's width (HOST memory), z of row
+ * `param` (folded = 0) or zf (folded = 1).  A row that holds a NaN fills out_host with NaN; so does a median that is not finite when
+ * folded = 1. */
+int mhx_run_rank_scores(mhx_run *run, int32_t param, int32_t folded, void *out_host);
+
 /* Exact order statistics (and with them quantiles, medians, credible intervals: what MCMCChains prints as its "Quantiles" table,
  * README.md:65-71) of the parameters params[0..nparams) (indices into the dim+1 rows, lp = dim) of the sample buffer, without a
  * sort and without a copy of the draws: a histogram radix SELECT that reads the [n_saved][dim+1][nchains] tensor in place.
