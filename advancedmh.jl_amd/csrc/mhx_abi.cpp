@@ -400,6 +400,37 @@ extern "C" int mhx_run_hpd(mhx_run* r, const int32_t* params, int32_t nparams, d
     return is64(r) ? mhx_f64::api_run_hpd(R64(r), params, nparams, alpha, lower, upper)
                    : mhx_f32::api_run_hpd(R32(r), params, nparams, alpha, lower, upper);
 }
+extern "C" int mhx_ctx_histogram(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
+                                 int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts, uint64_t* outside)
+{
+    NEED(ctx, "mhx_ctx_histogram");
+    return is64(ctx) ? mhx_f64::api_ctx_histogram(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, edges, nbins, counts, outside)
+                     : mhx_f32::api_ctx_histogram(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, edges, nbins, counts, outside);
+}
+extern "C" int mhx_run_histogram(mhx_run* r, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts,
+                                 uint64_t* outside)
+{
+    NEED(r, "mhx_run_histogram");
+    return is64(r) ? mhx_f64::api_run_histogram(R64(r), params, nparams, edges, nbins, counts, outside)
+                   : mhx_f32::api_run_histogram(R32(r), params, nparams, edges, nbins, counts, outside);
+}
+extern "C" int mhx_ctx_histogram2d(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
+                                   int32_t nparams, const double* edges, int32_t nbins, const int32_t* pairs, int32_t npairs, uint64_t* counts,
+                                   uint64_t* outside)
+{
+    NEED(ctx, "mhx_ctx_histogram2d");
+    return is64(ctx) ? mhx_f64::api_ctx_histogram2d(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, edges, nbins, pairs, npairs,
+                                                    counts, outside)
+                     : mhx_f32::api_ctx_histogram2d(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, edges, nbins, pairs, npairs,
+                                                    counts, outside);
+}
+extern "C" int mhx_run_histogram2d(mhx_run* r, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, const int32_t* pairs,
+                                   int32_t npairs, uint64_t* counts, uint64_t* outside)
+{
+    NEED(r, "mhx_run_histogram2d");
+    return is64(r) ? mhx_f64::api_run_histogram2d(R64(r), params, nparams, edges, nbins, pairs, npairs, counts, outside)
+                   : mhx_f32::api_run_histogram2d(R32(r), params, nparams, edges, nbins, pairs, npairs, counts, outside);
+}
 extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                      const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
 {

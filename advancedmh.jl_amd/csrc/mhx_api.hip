@@ -37,6 +37,7 @@
 #include "mhx_diag_kernels.h"
 #include "mhx_cross_kernels.h"
 #include "mhx_hpd_kernels.h"
+#include "mhx_hist_kernels.h"
 #ifdef MHX_TOOLS_BUILD
 #include "mhx_jit_embed_tools.inc"   // generated: the device headers as string literals for hiprtc, probes included
 #else
@@ -2103,5 +2104,6 @@ int api_run_destroy(mhx_run* r)
 #include "mhx_api_diag.inc"
 #include "mhx_api_moments.inc"
 #include "mhx_api_hpd.inc"
+#include "mhx_api_hist.inc"
 
 }  // namespace MHX_NS

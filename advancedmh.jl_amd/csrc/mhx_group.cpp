@@ -429,3 +429,47 @@ extern "C" int mhx_group_cross_moments(mhx_group* g, const int32_t* params, int3
     if (n_draws) *n_draws = total;
     return MHX_OK;
 }
+
+// Histograms and pair histograms of the UNION of all members' draws over the same edges: every member counts its own shard
+// (concurrently, each on its own thread and device) and integer counts add, here on the host -- exact, and equal to the unsharded
+// run's arrays.  pairs NULL: the 1-D form.  The members check the arguments; nothing is written unless all of them succeed.
+namespace {
+int group_histogram(mhx_group* g, const char* who, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, int32_t limit,
+                    const int32_t* pairs, int32_t npairs, uint64_t* counts, uint64_t* outside)
+{
+    int rc = need_runs(g, who);
+    if (rc) return rc;
+    if (!params || nparams <= 0 || !edges || !counts || (pairs && npairs <= 0)) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    if (nbins < 1 || nbins > limit) return mhx_fail(MHX_EINVAL, "%s: nbins = %d is not in [1, %d]", who, (int)nbins, (int)limit);
+    const size_t rows = pairs ? (size_t)npairs : (size_t)nparams;
+    const size_t ncount = rows * (size_t)nbins * (pairs ? (size_t)nbins : 1), nout = rows * (pairs ? 1 : 3), stride = ncount + nout;
+    const size_t n = g->mem.size();
+    std::vector<uint64_t> buf(n * stride, 0);
+    rc = for_all(g, who, [g, params, nparams, edges, nbins, pairs, npairs, ncount, stride, &buf](int i) {
+        uint64_t* b = buf.data() + (size_t)i * stride;
+        return pairs ? mhx_run_histogram2d(g->mem[i]->run, params, nparams, edges, nbins, pairs, npairs, b, b + ncount)
+                     : mhx_run_histogram(g->mem[i]->run, params, nparams, edges, nbins, b, b + ncount);
+    });
+    if (rc) return rc;
+    for (size_t k = 0; k < stride; ++k) {
+        uint64_t a = 0;
+        for (size_t i = 0; i < n; ++i) a += buf[i * stride + k];
+        if (k < ncount) counts[k] = a;
+        else if (outside) outside[k - ncount] = a;
+    }
+    return MHX_OK;
+}
+}  // namespace
+
+extern "C" int mhx_group_histogram(mhx_group* g, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts,
+                                   uint64_t* outside)
+{
+    return group_histogram(g, "mhx_group_histogram", params, nparams, edges, nbins, 2048, nullptr, 0, counts, outside);
+}
+
+extern "C" int mhx_group_histogram2d(mhx_group* g, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins,
+                                     const int32_t* pairs, int32_t npairs, uint64_t* counts, uint64_t* outside)
+{
+    if (!pairs) return mhx_fail(MHX_EINVAL, "mhx_group_histogram2d: no pairs");
+    return group_histogram(g, "mhx_group_histogram2d", params, nparams, edges, nbins, 128, pairs, npairs, counts, outside);
+}

@@ -5,7 +5,8 @@ from .dist import Group
 from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposal, ConditionalProposal, CorrGaussian, DensityModel, Ensemble, Exponential, Funnel, Gamma, HipLogDensity, IIDNormal,
                   InverseGamma, IsoGaussian, Laplace, LogDensityModel, MALA, MCMCDistributed, MCMCHIP, MCMCSerial, MCMCThreads, MetropolisHastings, MvNormal, NamedProposals, Normal, RandomWalkProposal,
                   RobustAdaptiveMetropolis, Run, RWMH, StaticMH, StaticProposal, StructArray, combine_diagnostics, StretchProposal,
-                  correlation_from_covariance, covariance_from_moments, hpd_ranks,
+                  correlation_from_covariance, covariance_from_moments, hpd_ranks, Corner, density_binning_bound, density_from_counts, histogram_edges,
+                  silverman_bandwidth,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
                   logdensity, pack_lower, sample, unpack_lower, zeros)
 from . import trace

@@ -131,6 +131,7 @@ EXPORTS = [
     "mhx_rwmh_create_composite", "mhx_run_order_statistics", "mhx_ctx_order_statistics", "mhx_group_order_statistics",
     "mhx_run_select_histogram", "mhx_run_cross_moments", "mhx_ctx_cross_moments", "mhx_group_cross_moments",
     "mhx_run_hpd", "mhx_ctx_hpd", "mhx_run_rank_diagnostics", "mhx_run_rank_scores",
+    "mhx_run_histogram", "mhx_ctx_histogram", "mhx_group_histogram", "mhx_run_histogram2d", "mhx_ctx_histogram2d", "mhx_group_histogram2d",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -275,6 +276,12 @@ def lib():
         L.mhx_ctx_hpd.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_double, dp, dp]
         L.mhx_run_rank_diagnostics.argtypes = [vp, C.POINTER(DiagCfg), i32p, C.c_int32, dp, dp, dp, dp]
         L.mhx_run_rank_scores.argtypes = [vp, C.c_int32, C.c_int32, rp]
+        L.mhx_run_histogram.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, u64p, u64p]
+        L.mhx_ctx_histogram.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, dp, C.c_int32, u64p, u64p]
+        L.mhx_group_histogram.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, u64p, u64p]
+        L.mhx_run_histogram2d.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
+        L.mhx_ctx_histogram2d.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
+        L.mhx_group_histogram2d.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
         _lib = _loaded[_lib_path] = L
     return _lib
 

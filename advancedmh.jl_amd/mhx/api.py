@@ -824,6 +824,141 @@ def correlation_from_covariance(cov):
     return cor
 
 
+HISTOGRAM_MAX_BINS, HISTOGRAM2D_MAX_BINS = 2048, 128      # MHX_HIST_MAX_BINS / MHX_HIST2D_MAX_BINS of the library
+
+
+def histogram_edges(lo, hi, bins):
+    """The bins + 1 float64 edges numpy itself uses for `np.histogram(x, bins, range=(lo, hi))`:
+    np.histogram_bin_edges([], bins, (lo, hi)), its widening of lo == hi to (lo - 0.5, hi + 0.5) included."""
+    try:
+        bins, lo, hi = int(bins), float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise L.ArgumentError(L.MHX_EINVAL, "histogram_edges: bins must be an integer and lo, hi numbers")
+    if bins < 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "histogram_edges: bins = %d must be at least 1" % bins)
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+        raise L.ArgumentError(L.MHX_EINVAL, "histogram_edges: the range (%r, %r) must be finite and non-decreasing" % (lo, hi))
+    return np.histogram_bin_edges(np.empty(0, dtype=np.float64), bins, (lo, hi))
+
+
+def _histogram_edges(owner, idx, bins, range, edges, what):
+    """[m][bins + 1] float64 edges of a histogram call on a Run or Group: `edges` passed through (one set, or one per row), else
+    numpy's edges of `range` (one (lo, hi), or one per row), else of every row's own minimum and maximum -- ONE order_statistics call
+    for ranks 0 and S - 1.  A NaN or infinite end is refused with the row's index (numpy raises ValueError there)."""
+    m = len(idx)
+    if edges is not None:
+        e = np.array(edges, dtype=np.float64, ndmin=1)
+        if e.ndim == 1:
+            e = np.tile(e, (m, 1))
+        if e.ndim != 2 or e.shape[0] != m or e.shape[1] < 2:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: edges must be [bins + 1] or [%d][bins + 1]" % (what, m))
+        return np.ascontiguousarray(e)
+    if range is None:
+        S = owner._n_draws()
+        if S < 1:
+            owner.order_statistics([0], idx)                # raises the library's refusal (no device sample tensor)
+        ends = owner.order_statistics([0, S - 1], idx)
+    else:
+        ends = np.array(range, dtype=np.float64)
+        if ends.shape == (2,):
+            ends = np.tile(ends, (m, 1))
+        if ends.shape != (m, 2):
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: range must be (lo, hi) or one (lo, hi) per row, [%d][2]" % (what, m))
+    for k in np.arange(m):
+        if not np.all(np.isfinite(ends[k])):
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: the range of row %d, (%r, %r), is not finite%s" % (
+                what, int(idx[k]), float(ends[k, 0]), float(ends[k, 1]), " (the row holds such draws: give a range)" if range is None else ""))
+    if m == 0:
+        return np.empty((0, int(bins) + 1))
+    return np.ascontiguousarray(np.stack([histogram_edges(lo, hi, bins) for lo, hi in ends]))
+
+
+def _all_pairs(m):
+    """every i < j of m slots, [m (m - 1) / 2][2] int32"""
+    i, j = np.triu_indices(int(m), 1)
+    return np.ascontiguousarray(np.stack([i, j], axis=1), dtype=np.int32)
+
+
+def _histogram_call(fn, handle, idx, e, pairs=None):
+    """one mhx_*_histogram (pairs None) or mhx_*_histogram2d call: (counts, outside) as int64"""
+    m, B = len(idx), e.shape[1] - 1
+    i32p, u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    if pairs is None:
+        counts, outside = np.zeros((m, B), dtype=np.uint64), np.zeros((m, 3), dtype=np.uint64)
+        rc = fn(handle, idx.ctypes.data_as(i32p), m, e.ctypes.data_as(C.POINTER(C.c_double)), B, counts.ctypes.data_as(u64p),
+                outside.ctypes.data_as(u64p))
+    else:
+        counts, outside = np.zeros((len(pairs), B, B), dtype=np.uint64), np.zeros(len(pairs), dtype=np.uint64)
+        rc = fn(handle, idx.ctypes.data_as(i32p), m, e.ctypes.data_as(C.POINTER(C.c_double)), B, pairs.ctypes.data_as(i32p), len(pairs),
+                counts.ctypes.data_as(u64p), outside.ctypes.data_as(u64p))
+    L.check(rc)
+    return counts.view(np.int64), outside.view(np.int64)
+
+
+def _histogram(owner, fn, bins, range, params, edges):
+    idx = owner._rows(params)
+    e = _histogram_edges(owner, idx, bins, range, edges, "histogram")
+    counts, outside = _histogram_call(fn, owner.h, idx, e)
+    return counts, e, outside
+
+
+def _histogram2d(owner, fn, params, pairs, bins, range, edges):
+    idx = owner._rows(params)
+    pr = _all_pairs(len(idx)) if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    e = _histogram_edges(owner, idx, bins, range, edges, "histogram2d")
+    counts, outside = _histogram_call(fn, owner.h, idx, e, pr)
+    return counts, e, outside, pr
+
+
+def silverman_bandwidth(std, q25, q75, S):
+    """Silverman's rule as KernelDensity.jl's default applies it: 0.9 min(std, IQR / 1.34) S^(-1/5); where that minimum is 0 the std
+    takes its place, and 1 where the std is 0 as well (or there is a single draw)."""
+    width = min(float(std), (float(q75) - float(q25)) / 1.34) if int(S) > 1 else 0.0
+    if width == 0.0:
+        width = float(std) if int(S) > 1 and float(std) != 0.0 else 1.0
+    return 0.9 * width * float(int(S)) ** -0.2
+
+
+def density_from_counts(counts, edges, h):
+    """(x, density): the Gaussian kernel density estimate of bandwidth h of draws that were binned to `counts` over `edges`, every
+    draw standing at its bin's centre: x[k] = the centres, density[k] = sum_j counts[j] phi_h(x[k] - x[j]) / sum(counts), a direct
+    sum in float64.  Every draw moved by at most half a cell delta / 2, so
+    |density[k] - the exact estimate at x[k]| <= (delta / 2) max|phi_h'| = delta / (2 h^2 sqrt(2 pi e))."""
+    counts, edges, h = np.asarray(counts, dtype=np.float64), np.asarray(edges, dtype=np.float64), float(h)
+    x = 0.5 * (edges[:-1] + edges[1:])
+    nz = np.flatnonzero(counts)
+    z = (x[:, None] - x[None, nz]) / h
+    dens = (np.exp(-0.5 * z * z) @ counts[nz]) / (counts.sum() * h * math.sqrt(2.0 * math.pi))
+    return x, dens
+
+
+def density_binning_bound(edges, h):
+    """the bound of density_from_counts for uniform edges"""
+    delta = (float(edges[-1]) - float(edges[0])) / (len(edges) - 1)
+    return delta / (2.0 * float(h) ** 2 * math.sqrt(2.0 * math.pi * math.e))
+
+
+class Corner:
+    """what Chains.corner returns: the numbers of a corner plot.  names [m]; edges[name] [bins + 1]; marginal[name] int64 [bins];
+    joint[(a, b)] int64 [bins][bins] for every a before b in names, cell [bin of a][bin of b]; outside[name] / outside[(a, b)]:
+    the draws a histogram left out (none for a row of finite draws: the edges span each row's minimum and maximum)."""
+
+    def __init__(self, names, edges, marginal, joint, outside):
+        self.names, self.edges, self.marginal, self.joint, self.outside = list(names), edges, marginal, joint, outside
+
+    def __repr__(self):
+        bins = len(next(iter(self.edges.values()))) - 1 if self.edges else 0
+        lines = ["Corner (%d parameters, %d bins): %d marginal [%d], %d joint [%d][%d]" % (
+            len(self.names), bins, len(self.marginal), bins, len(self.joint), bins, bins)]
+        for n in self.names:
+            lines.append("  %-12s [%.4g, %.4g]  %d draws" % (n, self.edges[n][0], self.edges[n][-1], int(self.marginal[n].sum())))
+        for (a, b), H in self.joint.items():
+            lines.append("  %-12s %d draws" % ("%s x %s" % (a, b), int(H.sum())))
+        return "\n".join(lines)
+
+    __str__ = __repr__
+
+
 def _check_moments(rc):
     """check() for the cross moments: asking a run that kept no sample tensor for them is an ArgumentError here (the C ABI says
     MHX_ESTATE, as for the order statistics)"""
@@ -980,6 +1115,80 @@ class Chains:
         """the correlation matrix of the same rows (MCMCChains' `cor(chain)`); prints with the parameter names"""
         idx = self._moment_rows(include_lp, "cor")
         return CorrelationMatrix(self.state.cor(params=idx), [self.names[i] for i in idx])
+
+    def _live_row(self, name, what):
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s needs the live run (chain.state)" % what)
+        return self.names.index(name)
+
+    def histogram(self, name, bins=64, range=None):
+        """(counts int64 [bins], edges [bins + 1]) of one parameter over all draws of all chains, counted on the device from the run's
+        sample buffer (mhx_run_histogram): both members equal `np.histogram(chain[name].astype(np.float64).ravel(), bins, range)`
+        -- the draws widened, as numpy builds float32 edges for a float32 array.  range None: the row's minimum and maximum."""
+        row = self._live_row(name, "histogram")
+        counts, e, _ = self.state.histogram(bins, range, params=[row])
+        return counts[0], e[0]
+
+    def histogram2d(self, x, y, bins=32, range=None):
+        """(H int64 [bins][bins], xedges, yedges) of two parameters over all draws of all chains, counted on the device
+        (mhx_run_histogram2d): what `np.histogram2d` gives for the widened draws, its H cast to integers.  range: None (each row's
+        minimum and maximum) or [(xlo, xhi), (ylo, yhi)]."""
+        rows = [self._live_row(x, "histogram2d"), self._live_row(y, "histogram2d")]
+        H, e, _, _ = self.state.histogram2d(params=rows, pairs=[(0, 1)], bins=bins, range=range)
+        return H[0], e[0], e[1]
+
+    def corner(self, names=None, bins=32):
+        """MCMCChains' `corner`, as numbers: a Corner with the marginal histogram of every parameter in `names` (default: all,
+        internals (lp) left out unless named) and the joint histogram of every pair, over `bins` uniform bins between each row's
+        minimum and maximum -- one order-statistics call, one 1-D and one 2-D histogram call on the device."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "corner needs the live run (chain.state)")
+        names = self.params() if names is None else list(names)
+        idx = np.array([self.names.index(n) for n in names], dtype=np.int32)
+        e = _histogram_edges(self.state, idx, bins, None, None, "corner")
+        if e.shape[1] - 1 > HISTOGRAM2D_MAX_BINS:
+            raise L.ArgumentError(L.MHX_EINVAL, "corner: bins = %d is not in [1, %d]" % (e.shape[1] - 1, HISTOGRAM2D_MAX_BINS))
+        counts, _, out1 = self.state.histogram(params=idx, edges=e)
+        joint, outside = {}, {n: out1[i] for i, n in enumerate(names)}
+        if len(names) > 1:
+            H, _, out2, pairs = self.state.histogram2d(params=idx, edges=e)
+            for q, (i, j) in enumerate(pairs):
+                joint[(names[i], names[j])] = H[q]
+                outside[(names[i], names[j])] = int(out2[q])
+        return Corner(names, {n: e[i] for i, n in enumerate(names)}, {n: counts[i] for i, n in enumerate(names)}, joint, outside)
+
+    def density(self, name, npoints=2048, bandwidth=None):
+        """MCMCChains' `density`: (x [npoints], density [npoints]), the Gaussian kernel density estimate of one parameter over all
+        draws of all chains.  bandwidth None: Silverman's rule as KernelDensity.jl's default applies it (silverman_bandwidth), the
+        std from the pooled variance (Run.cov of the row), the quartiles by the definition of Run.quantiles.  x are the centres of
+        the npoints (<= 2048) bins of histogram_edges(min - 4 h, max + 4 h, npoints); the only sweep of the draws is a histogram on
+        the device (mhx_run_histogram), and the kernel sum over its integer counts runs on the host in float64
+        (density_from_counts).
+        Deviation from KernelDensity.jl: that package spreads every draw linearly over its two neighbouring grid points (and
+        convolves by FFT); here a draw counts in the cell it lies in, so that the counts stay integers -- exact, reproducible and
+        additive over shards.  The price is bounded: a draw moves by at most half a cell delta / 2, so
+        |density[k] - the exact estimate at x[k]| <= delta / (2 h^2 sqrt(2 pi e)) (density_binning_bound)."""
+        row = self._live_row(name, "density")
+        run = self.state
+        S = run._n_draws()
+        if S < 1:
+            run.order_statistics([0], [row])               # raises the library's refusal
+        j, j1, g = quantile_ranks(S, [0.25, 0.75])
+        os_ = run.order_statistics(np.concatenate([j, j1, [0, S - 1]]), [row])[0]
+        q25, q75 = quantiles_from_order_statistics(os_[:2], os_[2:4], g)
+        lo, hi = float(os_[4]), float(os_[5])
+        if not (math.isfinite(lo) and math.isfinite(hi)):
+            raise L.ArgumentError(L.MHX_EINVAL, "density: the draws of %s span (%r, %r): not finite" % (name, lo, hi))
+        if bandwidth is None:
+            std = math.sqrt(max(float(run.cov([row])[0, 0]), 0.0)) if S > 1 else 0.0
+            h = silverman_bandwidth(std, q25, q75, S)
+        else:
+            h = float(bandwidth)
+        if not (math.isfinite(h) and h > 0.0):
+            raise L.ArgumentError(L.MHX_EINVAL, "density: the bandwidth %r is not a positive finite number" % h)
+        e = histogram_edges(lo - 4.0 * h, hi + 4.0 * h, npoints)
+        counts, _, _ = run.histogram(params=[row], edges=e)
+        return density_from_counts(counts[0], e, h)
 
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
@@ -1425,6 +1634,31 @@ class Run:
         L.check(L.lib().mhx_run_hpd(self.h, idx.ctypes.data_as(C.POINTER(C.c_int32)), len(idx), float(alpha),
                                     lower.ctypes.data_as(dp), upper.ctypes.data_as(dp)))
         return lower, upper
+
+    def _n_draws(self):
+        """n_saved x nchains of the last sample buffer (0: the run holds none)"""
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
+        return max(int(n_saved.value), 0) * self.n
+
+    def histogram(self, bins=64, range=None, params=None, edges=None):
+        """(counts int64 [m][bins], edges float64 [m][bins + 1], outside int64 [m][3]) of the given parameter rows (default: all, lp
+        included; a row may repeat) over all draws of all chains of the last sample buffer, counted on the device in one sweep of
+        the tensor in place (mhx_run_histogram).  Bin j holds e[j] <= x < e[j+1], the last bin is closed; outside = the draws below
+        e[0], above e[bins], and NaN: exactly `np.histogram` of the draws cast to float64 over the same edges, and
+        counts.sum(1) + outside.sum(1) == n_saved x nchains.
+        range: one (lo, hi) or one per row, turned into numpy's own edges (histogram_edges); None: every row's minimum and maximum,
+        from one order_statistics call (a NaN or infinite end is an ArgumentError that names the row).  edges: explicit edges
+        ([bins + 1] for all rows or [m][bins + 1]; finite, non-decreasing, need not be uniform) instead of bins / range."""
+        return _histogram(self, L.lib().mhx_run_histogram, bins, range, params, edges)
+
+    def histogram2d(self, params=None, pairs=None, bins=32, range=None, edges=None):
+        """(counts int64 [npairs][bins][bins], edges [m][bins + 1], outside int64 [npairs], pairs int32 [npairs][2]): the pair
+        histograms of the given rows (mhx_run_histogram2d).  pairs: slots (i, j) into params, default every i < j; cell
+        [bin of slot i][bin of slot j] by the rule of histogram on each axis (what `np.histogram2d` gives for the widened draws); a
+        draw without a bin on either axis counts in the pair's outside.  bins (one for both axes, <= 128), range and edges as in
+        histogram, per row.  One sweep reads both rows of every pair: m (m - 1) rows for all pairs of m."""
+        return _histogram2d(self, L.lib().mhx_run_histogram2d, params, pairs, bins, range, edges)
 
     def _rows(self, params):
         return np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)

@@ -184,6 +184,28 @@ class Group:
             return self.order_statistics([0], params)       # raises the library's refusal
         return _quantiles(self.order_statistics, int(n_saved.value) * self.n, probs, params)
 
+    def _rows(self, params):
+        return np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)
+
+    def _n_draws(self):
+        from . import _lib as L
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_device_samples(self.runs[0].h, None, None, C.byref(n_saved)))
+        return max(int(n_saved.value), 0) * self.n
+
+    def histogram(self, bins=64, range=None, params=None, edges=None):
+        """Run.histogram over the UNION of all members' draws (mhx_group_histogram): the members count their shards over the same
+        edges side by side and the integer counts are added on the host -- equal to the unsharded run's arrays."""
+        from . import _lib as L
+        from .api import _histogram
+        return _histogram(self, L.lib().mhx_group_histogram, bins, range, params, edges)
+
+    def histogram2d(self, params=None, pairs=None, bins=32, range=None, edges=None):
+        """Run.histogram2d over the UNION of all members' draws (mhx_group_histogram2d)"""
+        from . import _lib as L
+        from .api import _histogram2d
+        return _histogram2d(self, L.lib().mhx_group_histogram2d, params, pairs, bins, range, edges)
+
     def cross_moments(self, params=None, shift=None):
         """Run.cross_moments over the UNION of all members' draws (mhx_group_cross_moments): every member takes the moments of its
         shard about the same shift, and the group adds them in member order.  shift None: the mean of saved sample 0 over the chains

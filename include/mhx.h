@@ -755,6 +755,38 @@ int mhx_run_hpd(mhx_run *run, const int32_t *params, int32_t nparams, double alp
 int mhx_ctx_hpd(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                 const int32_t *params, int32_t nparams, double alpha, double *lower, double *upper);
 
+/* Histograms of the pooled draws over caller-given bin edges (what MCMCChains offers as `histogram`, and the counts behind `density`
+ * and `corner`) of the parameters params[0..nparams) (indices into the dim+1 rows, lp = dim; any order, a row may repeat), counted on
+ * the device in ONE sweep of the [n_saved][dim+1][nchains] tensor in place.
+ *   edges[nparams][nbins+1]  the edges of every row slot: finite, non-decreasing (repeats allowed); nbins in [1, 2048]
+ *   counts[nparams][nbins]   bin j of a slot holds the draws with e[j] <= x < e[j+1]; the last bin is closed: x == e[nbins] counts in
+ *                            bin nbins - 1.  j = (number of edges <= x) - 1, so of a run of equal edges the last one takes the draw
+ *   outside[nparams][3]      (NULL: not wanted) draws below e[0] (-inf included), above e[nbins] (+inf included), NaN (either sign)
+ * A draw is widened exactly to double and every comparison is a double comparison: the counts are those of numpy.histogram on the
+ * draws cast to float64 with bins=edges.  -0.0 and +0.0 are the same draw.  Per-block counts in LDS, added to uint64 counters with
+ * integer atomics: exact, two calls return the same bits, and for every slot sum(counts) + below + above + nan == n_saved * nchains
+ * (no 2^32 limit).  No floating-point atomics.
+ * MHX_EINVAL: a parameter outside [0, dim], nbins outside [1, 2048], an edge that is not finite, edges that decrease, more than 65535
+ * slots; MHX_ESTATE: the run holds no device sample tensor.  Nothing is written unless the call succeeds.  Blocking. */
+int mhx_run_histogram(mhx_run *run, const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, uint64_t *counts,
+                      uint64_t *outside);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics) */
+int mhx_ctx_histogram(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                      const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, uint64_t *counts, uint64_t *outside);
+/* Pair histograms (the cells of a corner plot): pair q counts the draws of the rows params[pairs[2q]] and params[pairs[2q+1]] --
+ * slots into params, which also pick each axis' edges -- that share a saved sample and a chain.
+ *   edges[nparams][nbins+1]  as above; one nbins for both axes, in [1, 128]
+ *   counts[npairs][nbins][nbins]  the first slot slowest: cell [bin of the first row][bin of the second], each by the rule above (what
+ *                            numpy.histogram2d gives for the widened draws)
+ *   outside[npairs]          (NULL: not wanted) draws without a bin on either axis: NaN, below or above
+ * One sweep reads both rows of every pair, so m (m - 1) / 2 pairs read m (m - 1) rows.  sum(counts) + outside == n_saved * nchains for
+ * every pair.  MHX_EINVAL as above with nbins outside [1, 128], and a pair slot outside [0, nparams) or more than 65535 pairs. */
+int mhx_run_histogram2d(mhx_run *run, const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, const int32_t *pairs,
+                        int32_t npairs, uint64_t *counts, uint64_t *outside);
+int mhx_ctx_histogram2d(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                        const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, const int32_t *pairs, int32_t npairs,
+                        uint64_t *counts, uint64_t *outside);
+
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
  * (README.md:135-148: one task per chain) -- here one host thread per GPU behind the ABI.  A group is N member contexts (one
@@ -798,6 +830,12 @@ int mhx_group_order_statistics(mhx_group *g, const int32_t *params, int32_t npar
  * (concurrently), and sums about a common shift add -- here on the host, in member order.  *n_draws = the draws of all members. */
 int mhx_group_cross_moments(mhx_group *g, const int32_t *params, int32_t nparams, const double *shift, double *sum, double *cross,
                             int64_t *n_draws);
+/* mhx_run_histogram / mhx_run_histogram2d over the UNION of all members' draws and the same edges: the members count their shards
+ * concurrently and the group adds the integers on the host -- exact, and equal to the unsharded run's arrays */
+int mhx_group_histogram(mhx_group *g, const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, uint64_t *counts,
+                        uint64_t *outside);
+int mhx_group_histogram2d(mhx_group *g, const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, const int32_t *pairs,
+                          int32_t npairs, uint64_t *counts, uint64_t *outside);
 
 #ifdef __cplusplus
 }
