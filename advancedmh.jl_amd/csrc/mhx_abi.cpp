@@ -431,6 +431,23 @@ extern "C" int mhx_run_histogram2d(mhx_run* r, const int32_t* params, int32_t np
     return is64(r) ? mhx_f64::api_run_histogram2d(R64(r), params, nparams, edges, nbins, pairs, npairs, counts, outside)
                    : mhx_f32::api_run_histogram2d(R32(r), params, nparams, edges, nbins, pairs, npairs, counts, outside);
 }
+extern "C" int mhx_ctx_autocovariance(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
+                                      int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin, int64_t chain_count,
+                                      int32_t normalise, double* acov, int64_t* nvalid)
+{
+    NEED(ctx, "mhx_ctx_autocovariance");
+    return is64(ctx) ? mhx_f64::api_ctx_autocovariance(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, params, nparams, lags, nlags, chain_begin,
+                                                       chain_count, normalise, acov, nvalid)
+                     : mhx_f32::api_ctx_autocovariance(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, params, nparams, lags, nlags, chain_begin,
+                                                       chain_count, normalise, acov, nvalid);
+}
+extern "C" int mhx_run_autocovariance(mhx_run* r, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin,
+                                      int64_t chain_count, int32_t normalise, double* acov, int64_t* nvalid)
+{
+    NEED(r, "mhx_run_autocovariance");
+    return is64(r) ? mhx_f64::api_run_autocovariance(R64(r), params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid)
+                   : mhx_f32::api_run_autocovariance(R32(r), params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid);
+}
 extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                      const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
 {

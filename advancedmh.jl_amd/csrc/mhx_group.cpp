@@ -473,3 +473,35 @@ extern "C" int mhx_group_histogram2d(mhx_group* g, const int32_t* params, int32_
     if (!pairs) return mhx_fail(MHX_EINVAL, "mhx_group_histogram2d: no pairs");
     return group_histogram(g, "mhx_group_histogram2d", params, nparams, edges, nbins, 128, pairs, npairs, counts, outside);
 }
+
+// Autocovariance sums over ALL chains of ALL members: sums over chains, so every member takes those of its own shard (concurrently)
+// and the group adds them in member order, on the host.  A row that is NaN in one member is NaN in the group, with nvalid = 0.  The
+// members check the arguments; nothing is written unless all of them succeed.
+extern "C" int mhx_group_autocovariance(mhx_group* g, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags,
+                                        int32_t normalise, double* acov, int64_t* nvalid)
+{
+    const char* who = "mhx_group_autocovariance";
+    int rc = need_runs(g, who);
+    if (rc) return rc;
+    if (!params || nparams <= 0 || !lags || nlags <= 0 || !acov) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    const size_t n = g->mem.size(), na = (size_t)nparams * (size_t)nlags;
+    std::vector<double> buf(n * na, 0.0);
+    std::vector<int64_t> nv(n * (size_t)nparams, 0);
+    rc = for_all(g, who, [g, params, nparams, lags, nlags, normalise, na, &buf, &nv](int i) {
+        return mhx_run_autocovariance(g->mem[i]->run, params, nparams, lags, nlags, 0, 0, normalise, buf.data() + (size_t)i * na,
+                                      nv.data() + (size_t)i * (size_t)nparams);
+    });
+    if (rc) return rc;
+    for (size_t k = 0; k < na; ++k) {
+        double a = 0.0;
+        for (size_t i = 0; i < n; ++i) a += buf[i * na + k];
+        acov[k] = a;
+    }
+    if (nvalid)
+        for (size_t p = 0; p < (size_t)nparams; ++p) {
+            int64_t a = 0;
+            for (size_t i = 0; i < n; ++i) a += nv[i * (size_t)nparams + p];
+            nvalid[p] = std::isnan(acov[p * (size_t)nlags]) ? 0 : a;
+        }
+    return MHX_OK;
+}

@@ -132,6 +132,7 @@ EXPORTS = [
     "mhx_run_select_histogram", "mhx_run_cross_moments", "mhx_ctx_cross_moments", "mhx_group_cross_moments",
     "mhx_run_hpd", "mhx_ctx_hpd", "mhx_run_rank_diagnostics", "mhx_run_rank_scores",
     "mhx_run_histogram", "mhx_ctx_histogram", "mhx_group_histogram", "mhx_run_histogram2d", "mhx_ctx_histogram2d", "mhx_group_histogram2d",
+    "mhx_run_autocovariance", "mhx_ctx_autocovariance", "mhx_group_autocovariance",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -282,6 +283,10 @@ def lib():
         L.mhx_run_histogram2d.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
         L.mhx_ctx_histogram2d.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
         L.mhx_group_histogram2d.argtypes = [vp, i32p, C.c_int32, dp, C.c_int32, i32p, C.c_int32, u64p, u64p]
+        L.mhx_run_autocovariance.argtypes = [vp, i32p, C.c_int32, i32p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, dp, i64p]
+        L.mhx_ctx_autocovariance.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, i32p, C.c_int32, i32p, C.c_int32, C.c_int64, C.c_int64,
+                                             C.c_int32, dp, i64p]
+        L.mhx_group_autocovariance.argtypes = [vp, i32p, C.c_int32, i32p, C.c_int32, C.c_int32, dp, i64p]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -959,6 +959,66 @@ class Corner:
     __str__ = __repr__
 
 
+ACF_TILE = {"f64": 16, "f32": 8}                            # MHX_ACF_R of the library: the lags of a tile, per width
+
+
+def _autocovariance(owner, fn, lags, params, chains, normalise):
+    """one mhx_*_autocovariance call of a Run (chains: (begin, count), None = all) or a Group (chains False): (acov, nvalid)"""
+    idx = owner._rows(params)
+    lg = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64).reshape(-1)
+    if lg.size and (lg.min() < -2 ** 31 or lg.max() >= 2 ** 31):
+        raise L.ArgumentError(L.MHX_EINVAL, "autocovariance: a lag does not fit 32 bits")
+    lg = lg.astype(np.int32)
+    acov = np.full((len(idx), len(lg)), np.nan, dtype=np.float64)
+    nvalid = np.zeros(len(idx), dtype=np.int64)
+    i32p = C.POINTER(C.c_int32)
+    args = [idx.ctypes.data_as(i32p), len(idx), lg.ctypes.data_as(i32p), len(lg)]
+    if chains is not False:                                 # False: the group form, which takes no range
+        args += [0, 0] if chains is None else [int(chains[0]), int(chains[1])]
+    L.check(fn(owner.h, *args, 1 if normalise else 0, acov.ctypes.data_as(C.POINTER(C.c_double)),
+               nvalid.ctypes.data_as(C.POINTER(C.c_int64))))
+    return acov, nvalid
+
+
+def autocorrelation(acov):
+    """rho(k) = acov[..., k] / acov[..., 0] in float64, for sums over lags that start at lag 0 (either mode of
+    Run.autocovariance: un-normalised, the ratio of the pooled sums; normalised, the mean over the valid chains of each chain's own
+    autocorrelation, since acov[0] is then their number).  A row whose acov[0] is not positive (no chain with variance, or NaN) is
+    NaN."""
+    a = np.asarray(acov, dtype=np.float64)
+    a0 = a[..., :1]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        return np.where(a0 > 0.0, a / np.where(a0 > 0.0, a0, 1.0), np.nan)
+
+
+def integrated_time(rho, c=5.0):
+    """(tau, M, truncated) of ONE autocorrelation function rho over lags 0..K: taus = 2 cumsum(rho) - 1, the window M the first
+    index with M >= c taus[M] (Sokal's automatic windowing, emcee's `auto_window`), tau = taus[M].  No such index: M = K and
+    truncated = True -- the series is too short for this c.  A rho that holds a NaN gives (NaN, K, True)."""
+    r = np.asarray(rho, dtype=np.float64).reshape(-1)
+    if r.size < 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "integrated_time: rho is empty")
+    taus = 2.0 * np.cumsum(r) - 1.0
+    with np.errstate(invalid="ignore"):
+        ok = np.flatnonzero(np.arange(r.size) >= float(c) * taus)
+    if ok.size == 0 or not np.isfinite(taus).all():
+        return float(taus[-1]), r.size - 1, True
+    M = int(ok[0])
+    return float(taus[M]), M, False
+
+
+class AutocorTable(dict):
+    """what Chains.autocor returns: dict(parameters, lags, autocor [nparams][nlags]) that prints as MCMCChains' Autocorrelation table"""
+
+    def __str__(self):
+        lines = ["Autocorrelation", "  parameters   " + " ".join("%9s" % ("lag %d" % k) for k in self["lags"])]
+        for i, n in enumerate(self["parameters"]):
+            lines.append("  %-12s " % n + " ".join("%9.4f" % v for v in self["autocor"][i]))
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
 def _check_moments(rc):
     """check() for the cross moments: asking a run that kept no sample tensor for them is an ArgumentError here (the C ABI says
     MHX_ESTATE, as for the order statistics)"""
@@ -1189,6 +1249,58 @@ class Chains:
         e = histogram_edges(lo - 4.0 * h, hi + 4.0 * h, npoints)
         counts, _, _ = run.histogram(params=[row], edges=e)
         return density_from_counts(counts[0], e, h)
+
+    def autocor(self, lags=(1, 5, 10, 50), mean_of_chains=False, chains=None):
+        """MCMCChains' `autocor(chain; lags)`: an AutocorTable dict(parameters, lags, autocor [nparams][nlags]) of every parameter
+        (internals (lp) left out as in quantile), summed on the device from the run's sample buffer (mhx_run_autocovariance).
+        Every chain is centred about its own mean.  Default: the ratio of the sums over the chains, sum_c A_c(k) / sum_c A_c(0);
+        mean_of_chains: the mean over the chains of each chain's own autocorrelation A_c(k) / A_c(0) (chains that never moved left
+        out).  chains = (begin, count) restricts both to a range; with (c, 1) the row is StatsBase.autocor of chain c either way.
+        Lag 0 is always asked for (it is the denominator) and shown only if listed.  A lag >= len(chain) is an ArgumentError."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "autocor needs the live run (chain.state)")
+        lg = sorted(set(int(k) for k in np.atleast_1d(lags)))
+        for k in lg:
+            if k < 0 or k >= len(self):
+                raise L.ArgumentError(L.MHX_EINVAL, "autocor: lag %d is not in [0, %d), the draws of a chain" % (k, len(self)))
+        idx = [i for i, n in enumerate(self.names) if n not in self.internals]
+        ask = lg if lg and lg[0] == 0 else [0] + lg
+        acov, _ = self.state.autocovariance(ask, params=idx, chains=chains, normalise=bool(mean_of_chains))
+        rho = autocorrelation(acov)[:, len(ask) - len(lg):]
+        return AutocorTable(parameters=[self.names[i] for i in idx], lags=lg, autocor=rho)
+
+    def autocorr_time(self, c=5.0, tol=50, max_lag=None, ensemble=None):
+        """The integrated autocorrelation time of every parameter (internals left out), as emcee's `get_autocorr_time` defines it
+        for an ensemble: the mean over the chains (walkers) of each chain's own autocorrelation function -- the normalised sums of
+        mhx_run_autocovariance over lags 0..max_lag -- summed under Sokal's automatic window (mhx.integrated_time).
+        dict(parameters, tau [nparams], window, truncated, converged = N >= tol tau).  On an Ensemble run of several ensembles,
+        ensemble=e takes the walkers of ensemble e, chains [e W, (e + 1) W); the walkers of different ensembles never mix otherwise
+        than by this choice (None: all chains).
+        max_lag None: N - 1, every lag, as emcee does -- N (N + 1) / 2 multiply-adds per chain and row, about N / 2 sweeps' worth of
+        arithmetic over the tensor (the window rarely needs more than a few tau of them): max_lag caps the lags computed, and a
+        window that is not reached within them comes back truncated."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "autocorr_time needs the live run (chain.state)")
+        N = len(self)
+        K = N - 1 if max_lag is None else int(max_lag)
+        if K < 0 or K >= max(N, 1):
+            raise L.ArgumentError(L.MHX_EINVAL, "autocorr_time: max_lag = %d is not in [0, %d)" % (K, N))
+        chains = None
+        if ensemble is not None:
+            E = int(getattr(self.state, "n_ensembles", 0))
+            if E < 1 or not 0 <= int(ensemble) < E:
+                raise L.ArgumentError(L.MHX_EINVAL, "autocorr_time: ensemble %r of a run of %d ensembles" % (ensemble, E))
+            W = self.state.n // E
+            chains = (int(ensemble) * W, W)
+        idx = [i for i, n in enumerate(self.names) if n not in self.internals]
+        acov, nvalid = self.state.autocovariance(np.arange(K + 1), params=idx, chains=chains, normalise=True)
+        rho = autocorrelation(acov)
+        res = [integrated_time(r, c) for r in rho]
+        tau = np.array([r[0] for r in res], dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            converged = float(N) >= float(tol) * tau
+        return dict(parameters=[self.names[i] for i in idx], tau=tau, window=np.array([r[1] for r in res], dtype=np.int64),
+                    truncated=np.array([r[2] for r in res], dtype=bool), converged=converged, nvalid=nvalid)
 
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
@@ -1659,6 +1771,16 @@ class Run:
         draw without a bin on either axis counts in the pair's outside.  bins (one for both axes, <= 128), range and edges as in
         histogram, per row.  One sweep reads both rows of every pair: m (m - 1) rows for all pairs of m."""
         return _histogram2d(self, L.lib().mhx_run_histogram2d, params, pairs, bins, range, edges)
+
+    def autocovariance(self, lags, params=None, chains=None, normalise=False):
+        """(acov float64 [m][nlags], nvalid int64 [m]) of the given parameter rows (default: all, lp included) at the given lags
+        (strictly increasing, 0 <= lag < n_saved) over the chains `chains` = (begin, count) (count 0: to the last; None: all) of the
+        last sample buffer, summed on the device from the tensor in place (mhx_run_autocovariance).  With m_c the chain's own mean
+        and A_c(k) = sum_{t < N - k} (x_t - m_c)(x_{t+k} - m_c): acov[i][j] = sum_c A_c(k_j), un-normalised, so that shards add; with
+        normalise, sum_c A_c(k_j) / A_c(0) over the nvalid[i] chains that moved at all -- the sum over chains of each chain's own
+        autocorrelation function (StatsBase.autocor; emcee's walker-averaged f).  mhx.autocorrelation turns either into rho(k).  A
+        row with a non-finite draw among the chains read is NaN at every lag, its nvalid 0."""
+        return _autocovariance(self, L.lib().mhx_run_autocovariance, lags, params, chains, normalise)
 
     def _rows(self, params):
         return np.arange(self.dim + 1, dtype=np.int32) if params is None else np.ascontiguousarray(params, dtype=np.int32).reshape(-1)

@@ -206,6 +206,13 @@ class Group:
         from .api import _histogram2d
         return _histogram2d(self, L.lib().mhx_group_histogram2d, params, pairs, bins, range, edges)
 
+    def autocovariance(self, lags, params=None, normalise=False):
+        """Run.autocovariance over ALL chains of all members (mhx_group_autocovariance): sums over chains, so every member takes
+        those of its shard and the group adds acov and nvalid on the host, in member order.  It takes no chain range."""
+        from . import _lib as L
+        from .api import _autocovariance
+        return _autocovariance(self, L.lib().mhx_group_autocovariance, lags, params, False, normalise)
+
     def cross_moments(self, params=None, shift=None):
         """Run.cross_moments over the UNION of all members' draws (mhx_group_cross_moments): every member takes the moments of its
         shard about the same shift, and the group adds them in member order.  shift None: the mean of saved sample 0 over the chains

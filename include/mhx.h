@@ -88,6 +88,7 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *   summary         SELECT_BITS (digit width of a pass of mhx_*_order_statistics, 1..11; default 11; read at every call)
  *                   HPD_SCRATCH_MB (bound, in MiB, on the device scratch of a call of mhx_*_hpd: the rows go in batches that fit;
  *                   default 1024; a positive number, fractions allowed; read at every call)
+ *                   ACF_R (8 | 16 | 32 lags per tile of mhx_*_autocovariance; default: the fastest measured per width; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
  * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
@@ -787,6 +788,34 @@ int mhx_ctx_histogram2d(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, i
                         const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, const int32_t *pairs, int32_t npairs,
                         uint64_t *counts, uint64_t *outside);
 
+/* Autocovariance sums of the rows params[0..nparams) (indices into the dim+1 rows, lp = dim) at the lags lags[0..nlags) (strictly
+ * increasing, 0 <= lag < n_saved), over the chains [chain_begin, chain_begin + chain_count) (chain_count 0: to the last chain), from the
+ * [n_saved][dim+1][nchains] tensor in place.  With m_c = x_0 + sum_t (x_t - x_0) / N the chain's own mean
+ * (fp64) and A_c(k) = sum_{t < N-k} (x_t - m_c)(x_{t+k} - m_c):
+ *   normalise = 0   acov[i][j] = sum_c A_c(k_j): un-normalised, so the sums of shards (members of a group, ranks of a job) simply add;
+ *                   nvalid[i] (NULL: not wanted) = the chains with A_c(0) > 0
+ *   normalise = 1   acov[i][j] = sum_c A_c(k_j) / A_c(0) over the chains with A_c(0) > 0, nvalid[i] of them: the sum over chains of each
+ *                   chain's own autocorrelation function (StatsBase.autocor per chain; emcee's walker-averaged f times nvalid).  A
+ *                   chain that never moved is left out and counted out, never divided by zero; A_c(0) here is the fp64 sum of the
+ *                   squares about m_c, which is exactly 0 for such a chain.
+ * How the sums are accumulated (the tests' bounds are built from this): m_c is rounded once to the run's width; x - m_c, and the
+ * products, are taken and accumulated in that width by fused multiply-adds, at most 512 in a row per accumulator, which is then
+ * added to an fp64 partner; the draws go in time chunks of 1024, a chain's fp64 partial of a chunk is (normalise = 1: multiplied by
+ * 1 / A_c(0) and) added over the 64 chains of a wave in 6 shuffle steps, and ONE fp64 atomic per (lag, 64 chains, chunk) adds it to
+ * the result -- the order of those atomics is not fixed, so two calls may differ in the last bits.  The lags go in tiles of R
+ * consecutive lags (a register window of the series; R per width, option ACF_R = 8 | 16 | 32 overrides it); a sparse list launches
+ * only the tiles that hold a listed lag.
+ * A row with a non-finite draw among the chains read is NaN at every lag, its nvalid 0; no other row changes.
+ * MHX_EINVAL: acov NULL, a parameter outside [0, dim], no lags, a lag outside [0, n_saved) or not above its predecessor (the message
+ * names the entry), a chain range outside [0, nchains); MHX_ESTATE: no device sample tensor, or fewer than 2 saved draws.  Nothing is
+ * written unless the call succeeds.  Blocking. */
+int mhx_run_autocovariance(mhx_run *run, const int32_t *params, int32_t nparams, const int32_t *lags, int32_t nlags,
+                           int64_t chain_begin, int64_t chain_count, int32_t normalise, double *acov, int64_t *nvalid);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics) */
+int mhx_ctx_autocovariance(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                           const int32_t *params, int32_t nparams, const int32_t *lags, int32_t nlags,
+                           int64_t chain_begin, int64_t chain_count, int32_t normalise, double *acov, int64_t *nvalid);
+
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
  * (README.md:135-148: one task per chain) -- here one host thread per GPU behind the ABI.  A group is N member contexts (one
@@ -836,6 +865,10 @@ int mhx_group_histogram(mhx_group *g, const int32_t *params, int32_t nparams, co
                         uint64_t *outside);
 int mhx_group_histogram2d(mhx_group *g, const int32_t *params, int32_t nparams, const double *edges, int32_t nbins, const int32_t *pairs,
                           int32_t npairs, uint64_t *counts, uint64_t *outside);
+/* mhx_run_autocovariance over all chains of all members: the sums are sums over chains, so the members take their shards
+ * concurrently and the group adds acov and nvalid on the host, in member order (a row NaN in one member: NaN, nvalid 0) */
+int mhx_group_autocovariance(mhx_group *g, const int32_t *params, int32_t nparams, const int32_t *lags, int32_t nlags,
+                             int32_t normalise, double *acov, int64_t *nvalid);
 
 #ifdef __cplusplus
 }
