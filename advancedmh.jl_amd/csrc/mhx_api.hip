@@ -246,14 +246,16 @@ struct mhx_ctx : mhx_handle_hdr {
     mhx_compact_hdr* hdr_pinned = nullptr;
     mhx_expander* expander = nullptr;
     int expander_threads = 0, expander_chunk = 0, expander_numa = -1;   // the options / memory node the expander was created with
-    void* select_scratch = nullptr;                 // histograms, prefixes and group counts of the order-statistics passes (grown on demand)
-    size_t select_bytes = 0;
-    uint64_t* select_landing = nullptr;             // ... and their page-locked landing place on the host (grown on demand)
+    // three scratch blocks of the post-run statistics, each grown on demand by scratch_carve and kept until the context closes
+    // (DESIGN.md section 6.5).  A block belongs to one call at a time: whoever carves it owns all of it until that call returns.
+    void* select_scratch = nullptr;                 // the sweeps that return counters or sums: a select pass (also the one inside HPD), the
+    size_t select_bytes = 0;                        // histograms, the autocovariance
+    uint64_t* select_landing = nullptr;             // the select's page-locked landing place on the host (grown on demand)
     size_t select_landing_words = 0;
-    void* cross_scratch = nullptr;                  // partial tiles, tables and results of the cross moments (grown on demand)
+    void* cross_scratch = nullptr;                  // the cross moments alone: partial tiles, tables and results
     size_t cross_bytes = 0;
-    void* hpd_scratch = nullptr;                    // tail keys, their sort and the partial minima of the HPD intervals (grown on demand, bounded by HPD_SCRATCH_MB)
-    size_t hpd_bytes = 0;
+    void* hpd_scratch = nullptr;                    // HPD alone, held across its select passes: tail keys, their sort, the partial minima
+    size_t hpd_bytes = 0;                           // (bounded by HPD_SCRATCH_MB)
     ~mhx_ctx()
     {
         if (hpd_scratch) (void)hipFree(hpd_scratch);
@@ -1723,12 +1725,14 @@ static void schedule_counts(const mhx_schedule* s, uint64_t* n_transitions, uint
     *n_adapt = (uint64_t)(dfw + (k >= 2 ? (k - 1) * th : 0));
 }
 
-static int ensure_buffer(void** p, size_t* cap, size_t need)
+// a device buffer that only grows: kept (never shrunk) until its owner closes, replaced -- its contents lost -- by a call that needs
+// more.  who: the entry point, what: what the bytes are, for the message
+static int ensure_buffer(void** p, size_t* cap, size_t need, const char* who, const char* what)
 {
     if (*cap >= need && *p) return MHX_OK;
     if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
     hipError_t e = hipMalloc(p, need);
-    if (e != hipSuccess) return mhx_fail(MHX_ENOMEM, "sample buffer of %zu bytes: %s", need, hipGetErrorString(e));
+    if (e != hipSuccess) { *p = nullptr; return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of %s: %s", who, need, what, hipGetErrorString(e)); }
     *cap = need;
     return MHX_OK;
 }
@@ -1805,9 +1809,9 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
             if (rcj) return rcj;
         }
         const size_t bytes = ((size_t)r->dim + 1) * (size_t)r->n * sizeof(mhx_real);
-        int rc = ensure_buffer((void**)&r->d_mom_mean, &r->mom_cap, bytes);
+        int rc = ensure_buffer((void**)&r->d_mom_mean, &r->mom_cap, bytes, "mhx_run_sample", "running-moment buffer");
         if (rc) return rc;
-        rc = ensure_buffer((void**)&r->d_mom_m2, &r->mom_cap2, bytes);
+        rc = ensure_buffer((void**)&r->d_mom_m2, &r->mom_cap2, bytes, "mhx_run_sample", "running-moment buffer");
         if (rc) return rc;
         r->moments_mode = true;
         r->mom_n = 0;
@@ -1824,9 +1828,9 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
         }
     } else if (save_samples) {
         const size_t N = (size_t)s->n_samples, n = (size_t)r->n, d1 = (size_t)r->dim + 1;
-        int rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, N * d1 * n * sizeof(mhx_real));
+        int rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, N * d1 * n * sizeof(mhx_real), "mhx_run_sample", "sample buffer");
         if (rc) return rc;
-        rc = ensure_buffer((void**)&r->d_accepted, &r->accepted_cap, N * n);
+        rc = ensure_buffer((void**)&r->d_accepted, &r->accepted_cap, N * n, "mhx_run_sample", "accept-flag buffer");
         if (rc) return rc;
         r->n_saved = s->n_samples;
         if (r->kind == RUN_RAM) { rc = ram_prepare_step_stats(r, s, nA); if (rc) return rc; }
@@ -2102,6 +2106,83 @@ int api_run_destroy(mhx_run* r)
 #include "mhx_api_emcee.inc"
 #include "mhx_api_ram.inc"
 #include "mhx_api_mala.inc"
+
+// ---- what the post-run statistics share (the five .inc files below) ----
+// The draws a statistic reads: a tensor [N][d1][C] on ctx's device, and the entry point's name for its messages.
+struct draws_view {
+    mhx_ctx* ctx;
+    const mhx_real* tensor;
+    long N, C;
+    int d1;
+    const char* who;
+    unsigned long long S() const { return (unsigned long long)N * (unsigned long long)C; }      // draws of a row
+};
+
+// ... a caller's tensor (the mhx_ctx_* forms)
+static int draws_of_ctx(const char* who, mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, draws_view* v)
+{
+    if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
+    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
+    *v = draws_view{ctx, d_tensor, (long)n_samples, (long)nchains, dim1, who};
+    return MHX_OK;
+}
+
+// ... the sample buffer of a run (the mhx_run_* forms)
+static int draws_of_run(const char* who, const mhx_run* r, draws_view* v)
+{
+    if (!r) return mhx_fail(MHX_EINVAL, "%s: run is NULL", who);
+    if (r->moments_mode || r->n_saved < 1 || !r->d_samples)
+        return mhx_fail(MHX_ESTATE, "%s: the run holds no device sample tensor (moments mode, save_samples = 0 or a host-streamed run)", who);
+    *v = draws_view{r->ctx, r->d_samples, (long)r->n_saved, (long)r->n, r->dim + 1, who};
+    return MHX_OK;
+}
+
+// The pieces of a scratch block, listed ONCE by the call that uses it: scratch_carve runs the list twice, first to add up the bytes,
+// then -- the block grown to hold them -- to hand out the pointers.  Every piece starts on a 256-byte line.
+struct scratch_pieces {
+    char* base;                                     // NULL: the sizing run
+    size_t bytes = 0;
+    template <class T> T* take(size_t count)
+    {
+        T* p = base ? (T*)(base + bytes) : nullptr;
+        bytes += (count * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+template <class List>
+static int scratch_carve(void** block, size_t* cap, const char* who, const char* what, List&& list)
+{
+    scratch_pieces sizing{nullptr};
+    list(sizing);
+    int rc = ensure_buffer(block, cap, sizing.bytes, who, what);
+    if (rc) return rc;
+    scratch_pieces placing{(char*)*block};
+    list(placing);
+    return MHX_OK;
+}
+
+// The grid of a sweep over the S draws of each of `rows` rows (k_select_hist, k_hpd_gather, k_hist1d / 2d): enough blocks for the whole
+// chip, chunks of at least one unrolled block sweep and below 2^31 draws
+static unsigned long long sweep_blocks(unsigned long long S, int rows, unsigned long long* chunk)
+{
+    const unsigned long long sweep = (unsigned long long)MHX_SELECT_THREADS * MHX_SELECT_UNROLL;
+    unsigned long long nblk = std::min<unsigned long long>((2048 + rows - 1) / rows, (S + sweep - 1) / sweep);
+    nblk = std::max<unsigned long long>(std::max<unsigned long long>(nblk, 1), (S + (1ull << 31) - 1) >> 31);
+    *chunk = (S + nblk - 1) / nblk;
+    return nblk;
+}
+
+// device memory of one call, freed however the call returns
+template <class T>
+struct dev_array {
+    T* p = nullptr;
+    dev_array() = default;
+    dev_array(const dev_array&) = delete;
+    dev_array& operator=(const dev_array&) = delete;
+    ~dev_array() { if (p) (void)hipFree(p); }
+    bool alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)) == hipSuccess; }
+};
+
 #include "mhx_api_diag.inc"
 #include "mhx_api_moments.inc"
 #include "mhx_api_hpd.inc"

@@ -1,5 +1,5 @@
-// autocovariance sums host side (included by mhx_api.hip after mhx_api_hist.inc): the checks, the tile list, two launches per call,
-// the sums back in one copy (mhx_acf_kernels.h, DESIGN.md section 6.5.4)
+// autocovariance sums host side (included by mhx_api.hip after mhx_api_hist.inc): the checks, the tile list, two launches per call on
+// the context's select block, the sums back in one copy (mhx_acf_kernels.h, DESIGN.md section 6.5.4)
 
 __global__ void __launch_bounds__(256)
 k_acf_centre(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const int* __restrict__ params, const int P,
@@ -24,12 +24,14 @@ k_acf_tile(const mhx_real* __restrict__ samples, const long N, const int d1, con
 #define MHX_ACF_R 8
 #endif
 
-static int acf_check(const char* who, const int32_t* params, int32_t nparams, int d1, const int32_t* lags, int32_t nlags, int64_t N,
-                     int64_t C, int64_t chain_begin, int64_t chain_count, const double* acov)
+static int acf_check(const draws_view& v, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin,
+                     int64_t chain_count, const double* acov)
 {
+    const char* who = v.who;
+    const int64_t N = v.N, C = v.C;
     if (!acov) return mhx_fail(MHX_EINVAL, "%s: acov is NULL", who);
     if (N < 2) return mhx_fail(MHX_ESTATE, "%s: %lld draws per chain, an autocovariance needs at least 2", who, (long long)N);
-    int rc = select_check_params(who, params, nparams, d1);
+    int rc = select_check_params(who, params, nparams, v.d1);
     if (rc) return rc;
     if (nparams > MHX_HIST_MAX_ROWS) return mhx_fail(MHX_EINVAL, "%s: %d rows in one call, at most %d", who, (int)nparams, MHX_HIST_MAX_ROWS);
     if (!lags || nlags <= 0) return mhx_fail(MHX_EINVAL, "%s: no lags", who);
@@ -46,10 +48,15 @@ static int acf_check(const char* who, const int32_t* params, int32_t nparams, in
     return MHX_OK;
 }
 
-// the arguments are checked; tensor [N][d1][C] on the context's device.  The caller's arrays are written last, after everything succeeded.
-static int acf_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, long N, int d1, long C, const int32_t* params, int P,
-                       const int32_t* lags, int nlags, long c0, long nc, int normalise, double* acov, int64_t* nvalid)
+// the arguments are checked.  The caller's arrays are written last, after everything succeeded.
+static int acf_compute(const draws_view& v, const int32_t* params, int P, const int32_t* lags, int nlags, long c0, long nc, int normalise,
+                       double* acov, int64_t* nvalid)
 {
+    mhx_ctx* ctx = v.ctx;
+    const char* who = v.who;
+    const mhx_real* tensor = v.tensor;
+    const long N = v.N, C = v.C;
+    const int d1 = v.d1;
     HIP_TRY(hipSetDevice(ctx->device));
     if (nc == 0) nc = C - c0;
     int R = opt_int(ctx, "ACF_R", MHX_ACF_R);
@@ -68,21 +75,18 @@ static int acf_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
     const long chunks = (N + MHX_ACF_CHUNK - 1) / MHX_ACF_CHUNK;
     if ((double)ncb * (double)ngroups * (double)P > 2147483647.0)
         return mhx_fail(MHX_EINVAL, "%s: %ld chain blocks x %ld tile groups x %d rows exceed one launch: ask for fewer lags or rows per call", who, ncb, ngroups, P);
-    // scratch of the context (the select's, grown on demand): sums | counters | means | lag-0 sums | rows | tiles
     const size_t npc = (size_t)P * (size_t)nc;
-    const size_t bytes = (nout + 2 * (size_t)P + 2 * npc) * sizeof(double) + ((size_t)P + ntiles) * sizeof(int32_t);
-    if (bytes > ctx->select_bytes) {
-        if (ctx->select_scratch) (void)hipFree(ctx->select_scratch);
-        ctx->select_scratch = nullptr; ctx->select_bytes = 0;
-        if (hipMalloc(&ctx->select_scratch, bytes) != hipSuccess) return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of autocovariance scratch", who, bytes);
-        ctx->select_bytes = bytes;
-    }
-    double* d_out = (double*)ctx->select_scratch;
+    double *d_out = nullptr, *d_mean = nullptr, *d_ss = nullptr;
+    int *d_par = nullptr, *d_tiles = nullptr;
+    int rc = scratch_carve(&ctx->select_scratch, &ctx->select_bytes, who, "autocovariance scratch", [&](scratch_pieces& c) {
+        d_out = c.take<double>(nout + 2 * (size_t)P);       // sums, then 2 P counters of the same size: one memset, one copy back
+        d_mean = c.take<double>(npc);
+        d_ss = c.take<double>(npc);                         // lag-0 sums
+        d_par = c.take<int>(P);
+        d_tiles = c.take<int>(ntiles);
+    });
+    if (rc) return rc;
     unsigned long long* d_cnt = (unsigned long long*)(d_out + nout);
-    double* d_mean = (double*)(d_cnt + 2 * (size_t)P);
-    double* d_ss = d_mean + npc;
-    int* d_par = (int*)(d_ss + npc);
-    int* d_tiles = d_par + P;
     HIP_TRY(hipMemsetAsync(d_out, 0, (nout + 2 * (size_t)P) * sizeof(double), ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_par, params, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_tiles, tiles.data(), ntiles * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -111,26 +115,27 @@ static int acf_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
     return MHX_OK;
 }
 
+// v is checked, nothing else is
+static int acf_checked(const draws_view& v, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin,
+                       int64_t chain_count, int32_t normalise, double* acov, int64_t* nvalid)
+{
+    int rc = acf_check(v, params, nparams, lags, nlags, chain_begin, chain_count, acov);
+    return rc ? rc : acf_compute(v, params, nparams, lags, nlags, (long)chain_begin, (long)chain_count, normalise, acov, nvalid);
+}
+
 int api_ctx_autocovariance(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
                            int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin, int64_t chain_count, int32_t normalise,
                            double* acov, int64_t* nvalid)
 {
-    const char* who = "mhx_ctx_autocovariance";
-    if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
-    int rc = acf_check(who, params, nparams, dim1, lags, nlags, n_samples, nchains, chain_begin, chain_count, acov);
-    if (rc) return rc;
-    return acf_compute(ctx, who, d_tensor, (long)n_samples, dim1, (long)nchains, params, nparams, lags, nlags, (long)chain_begin, (long)chain_count,
-                       normalise, acov, nvalid);
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_autocovariance", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : acf_checked(v, params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid);
 }
 
 int api_run_autocovariance(mhx_run* r, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags, int64_t chain_begin,
                            int64_t chain_count, int32_t normalise, double* acov, int64_t* nvalid)
 {
-    const char* who = "mhx_run_autocovariance";
-    int rc = select_need_tensor(r, who);
-    if (rc) return rc;
-    if ((rc = acf_check(who, params, nparams, r->dim + 1, lags, nlags, r->n_saved, r->n, chain_begin, chain_count, acov))) return rc;
-    return acf_compute(r->ctx, who, r->d_samples, (long)r->n_saved, r->dim + 1, (long)r->n, params, nparams, lags, nlags, (long)chain_begin,
-                       (long)chain_count, normalise, acov, nvalid);
+    draws_view v;
+    int rc = draws_of_run("mhx_run_autocovariance", r, &v);
+    return rc ? rc : acf_checked(v, params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid);
 }

@@ -1,5 +1,5 @@
-// histograms and pair histograms host side (included by mhx_api.hip after mhx_api_hpd.inc): the checks, one launch per call, the
-// counters back in one copy (mhx_hist_kernels.h, DESIGN.md section 6.5.3)
+// histograms and pair histograms host side (included by mhx_api.hip after mhx_api_hpd.inc): the checks, one launch per call on the
+// context's select block, the counters back in one copy (mhx_hist_kernels.h, DESIGN.md section 6.5.3)
 
 __global__ void __launch_bounds__(MHX_SELECT_THREADS)
 k_hist1d(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const int* __restrict__ params,
@@ -24,11 +24,12 @@ k_hist2d(const mhx_real* __restrict__ samples, const long N, const int d1, const
 
 #define MHX_HIST_MAX_ROWS 65535                             // rows (pairs) of a call: the grid's second dimension
 
-static int hist_check(const char* who, const int32_t* params, int32_t nparams, int d1, const double* edges, int32_t nbins, int32_t limit,
+static int hist_check(const draws_view& v, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, int32_t limit,
                       const uint64_t* counts)
 {
+    const char* who = v.who;
     if (!edges || !counts) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    int rc = select_check_params(who, params, nparams, d1);
+    int rc = select_check_params(who, params, nparams, v.d1);
     if (rc) return rc;
     if (nparams > MHX_HIST_MAX_ROWS) return mhx_fail(MHX_EINVAL, "%s: %d rows in one call, at most %d", who, (int)nparams, MHX_HIST_MAX_ROWS);
     if (nbins < 1 || nbins > limit) return mhx_fail(MHX_EINVAL, "%s: nbins = %d is not in [1, %d]", who, (int)nbins, (int)limit);
@@ -52,44 +53,37 @@ static int hist_check_pairs(const char* who, const int32_t* pairs, int32_t npair
     return MHX_OK;
 }
 
-// the sweep's geometry is the select's: enough blocks for the whole chip, chunks of at least one unrolled block sweep, below 2^31 draws
-static unsigned long long hist_blocks(unsigned long long S, int rows, unsigned long long* chunk)
+// the arguments are checked.  pairs NULL: the 1-D form (counts [P][B], outside [P][3]), else counts [Q][B][B] and outside [Q].  The
+// caller's arrays are written last, after everything succeeded.
+static int hist_compute(const draws_view& v, const int32_t* params, int P, const double* edges, int B, const int32_t* pairs, int Q,
+                        uint64_t* counts, uint64_t* outside)
 {
-    const unsigned long long sweep = (unsigned long long)MHX_SELECT_THREADS * MHX_SELECT_UNROLL;
-    unsigned long long nblk = std::min<unsigned long long>((2048 + rows - 1) / rows, (S + sweep - 1) / sweep);
-    nblk = std::max<unsigned long long>(std::max<unsigned long long>(nblk, 1), (S + (1ull << 31) - 1) >> 31);
-    *chunk = (S + nblk - 1) / nblk;
-    return nblk;
-}
-
-// the arguments are checked; tensor [N][d1][C] on the context's device.  pairs NULL: the 1-D form (counts [P][B], outside [P][3]), else
-// counts [Q][B][B] and outside [Q].  The caller's arrays are written last, after everything succeeded.
-static int hist_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, long N, int d1, long C, const int32_t* params, int P,
-                        const double* edges, int B, const int32_t* pairs, int Q, uint64_t* counts, uint64_t* outside)
-{
+    mhx_ctx* ctx = v.ctx;
+    const char* who = v.who;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t ncount = pairs ? (size_t)Q * B * B : (size_t)P * B, nout = pairs ? (size_t)Q : (size_t)P * 3;
-    const size_t nedge = (size_t)P * (B + 1), nidx = (size_t)P + (pairs ? 2 * (size_t)Q : 0);
-    // scratch of the context (the select's, grown on demand): counters | outside | edges | rows | pairs
-    const size_t bytes = (ncount + nout) * sizeof(uint64_t) + nedge * sizeof(double) + nidx * sizeof(int32_t);
-    if (bytes > ctx->select_bytes) {
-        if (ctx->select_scratch) (void)hipFree(ctx->select_scratch);
-        ctx->select_scratch = nullptr; ctx->select_bytes = 0;
-        if (hipMalloc(&ctx->select_scratch, bytes) != hipSuccess) return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of histogram scratch", who, bytes);
-        ctx->select_bytes = bytes;
-    }
-    unsigned long long* d_counts = (unsigned long long*)ctx->select_scratch;
+    const size_t nedge = (size_t)P * (B + 1);
+    unsigned long long* d_counts = nullptr;
+    double* d_edges = nullptr;
+    int *d_par = nullptr, *d_pairs = nullptr;
+    int rc = scratch_carve(&ctx->select_scratch, &ctx->select_bytes, who, "histogram scratch", [&](scratch_pieces& c) {
+        d_counts = c.take<unsigned long long>(ncount + nout);          // counters, then outside: one memset, one copy back
+        d_edges = c.take<double>(nedge);
+        d_par = c.take<int>(P);
+        d_pairs = c.take<int>(pairs ? 2 * (size_t)Q : 0);
+    });
+    if (rc) return rc;
     unsigned long long* d_out = d_counts + ncount;
-    double* d_edges = (double*)(d_out + nout);
-    int* d_par = (int*)(d_edges + nedge);
-    int* d_pairs = d_par + P;
     HIP_TRY(hipMemsetAsync(d_counts, 0, (ncount + nout) * sizeof(uint64_t), ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_edges, edges, nedge * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_par, params, (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if (pairs) HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 2 * (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const unsigned long long S = (unsigned long long)N * (unsigned long long)C;
+    const mhx_real* tensor = v.tensor;
+    const long N = v.N, C = v.C;
+    const int d1 = v.d1;
+    const unsigned long long S = v.S();
     unsigned long long chunk = 0;
-    const unsigned long long nblk = hist_blocks(S, pairs ? Q : P, &chunk);
+    const unsigned long long nblk = sweep_blocks(S, pairs ? Q : P, &chunk);
     const dim3 grid((unsigned)nblk, (unsigned)(pairs ? Q : P)), block(MHX_SELECT_THREADS);
     if (!pairs)
         hipLaunchKernelGGL(k_hist1d, grid, block, 0, ctx->stream, tensor, N, d1, C, d_par, d_edges, B, chunk, d_counts, d_out);
@@ -116,54 +110,50 @@ static int hist_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, l
     return MHX_OK;
 }
 
-static int hist_check_tensor(const char* who, const mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains)
+// v is checked, nothing else is
+static int hist_checked(const draws_view& v, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts,
+                        uint64_t* outside)
 {
-    if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
-    return MHX_OK;
+    int rc = hist_check(v, params, nparams, edges, nbins, MHX_HIST_MAX_BINS, counts);
+    return rc ? rc : hist_compute(v, params, nparams, edges, nbins, nullptr, 0, counts, outside);
+}
+static int hist2d_checked(const draws_view& v, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins,
+                          const int32_t* pairs, int32_t npairs, uint64_t* counts, uint64_t* outside)
+{
+    int rc = hist_check(v, params, nparams, edges, nbins, MHX_HIST2D_MAX_BINS, counts);
+    if (!rc) rc = hist_check_pairs(v.who, pairs, npairs, nparams);
+    return rc ? rc : hist_compute(v, params, nparams, edges, nbins, pairs, npairs, counts, outside);
 }
 
 int api_ctx_histogram(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
                       int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts, uint64_t* outside)
 {
-    const char* who = "mhx_ctx_histogram";
-    int rc = hist_check_tensor(who, ctx, d_tensor, n_samples, dim1, nchains);
-    if (rc) return rc;
-    if ((rc = hist_check(who, params, nparams, dim1, edges, nbins, MHX_HIST_MAX_BINS, counts))) return rc;
-    return hist_compute(ctx, who, d_tensor, (long)n_samples, dim1, (long)nchains, params, nparams, edges, nbins, nullptr, 0, counts, outside);
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_histogram", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : hist_checked(v, params, nparams, edges, nbins, counts, outside);
 }
 
 int api_run_histogram(mhx_run* r, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, uint64_t* counts,
                       uint64_t* outside)
 {
-    const char* who = "mhx_run_histogram";
-    int rc = select_need_tensor(r, who);
-    if (rc) return rc;
-    if ((rc = hist_check(who, params, nparams, r->dim + 1, edges, nbins, MHX_HIST_MAX_BINS, counts))) return rc;
-    return hist_compute(r->ctx, who, r->d_samples, (long)r->n_saved, r->dim + 1, (long)r->n, params, nparams, edges, nbins, nullptr, 0, counts,
-                        outside);
+    draws_view v;
+    int rc = draws_of_run("mhx_run_histogram", r, &v);
+    return rc ? rc : hist_checked(v, params, nparams, edges, nbins, counts, outside);
 }
 
 int api_ctx_histogram2d(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
                         int32_t nparams, const double* edges, int32_t nbins, const int32_t* pairs, int32_t npairs, uint64_t* counts,
                         uint64_t* outside)
 {
-    const char* who = "mhx_ctx_histogram2d";
-    int rc = hist_check_tensor(who, ctx, d_tensor, n_samples, dim1, nchains);
-    if (rc) return rc;
-    if ((rc = hist_check(who, params, nparams, dim1, edges, nbins, MHX_HIST2D_MAX_BINS, counts))) return rc;
-    if ((rc = hist_check_pairs(who, pairs, npairs, nparams))) return rc;
-    return hist_compute(ctx, who, d_tensor, (long)n_samples, dim1, (long)nchains, params, nparams, edges, nbins, pairs, npairs, counts, outside);
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_histogram2d", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : hist2d_checked(v, params, nparams, edges, nbins, pairs, npairs, counts, outside);
 }
 
 int api_run_histogram2d(mhx_run* r, const int32_t* params, int32_t nparams, const double* edges, int32_t nbins, const int32_t* pairs,
                         int32_t npairs, uint64_t* counts, uint64_t* outside)
 {
-    const char* who = "mhx_run_histogram2d";
-    int rc = select_need_tensor(r, who);
-    if (rc) return rc;
-    if ((rc = hist_check(who, params, nparams, r->dim + 1, edges, nbins, MHX_HIST2D_MAX_BINS, counts))) return rc;
-    if ((rc = hist_check_pairs(who, pairs, npairs, nparams))) return rc;
-    return hist_compute(r->ctx, who, r->d_samples, (long)r->n_saved, r->dim + 1, (long)r->n, params, nparams, edges, nbins, pairs, npairs,
-                        counts, outside);
+    draws_view v;
+    int rc = draws_of_run("mhx_run_histogram2d", r, &v);
+    return rc ? rc : hist2d_checked(v, params, nparams, edges, nbins, pairs, npairs, counts, outside);
 }

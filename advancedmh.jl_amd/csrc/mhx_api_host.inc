@@ -265,9 +265,9 @@ int api_run_sample_to_host(mhx_run* r, const mhx_schedule* s, mhx_real* host_sam
     }
     const size_t nslab = ring ? 2 : (N + K - 1) / K;
     const size_t dev_samples = ring ? 2 * K : N;
-    rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, dev_samples * rec);
+    rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, dev_samples * rec, "mhx_run_sample_to_host", "sample buffer");
     if (rc) return rc;
-    rc = ensure_buffer((void**)&r->d_accepted, &r->accepted_cap, dev_samples * n);
+    rc = ensure_buffer((void**)&r->d_accepted, &r->accepted_cap, dev_samples * n, "mhx_run_sample_to_host", "accept-flag buffer");
     if (rc) return rc;
     host_pin_guard pins(ctx);
     bool mine = false;

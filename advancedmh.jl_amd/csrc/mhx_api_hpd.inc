@@ -1,5 +1,6 @@
-// HPD intervals host side (included by mhx_api.hip after mhx_api_diag.inc): thresholds by the radix select, one gather sweep, a sort
-// of the tails only, the first minimum width (mhx_hpd_kernels.h, DESIGN.md section 6.5.2)
+// HPD intervals host side (included by mhx_api.hip after mhx_api_diag.inc): thresholds by the radix select (on the context's select
+// block), then on the context's HPD block one gather sweep, a sort of the tails only, the first minimum width (mhx_hpd_kernels.h,
+// DESIGN.md section 6.5.2)
 
 __global__ void __launch_bounds__(MHX_SELECT_THREADS)
 k_hpd_gather(const mhx_real* __restrict__ samples, const long N, const int d1, const long C, const int* __restrict__ params,
@@ -41,14 +42,15 @@ static unsigned long long hpd_key_of(const double v)
 #endif
 }
 
-static size_t hpd_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+static size_t hpd_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }      // (a piece of scratch_carve)
 
-// the arguments are checked; tensor [N][d1][C] on the context's device.  lower / upper are written last, after everything succeeded.
-static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, long N, int d1, long C, const int32_t* params, int P,
-                       double alpha, double* lower, double* upper)
+// the arguments are checked.  lower / upper are written last, after everything succeeded.
+static int hpd_compute(const draws_view& v, const int32_t* params, int P, double alpha, double* lower, double* upper)
 {
+    mhx_ctx* ctx = v.ctx;
+    const char* who = v.who;
     HIP_TRY(hipSetDevice(ctx->device));
-    const unsigned long long S = (unsigned long long)N * (unsigned long long)C;
+    const unsigned long long S = v.S();
     const double am = std::ceil(alpha * (double)S);
     const unsigned long long m = am < 1.0 ? 1ull : (unsigned long long)(int64_t)am;      // alpha < 1: m <= S
     const unsigned long long cap = m - 1;                   // keys a tail buffer holds: the draws strictly beyond a threshold
@@ -57,8 +59,8 @@ static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
         budget_mb = atof(v);
         if (!(budget_mb > 0.0) || !std::isfinite(budget_mb)) return mhx_fail(MHX_EINVAL, "%s: option HPD_SCRATCH_MB = '%s' is not a positive number", who, v);
     }
-    // the scratch plan, before any sweep: a batch of R rows holds tails | sorted tails (R x 2 x cap keys each) | sort space | counters |
-    // thresholds | rows | partial minima | results | tensor rows; a single row that does not fit the budget is refused here
+    // the scratch plan, before any sweep: row_bytes is what a row adds to the pieces carved below, each on its own 256-byte line; a single
+    // row that does not fit the budget is refused here
     size_t sort_bytes = 0, part_cap = 0;
     int Rmax = 0;
     if (cap > 0) {
@@ -79,7 +81,7 @@ static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
     // thresholds and the NaN check: ranks {m - 1, S - m, S - 1} of every row in one batch of the select
     const int64_t ranks[3] = {(int64_t)(m - 1), (int64_t)(S - m), (int64_t)(S - 1)};
     std::vector<double> os((size_t)P * 3);
-    select_source src{ctx, tensor, N, C, d1, params, P, who};
+    select_source src{v, params, P};
     const int digit = opt_int(ctx, "SELECT_BITS", MHX_SELECT_DIGIT_BITS);
     select_landing(ctx, digit, P, 3);
     int rc = mhx_select_drive(who, MHX_KEY_BITS, digit, P, ranks, 3, S, select_hist_pass, &src, os.data(), ctx->select_landing,
@@ -98,32 +100,26 @@ static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
     }
     if (cap > 0) {                                          // m = 1: one candidate, [y[0], y[S-1]], which the select gave
         const size_t n_tail = (size_t)Rmax * 2 * (size_t)cap;
-        const size_t o_sorted = hpd_align(n_tail * sizeof(mhx_key)), o_sort = o_sorted + hpd_align(n_tail * sizeof(mhx_key));
-        const size_t o_count = o_sort + sort_bytes, o_keyL = o_count + hpd_align((size_t)Rmax * 2 * MHX_HPD_COUNT_STRIDE * sizeof(uint64_t));
-        const size_t o_keyU = o_keyL + hpd_align((size_t)Rmax * sizeof(uint64_t)), o_rows = o_keyU + hpd_align((size_t)Rmax * sizeof(uint64_t));
-        const size_t o_pw = o_rows + hpd_align((size_t)Rmax * sizeof(mhx_hpd_row)), o_pi = o_pw + hpd_align((size_t)Rmax * part_cap * sizeof(double));
-        const size_t o_out = o_pi + hpd_align((size_t)Rmax * part_cap * sizeof(uint64_t)), o_par = o_out + hpd_align((size_t)Rmax * 2 * sizeof(double));
-        const size_t bytes = o_par + hpd_align((size_t)Rmax * sizeof(int32_t));
-        if (bytes > ctx->hpd_bytes) {
-            if (ctx->hpd_scratch) (void)hipFree(ctx->hpd_scratch);
-            ctx->hpd_scratch = nullptr; ctx->hpd_bytes = 0;
-            if (hipMalloc(&ctx->hpd_scratch, bytes) != hipSuccess) return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of tail scratch", who, bytes);
-            ctx->hpd_bytes = bytes;
-        }
-        char* base = (char*)ctx->hpd_scratch;
-        mhx_key* d_tails = (mhx_key*)base;
-        mhx_key* d_sorted = (mhx_key*)(base + o_sorted);
-        void* d_sort = base + o_sort;
-        unsigned long long* d_count = (unsigned long long*)(base + o_count);
-        unsigned long long* d_keyL = (unsigned long long*)(base + o_keyL);
-        unsigned long long* d_keyU = (unsigned long long*)(base + o_keyU);
-        mhx_hpd_row* d_rows = (mhx_hpd_row*)(base + o_rows);
-        double* d_pw = (double*)(base + o_pw);
-        unsigned long long* d_pi = (unsigned long long*)(base + o_pi);
-        double* d_out = (double*)(base + o_out);
-        int* d_par = (int*)(base + o_par);
-        // the gather's geometry is the select's: enough blocks for the whole chip, chunks of at least one unrolled block sweep, below 2^31 draws
-        const unsigned long long sweep = (unsigned long long)MHX_SELECT_THREADS * MHX_SELECT_UNROLL;
+        mhx_key *d_tails = nullptr, *d_sorted = nullptr;
+        char* d_sort = nullptr;
+        unsigned long long *d_count = nullptr, *d_keyL = nullptr, *d_keyU = nullptr, *d_pi = nullptr;
+        mhx_hpd_row* d_rows = nullptr;
+        double *d_pw = nullptr, *d_out = nullptr;
+        int* d_par = nullptr;
+        rc = scratch_carve(&ctx->hpd_scratch, &ctx->hpd_bytes, who, "tail scratch", [&](scratch_pieces& c) {
+            d_tails = c.take<mhx_key>(n_tail);              // Rmax x 2 x cap keys beyond the thresholds
+            d_sorted = c.take<mhx_key>(n_tail);             // ... ascending
+            d_sort = c.take<char>(sort_bytes);              // sort space
+            d_count = c.take<unsigned long long>((size_t)Rmax * 2 * MHX_HPD_COUNT_STRIDE);
+            d_keyL = c.take<unsigned long long>(Rmax);      // thresholds
+            d_keyU = c.take<unsigned long long>(Rmax);
+            d_rows = c.take<mhx_hpd_row>(Rmax);
+            d_pw = c.take<double>((size_t)Rmax * part_cap); // partial minima
+            d_pi = c.take<unsigned long long>((size_t)Rmax * part_cap);
+            d_out = c.take<double>((size_t)Rmax * 2);       // results
+            d_par = c.take<int>(Rmax);                      // tensor rows
+        });
+        if (rc) return rc;
         std::vector<unsigned long long> hL((size_t)Rmax), hU((size_t)Rmax), hc((size_t)Rmax * 2), hcs((size_t)Rmax * 2 * MHX_HPD_COUNT_STRIDE);
         std::vector<mhx_hpd_row> hrows((size_t)Rmax);
         std::vector<double> hout((size_t)Rmax * 2);
@@ -141,11 +137,10 @@ static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
             HIP_TRY(hipMemcpyAsync(d_keyL, hL.data(), (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(d_keyU, hU.data(), (size_t)R * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipMemcpyAsync(d_par, params + r0, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-            unsigned long long nblk = std::min<unsigned long long>((2048 + R - 1) / R, (S + sweep - 1) / sweep);
-            nblk = std::max<unsigned long long>(std::max<unsigned long long>(nblk, 1), (S + (1ull << 31) - 1) >> 31);
-            const unsigned long long chunk = (S + nblk - 1) / nblk;
-            hipLaunchKernelGGL(k_hpd_gather, dim3((unsigned)nblk, (unsigned)R), dim3(MHX_SELECT_THREADS), 0, ctx->stream, tensor, N, d1, C,
-                               d_par, d_keyL, d_keyU, chunk, cap, d_count, d_tails);
+            unsigned long long chunk = 0;
+            const unsigned long long nblk = sweep_blocks(S, R, &chunk);
+            hipLaunchKernelGGL(k_hpd_gather, dim3((unsigned)nblk, (unsigned)R), dim3(MHX_SELECT_THREADS), 0, ctx->stream, v.tensor, v.N, v.d1,
+                               v.C, d_par, d_keyL, d_keyU, chunk, cap, d_count, d_tails);
             if (hipGetLastError() != hipSuccess) return mhx_fail(MHX_EHIP, "%s: k_hpd_gather failed to launch", who);
             HIP_TRY(hipMemcpyAsync(hcs.data(), d_count, (size_t)R * 2 * MHX_HPD_COUNT_STRIDE * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -195,29 +190,26 @@ static int hpd_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, lo
     return MHX_OK;
 }
 
-static int hpd_check(const char* who, const int32_t* params, int32_t nparams, int d1, double alpha, const double* lower, const double* upper)
+// v is checked, nothing else is
+static int hpd_checked(const draws_view& v, const int32_t* params, int32_t nparams, double alpha, double* lower, double* upper)
 {
-    if (!lower || !upper) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    if (!(alpha > 0.0 && alpha < 1.0)) return mhx_fail(MHX_EINVAL, "%s: alpha = %g is not in (0, 1)", who, alpha);
-    return select_check_params(who, params, nparams, d1);
+    if (!lower || !upper) return mhx_fail(MHX_EINVAL, "%s: bad argument", v.who);
+    if (!(alpha > 0.0 && alpha < 1.0)) return mhx_fail(MHX_EINVAL, "%s: alpha = %g is not in (0, 1)", v.who, alpha);
+    int rc = select_check_params(v.who, params, nparams, v.d1);
+    return rc ? rc : hpd_compute(v, params, nparams, alpha, lower, upper);
 }
 
 int api_ctx_hpd(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
                 int32_t nparams, double alpha, double* lower, double* upper)
 {
-    const char* who = "mhx_ctx_hpd";
-    if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
-    int rc = hpd_check(who, params, nparams, dim1, alpha, lower, upper);
-    if (rc) return rc;
-    return hpd_compute(ctx, who, d_tensor, (long)n_samples, dim1, (long)nchains, params, nparams, alpha, lower, upper);
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_hpd", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : hpd_checked(v, params, nparams, alpha, lower, upper);
 }
 
 int api_run_hpd(mhx_run* r, const int32_t* params, int32_t nparams, double alpha, double* lower, double* upper)
 {
-    const char* who = "mhx_run_hpd";
-    int rc = select_need_tensor(r, who);
-    if (rc) return rc;
-    if ((rc = hpd_check(who, params, nparams, r->dim + 1, alpha, lower, upper))) return rc;
-    return hpd_compute(r->ctx, who, r->d_samples, (long)r->n_saved, r->dim + 1, (long)r->n, params, nparams, alpha, lower, upper);
+    draws_view v;
+    int rc = draws_of_run("mhx_run_hpd", r, &v);
+    return rc ? rc : hpd_checked(v, params, nparams, alpha, lower, upper);
 }

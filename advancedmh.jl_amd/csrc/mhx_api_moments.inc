@@ -1,5 +1,5 @@
-// cross moments host side (included by mhx_api.hip): sum_k y_i and sum_k y_i y_j of chosen rows of a sample tensor on the fp64
-// matrix cores (mhx_cross_kernels.h, DESIGN.md section 6.5.1)
+// cross moments host side (included by mhx_api.hip after mhx_api_diag.inc): sum_k y_i and sum_k y_i y_j of chosen rows of the draws
+// on the fp64 matrix cores, on the context's cross block (mhx_cross_kernels.h, DESIGN.md section 6.5.1)
 
 template <int G, bool DIAG>
 __global__ void __launch_bounds__(64)
@@ -28,11 +28,12 @@ k_cross_reduce_sums(const double* __restrict__ psum, const int nsplit, const int
 
 #define MHX_CROSS_SCRATCH_BYTES ((size_t)64 << 20)          // bound on the partial tiles of a call: the splits of K shrink to fit
 
-static int cross_check(const char* who, const int32_t* params, int32_t nparams, int d1, const double* shift, const double* sum,
+static int cross_check(const draws_view& v, const int32_t* params, int32_t nparams, const double* shift, const double* sum,
                        const double* cross)
 {
+    const char* who = v.who;
     if (!sum || !cross) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    int rc = select_check_params(who, params, nparams, d1);
+    int rc = select_check_params(who, params, nparams, v.d1);
     if (rc) return rc;
     if (shift)
         for (int i = 0; i < nparams; ++i)
@@ -40,10 +41,14 @@ static int cross_check(const char* who, const int32_t* params, int32_t nparams, 
     return MHX_OK;
 }
 
-// the arguments are checked; tensor [N][d1][C] on the context's device
-static int cross_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, long N, int d1, long C, const int32_t* params, int m,
-                         const double* shift, double* sum, double* cross)
+// the arguments are checked
+static int cross_compute(const draws_view& v, const int32_t* params, int m, const double* shift, double* sum, double* cross)
 {
+    mhx_ctx* ctx = v.ctx;
+    const char* who = v.who;
+    const mhx_real* tensor = v.tensor;
+    const long N = v.N, C = v.C;
+    const int d1 = v.d1;
     HIP_TRY(hipSetDevice(ctx->device));
     const int T = (m + 15) / 16;
     const bool one = T <= MHX_CROSS_MAX_G;                  // one group: every tile pair in one wave
@@ -77,28 +82,22 @@ static int cross_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, 
     long nsplit = std::min<long>(total, std::max<long>(1, waves / std::max<long>(1, one ? 1 : ngroups)));
     nsplit = std::min<long>(nsplit, std::max<long>(1, (long)(MHX_CROSS_SCRATCH_BYTES / ((size_t)nslots * 256 * sizeof(double)))));
     nsplit = std::min<long>(nsplit, 65535);
-    // scratch of the context, grown on demand: partial tiles | partial sums | folded tiles | folded sums | cross | sum | rows' shifts |
-    // 32 zeros | rows | tiles
-    const size_t n_part = (size_t)nslots * nsplit * 256, n_psum = (size_t)ntiles * nsplit * 64, n_cross = (size_t)m * m;
-    const size_t n_ft = (size_t)nslots * 256, n_fs = (size_t)ntiles * 64;
-    const size_t n_dbl = n_part + n_psum + n_ft + n_fs + n_cross + (size_t)m + sh.size() + 32;
-    const size_t bytes = n_dbl * sizeof(double) + (rows.size() + tiles.size()) * sizeof(int);
-    if (bytes > ctx->cross_bytes) {
-        if (ctx->cross_scratch) (void)hipFree(ctx->cross_scratch);
-        ctx->cross_scratch = nullptr; ctx->cross_bytes = 0;
-        if (hipMalloc(&ctx->cross_scratch, bytes) != hipSuccess) return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of partial-tile scratch", who, bytes);
-        ctx->cross_bytes = bytes;
-    }
-    double* d_part = (double*)ctx->cross_scratch;
-    double* d_psum = d_part + n_part;
-    double* d_ft = d_psum + n_psum;
-    double* d_fs = d_ft + n_ft;
-    double* d_cross = d_fs + n_fs;
+    const size_t n_cross = (size_t)m * m;
+    double *d_part = nullptr, *d_psum = nullptr, *d_ft = nullptr, *d_fs = nullptr, *d_cross = nullptr, *d_sh = nullptr, *d_zero = nullptr;
+    int *d_rows = nullptr, *d_tiles = nullptr;
+    int rc = scratch_carve(&ctx->cross_scratch, &ctx->cross_bytes, who, "partial-tile scratch", [&](scratch_pieces& c) {
+        d_part = c.take<double>((size_t)nslots * nsplit * 256);        // partial tiles
+        d_psum = c.take<double>((size_t)ntiles * nsplit * 64);         // partial sums
+        d_ft = c.take<double>((size_t)nslots * 256);                   // folded tiles
+        d_fs = c.take<double>((size_t)ntiles * 64);                    // folded sums
+        d_cross = c.take<double>(n_cross + (size_t)m);                 // cross, then sum: one copy back
+        d_sh = c.take<double>(sh.size());                              // the rows' shifts
+        d_zero = c.take<double>(32);
+        d_rows = c.take<int>(rows.size());
+        d_tiles = c.take<int>(tiles.size());
+    });
+    if (rc) return rc;
     double* d_sum = d_cross + n_cross;
-    double* d_sh = d_sum + m;
-    double* d_zero = d_sh + sh.size();
-    int* d_rows = (int*)(d_zero + 32);
-    int* d_tiles = d_rows + rows.size();
     HIP_TRY(hipMemsetAsync(d_zero, 0, 32 * sizeof(double), ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_sh, sh.data(), sh.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -135,24 +134,26 @@ static int cross_compute(mhx_ctx* ctx, const char* who, const mhx_real* tensor, 
     return MHX_OK;
 }
 
+// v is checked, nothing else is
+static int cross_checked(const draws_view& v, const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
+{
+    int rc = cross_check(v, params, nparams, shift, sum, cross);
+    return rc ? rc : cross_compute(v, params, nparams, shift, sum, cross);
+}
+
 int api_ctx_cross_moments(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const int32_t* params,
                           int32_t nparams, const double* shift, double* sum, double* cross)
 {
-    const char* who = "mhx_ctx_cross_moments";
-    if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
-    if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
-    int rc = cross_check(who, params, nparams, dim1, shift, sum, cross);
-    if (rc) return rc;
-    return cross_compute(ctx, who, d_tensor, (long)n_samples, dim1, (long)nchains, params, nparams, shift, sum, cross);
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_cross_moments", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : cross_checked(v, params, nparams, shift, sum, cross);
 }
 
 int api_run_cross_moments(mhx_run* r, const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross, int64_t* n_draws)
 {
-    const char* who = "mhx_run_cross_moments";
-    int rc = select_need_tensor(r, who);
-    if (rc) return rc;
-    if ((rc = cross_check(who, params, nparams, r->dim + 1, shift, sum, cross))) return rc;
-    if ((rc = cross_compute(r->ctx, who, r->d_samples, (long)r->n_saved, r->dim + 1, (long)r->n, params, nparams, shift, sum, cross))) return rc;
-    if (n_draws) *n_draws = (int64_t)r->n_saved * (int64_t)r->n;
-    return MHX_OK;
+    draws_view v;
+    int rc = draws_of_run("mhx_run_cross_moments", r, &v);
+    if (!rc) rc = cross_checked(v, params, nparams, shift, sum, cross);
+    if (!rc && n_draws) *n_draws = (int64_t)v.S();
+    return rc;
 }

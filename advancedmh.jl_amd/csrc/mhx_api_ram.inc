@@ -391,7 +391,7 @@ static int ram_prepare_step_stats(mhx_run* r, const mhx_schedule* s, uint64_t n_
 {
     mhx_ctx* ctx = r->ctx;
     const size_t N = (size_t)s->n_samples, n = (size_t)r->n;
-    int rc = ensure_buffer((void**)&r->d_rec_loga, &r->rec_loga_cap, N * n * sizeof(mhx_real));
+    int rc = ensure_buffer((void**)&r->d_rec_loga, &r->rec_loga_cap, N * n * sizeof(mhx_real), "mhx_run_sample", "step-statistics buffer");
     if (rc) return rc;
     r->rec_loga_view = r->d_rec_loga;
     r->rec_n = s->n_samples;
@@ -408,7 +408,7 @@ static int ram_prepare_step_stats(mhx_run* r, const mhx_schedule* s, uint64_t n_
     r->watch_count = 0;
     if (r->watch_n > 0) {
         const size_t tri = (size_t)r->dim * (size_t)(r->dim + 1) / 2;
-        rc = ensure_buffer((void**)&r->d_watch, &r->watch_cap, N * (size_t)r->watch_n * tri * sizeof(mhx_real));
+        rc = ensure_buffer((void**)&r->d_watch, &r->watch_cap, N * (size_t)r->watch_n * tri * sizeof(mhx_real), "mhx_run_sample", "watched-factor buffer");
         if (rc) return rc;
         if (s->discard_initial == 0) { rc = ram_watch_record(r); if (rc) return rc; }
     }

@@ -103,6 +103,22 @@ int need_runs(const mhx_group* g, const char* who)
     return MHX_OK;
 }
 
+// sums over the union of the members' draws: fill(i, slice) has member i compute its shard's `len` sums into its slice of one buffer
+// (concurrently, each on its own thread and device); the host adds the slices in member order, 0 + member 0 + member 1 + ..., which
+// fixes the bits of a double sum.  Nothing reaches `sum` unless every member succeeded.
+template <class T, class Fill>
+int sum_over_members(mhx_group* g, const char* who, size_t len, std::vector<T>* sum, const Fill& fill)
+{
+    const size_t n = g->mem.size();
+    std::vector<T> buf(n * len, T(0));
+    int rc = for_all(g, who, [&fill, &buf, len](int i) { return fill(i, buf.data() + (size_t)i * len); });
+    if (rc) return rc;
+    sum->assign(len, T(0));
+    for (size_t k = 0; k < len; ++k)
+        for (size_t i = 0; i < n; ++i) (*sum)[k] += buf[i * len + k];
+    return MHX_OK;
+}
+
 }  // namespace
 
 extern "C" int mhx_group_create(const int32_t* devices, int32_t n, int dtype, mhx_group** out)
@@ -411,21 +427,17 @@ extern "C" int mhx_group_cross_moments(mhx_group* g, const int32_t* params, int3
     if (shift)
         for (int32_t i = 0; i < nparams; ++i)
             if (!std::isfinite(shift[i])) return mhx_fail(MHX_EINVAL, "%s: shift %d is not finite", who, (int)i);
-    const size_t n = g->mem.size(), m = (size_t)nparams, stride = m * m + m;
-    std::vector<double> buf(n * stride, 0.0);
-    std::vector<int64_t> nd(n, 0);
-    rc = for_all(g, who, [g, params, nparams, shift, m, stride, &buf, &nd](int i) {
-        double* b = buf.data() + (size_t)i * stride;
+    const size_t m = (size_t)nparams;
+    std::vector<int64_t> nd(g->mem.size(), 0);
+    std::vector<double> tot;                                        // cross [m][m], then sum [m]
+    rc = sum_over_members(g, who, m * m + m, &tot, [g, params, nparams, shift, m, &nd](int i, double* b) {
         return mhx_run_cross_moments(g->mem[i]->run, params, nparams, shift, b + m * m, b, &nd[(size_t)i]);
     });
     if (rc) return rc;
+    std::copy(tot.begin(), tot.begin() + m * m, cross);
+    std::copy(tot.begin() + m * m, tot.end(), sum);
     int64_t total = 0;
-    for (size_t k = 0; k < stride; ++k) {
-        double a = 0.0;
-        for (size_t i = 0; i < n; ++i) a += buf[i * stride + k];
-        (k < m * m ? cross[k] : sum[k - m * m]) = a;
-    }
-    for (size_t i = 0; i < n; ++i) total += nd[i];
+    for (int64_t x : nd) total += x;
     if (n_draws) *n_draws = total;
     return MHX_OK;
 }
@@ -443,20 +455,14 @@ int group_histogram(mhx_group* g, const char* who, const int32_t* params, int32_
     if (nbins < 1 || nbins > limit) return mhx_fail(MHX_EINVAL, "%s: nbins = %d is not in [1, %d]", who, (int)nbins, (int)limit);
     const size_t rows = pairs ? (size_t)npairs : (size_t)nparams;
     const size_t ncount = rows * (size_t)nbins * (pairs ? (size_t)nbins : 1), nout = rows * (pairs ? 1 : 3), stride = ncount + nout;
-    const size_t n = g->mem.size();
-    std::vector<uint64_t> buf(n * stride, 0);
-    rc = for_all(g, who, [g, params, nparams, edges, nbins, pairs, npairs, ncount, stride, &buf](int i) {
-        uint64_t* b = buf.data() + (size_t)i * stride;
+    std::vector<uint64_t> tot;                                      // counts, then outside
+    rc = sum_over_members(g, who, stride, &tot, [g, params, nparams, edges, nbins, pairs, npairs, ncount](int i, uint64_t* b) {
         return pairs ? mhx_run_histogram2d(g->mem[i]->run, params, nparams, edges, nbins, pairs, npairs, b, b + ncount)
                      : mhx_run_histogram(g->mem[i]->run, params, nparams, edges, nbins, b, b + ncount);
     });
     if (rc) return rc;
-    for (size_t k = 0; k < stride; ++k) {
-        uint64_t a = 0;
-        for (size_t i = 0; i < n; ++i) a += buf[i * stride + k];
-        if (k < ncount) counts[k] = a;
-        else if (outside) outside[k - ncount] = a;
-    }
+    std::copy(tot.begin(), tot.begin() + ncount, counts);
+    if (outside) std::copy(tot.begin() + ncount, tot.end(), outside);
     return MHX_OK;
 }
 }  // namespace
@@ -485,18 +491,13 @@ extern "C" int mhx_group_autocovariance(mhx_group* g, const int32_t* params, int
     if (rc) return rc;
     if (!params || nparams <= 0 || !lags || nlags <= 0 || !acov) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
     const size_t n = g->mem.size(), na = (size_t)nparams * (size_t)nlags;
-    std::vector<double> buf(n * na, 0.0);
     std::vector<int64_t> nv(n * (size_t)nparams, 0);
-    rc = for_all(g, who, [g, params, nparams, lags, nlags, normalise, na, &buf, &nv](int i) {
-        return mhx_run_autocovariance(g->mem[i]->run, params, nparams, lags, nlags, 0, 0, normalise, buf.data() + (size_t)i * na,
-                                      nv.data() + (size_t)i * (size_t)nparams);
+    std::vector<double> tot;
+    rc = sum_over_members(g, who, na, &tot, [g, params, nparams, lags, nlags, normalise, &nv](int i, double* b) {
+        return mhx_run_autocovariance(g->mem[i]->run, params, nparams, lags, nlags, 0, 0, normalise, b, nv.data() + (size_t)i * (size_t)nparams);
     });
     if (rc) return rc;
-    for (size_t k = 0; k < na; ++k) {
-        double a = 0.0;
-        for (size_t i = 0; i < n; ++i) a += buf[i * na + k];
-        acov[k] = a;
-    }
+    std::copy(tot.begin(), tot.end(), acov);
     if (nvalid)
         for (size_t p = 0; p < (size_t)nparams; ++p) {
             int64_t a = 0;

@@ -9,6 +9,7 @@ import pytest
 
 import acf_ref as A
 import diag_ref as R
+from planted import plant_ptr as _plant
 
 pytestmark = pytest.mark.gpu
 K = R.MARGIN
@@ -16,23 +17,6 @@ SENT_D, SENT_I = -12345.678, -987654321
 I32P, I64P, DP = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 NONFINITE = (R.R_NAN, R.R_NEG_NAN, R.R_PINF, R.R_NINF)
 MODES = (("un", "acov", False), ("nm", "nacov", True))
-
-
-def _plant(mhx, x):
-    """a run whose device sample buffer holds x [N][dim+1][C] (the way tests/test_gpu_diagnostics.py plants it)"""
-    N, d1, nch = x.shape
-    d = d1 - 1
-    run = mhx.Run(mhx.DensityModel(mhx.IsoGaussian(d)), mhx.RWMH(mhx.MvNormal(mhx.zeros(d), mhx.I)), nchains=nch, seed=1)
-    run.init(None)
-    run.sample(N, 0, 1, 0)
-    assert x.dtype == run.real and x.flags.c_contiguous
-    ptr, n = C.c_void_p(), C.c_int64()
-    mhx.check(mhx.lib().mhx_run_device_samples(run.h, C.byref(ptr), None, C.byref(n)))
-    assert n.value == N and ptr.value
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    assert hip.hipMemcpy(ptr, x.ctypes.data_as(C.c_void_p), x.nbytes, 1) == 0        # hipMemcpyHostToDevice, blocking
-    return run, ptr
 
 
 def _raw(fn, head, params, lags, chains, normalise, acov_null=False, nlags=None):

@@ -6,7 +6,6 @@ The scores are compared element by element -- which pins every rank, bulk and fo
 the reference's own bounds.  The tensors are planted in the sample buffer of a run of their shape, as tests/test_gpu_diagnostics.py
 does.  Every comparison of an R-hat prints `DIAG_RATIO <width> rhat_bulk|rhat_tail <|error| / bound>`; the largest per width are
 tabulated in DESIGN.md 6.5."""
-import ctypes as C
 import re
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 
 import diag_ref as R
 import rank_rhat_ref as F
+from planted import plant as _plant
 
 pytestmark = pytest.mark.gpu
 K = R.MARGIN
@@ -23,25 +23,6 @@ SUBSET = np.array([R.R_NINF, 9, 2, 2, 0, R.R_NAN, R.R_CONST], dtype=np.int32)   
 
 def _id(key):
     return key if isinstance(key, str) else ("extras-N%d-C%d" % key[1:] if key[0] == "extras" else R.case_id(key))
-
-
-def _plant(mhx, x):
-    """a run whose device sample buffer holds x [N][dim+1][C]"""
-    N, d1, nch = x.shape
-    d = d1 - 1
-    run = mhx.Run(mhx.DensityModel(mhx.IsoGaussian(d)), mhx.RWMH(mhx.MvNormal(mhx.zeros(d), mhx.I)), nchains=nch, seed=1)
-    run.init(None)
-    run.sample(N, 0, 1, 0)
-    assert x.dtype == run.real and x.flags.c_contiguous
-    ptr, n = C.c_void_p(), C.c_int64()
-    mhx.check(mhx.lib().mhx_run_device_samples(run.h, C.byref(ptr), None, C.byref(n)))
-    assert n.value == N and ptr.value
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    assert hip.hipMemcpy(ptr, x.ctypes.data_as(C.c_void_p), x.nbytes, 1) == 0        # hipMemcpyHostToDevice, blocking
-    back, _ = run.samples(want_accepted=False)
-    assert np.array_equal(back.view(np.uint8), x.view(np.uint8))
-    return run
 
 
 def _near(got, want, bound, width, what, where):
