@@ -53,6 +53,21 @@ static inline bool same(const void* a, const void* b) { return !a || !b || is64(
     } while (0)
 #define MIXED(name) mhx_fail(MHX_EINVAL, name ": the handles belong to contexts of different dtype")
 
+// The one guard of the entry points that step, initialise, set, save or load state, or read sampler state: a derived run
+// (mhx_run_derive) holds a sample tensor and nothing else.  Which entry is on which list: include/mhx.h at mhx_run_derive.
+static int refuse_derived(const mhx_run* r, const char* name)
+{
+    const bool derived = is64(r) ? mhx_f64::api_run_is_derived(reinterpret_cast<const mhx_f64::mhx_run*>(r))
+                                 : mhx_f32::api_run_is_derived(reinterpret_cast<const mhx_f32::mhx_run*>(r));
+    if (!derived) return MHX_OK;
+    return mhx_fail(MHX_ESTATE, "%s: the run is a derived run (mhx_run_derive): it holds a sample tensor and no sampler state", name);
+}
+#define NEED_SAMPLER(h, name)                                                          \
+    do {                                                                               \
+        NEED(h, name);                                                                 \
+        if (int rc_ = refuse_derived(h, name)) return rc_;                             \
+    } while (0)
+
 extern "C" int mhx_ctx_create(int device, int dtype, mhx_ctx** out)
 {
     if (!out) return mhx_fail(MHX_EINVAL, "mhx_ctx_create: out is NULL");
@@ -216,32 +231,32 @@ extern "C" int mhx_rwmh_create_composite(mhx_ctx* ctx, const mhx_target* t, cons
 
 extern "C" int mhx_ram_set_factor(mhx_run* r, const void* S)
 {
-    NEED(r, "mhx_ram_set_factor");
+    NEED_SAMPLER(r, "mhx_ram_set_factor");
     return is64(r) ? mhx_f64::api_ram_set_factor(R64(r), CD(S)) : mhx_f32::api_ram_set_factor(R32(r), CF(S));
 }
 extern "C" int mhx_ram_set_factor_all(mhx_run* r, const void* S)
 {
-    NEED(r, "mhx_ram_set_factor_all");
+    NEED_SAMPLER(r, "mhx_ram_set_factor_all");
     return is64(r) ? mhx_f64::api_ram_set_factor_all(R64(r), CD(S)) : mhx_f32::api_ram_set_factor_all(R32(r), CF(S));
 }
 extern "C" int mhx_ram_get_factor(mhx_run* r, void* S, uint8_t* status)
 {
-    NEED(r, "mhx_ram_get_factor");
+    NEED_SAMPLER(r, "mhx_ram_get_factor");
     return is64(r) ? mhx_f64::api_ram_get_factor(R64(r), D(S), status) : mhx_f32::api_ram_get_factor(R32(r), F(S), status);
 }
 extern "C" int mhx_ram_get_diag_range(mhx_run* r, void* diag_min, void* diag_max)
 {
-    NEED(r, "mhx_ram_get_diag_range");
+    NEED_SAMPLER(r, "mhx_ram_get_diag_range");
     return is64(r) ? mhx_f64::api_ram_get_diag_range(R64(r), D(diag_min), D(diag_max)) : mhx_f32::api_ram_get_diag_range(R32(r), F(diag_min), F(diag_max));
 }
 extern "C" int mhx_ram_watch_factors(mhx_run* r, const int32_t* chains, int32_t n)
 {
-    NEED(r, "mhx_ram_watch_factors");
+    NEED_SAMPLER(r, "mhx_ram_watch_factors");
     return is64(r) ? mhx_f64::api_ram_watch_factors(R64(r), chains, n) : mhx_f32::api_ram_watch_factors(R32(r), chains, n);
 }
 extern "C" int mhx_ram_get_watched_factors(mhx_run* r, void* S, int64_t capacity, int64_t* n_recorded, int32_t* n_watched)
 {
-    NEED(r, "mhx_ram_get_watched_factors");
+    NEED_SAMPLER(r, "mhx_ram_get_watched_factors");
     long nrec = 0; int nw = 0;
     const int rc = is64(r) ? mhx_f64::api_ram_get_watched_factors(R64(r), D(S), (long)capacity, &nrec, &nw)
                            : mhx_f32::api_ram_get_watched_factors(R32(r), F(S), (long)capacity, &nrec, &nw);
@@ -251,7 +266,7 @@ extern "C" int mhx_ram_get_watched_factors(mhx_run* r, void* S, int64_t capacity
 }
 extern "C" int mhx_ram_get_step_stats(mhx_run* r, void* log_alpha, double* eta, int64_t capacity, int64_t* n_recorded)
 {
-    NEED(r, "mhx_ram_get_step_stats");
+    NEED_SAMPLER(r, "mhx_ram_get_step_stats");
     long nrec = 0;
     const int rc = is64(r) ? mhx_f64::api_ram_get_step_stats(R64(r), D(log_alpha), eta, (long)capacity, &nrec)
                            : mhx_f32::api_ram_get_step_stats(R32(r), F(log_alpha), eta, (long)capacity, &nrec);
@@ -260,19 +275,19 @@ extern "C" int mhx_ram_get_step_stats(mhx_run* r, void* log_alpha, double* eta, 
 }
 extern "C" int mhx_ram_get_adapt_state(mhx_run* r, void* log_alpha, double* eta, uint8_t* isaccept, uint64_t* iteration)
 {
-    NEED(r, "mhx_ram_get_adapt_state");
+    NEED_SAMPLER(r, "mhx_ram_get_adapt_state");
     return is64(r) ? mhx_f64::api_ram_get_adapt_state(R64(r), D(log_alpha), eta, isaccept, iteration)
                    : mhx_f32::api_ram_get_adapt_state(R32(r), F(log_alpha), eta, isaccept, iteration);
 }
 
 extern "C" int mhx_run_init(mhx_run* r, const void* initial_params)
 {
-    NEED(r, "mhx_run_init");
+    NEED_SAMPLER(r, "mhx_run_init");
     return is64(r) ? mhx_f64::api_run_init(R64(r), CD(initial_params)) : mhx_f32::api_run_init(R32(r), CF(initial_params));
 }
 extern "C" int mhx_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
 {
-    NEED(r, "mhx_run_sample");
+    NEED_SAMPLER(r, "mhx_run_sample");
     return is64(r) ? mhx_f64::api_run_sample(R64(r), s, save_samples) : mhx_f32::api_run_sample(R32(r), s, save_samples);
 }
 extern "C" int mhx_run_get_samples(mhx_run* r, void* samples, uint8_t* accepted)
@@ -287,7 +302,7 @@ extern "C" int mhx_run_host_stats(mhx_run* r, mhx_host_stats* out)
 }
 extern "C" int mhx_run_sample_to_host(mhx_run* r, const mhx_schedule* s, void* samples, uint8_t* accepted, int32_t slab_samples)
 {
-    NEED(r, "mhx_run_sample_to_host");
+    NEED_SAMPLER(r, "mhx_run_sample_to_host");
     return is64(r) ? mhx_f64::api_run_sample_to_host(R64(r), s, D(samples), accepted, slab_samples)
                    : mhx_f32::api_run_sample_to_host(R32(r), s, F(samples), accepted, slab_samples);
 }
@@ -298,27 +313,27 @@ extern "C" int mhx_run_device_samples(mhx_run* r, void** samples, void** accepte
 }
 extern "C" int mhx_run_get_state(mhx_run* r, void* x, void* lp, uint32_t* accept_counts)
 {
-    NEED(r, "mhx_run_get_state");
+    NEED_SAMPLER(r, "mhx_run_get_state");
     return is64(r) ? mhx_f64::api_run_get_state(R64(r), D(x), D(lp), accept_counts) : mhx_f32::api_run_get_state(R32(r), F(x), F(lp), accept_counts);
 }
 extern "C" int mhx_run_set_state(mhx_run* r, const void* x)
 {
-    NEED(r, "mhx_run_set_state");
+    NEED_SAMPLER(r, "mhx_run_set_state");
     return is64(r) ? mhx_f64::api_run_set_state(R64(r), CD(x)) : mhx_f32::api_run_set_state(R32(r), CF(x));
 }
 extern "C" int mhx_run_state_size(mhx_run* r, size_t* bytes)
 {
-    NEED(r, "mhx_run_state_size");
+    NEED_SAMPLER(r, "mhx_run_state_size");
     return is64(r) ? mhx_f64::api_run_state_size(R64(r), bytes) : mhx_f32::api_run_state_size(R32(r), bytes);
 }
 extern "C" int mhx_run_save_state(mhx_run* r, void* blob, size_t bytes)
 {
-    NEED(r, "mhx_run_save_state");
+    NEED_SAMPLER(r, "mhx_run_save_state");
     return is64(r) ? mhx_f64::api_run_save_state(R64(r), blob, bytes) : mhx_f32::api_run_save_state(R32(r), blob, bytes);
 }
 extern "C" int mhx_run_load_state(mhx_run* r, const void* blob, size_t bytes)
 {
-    NEED(r, "mhx_run_load_state");
+    NEED_SAMPLER(r, "mhx_run_load_state");
     return is64(r) ? mhx_f64::api_run_load_state(R64(r), blob, bytes) : mhx_f32::api_run_load_state(R32(r), blob, bytes);
 }
 extern "C" int mhx_run_stats(mhx_run* r, mhx_stats* out)
@@ -448,6 +463,23 @@ extern "C" int mhx_run_autocovariance(mhx_run* r, const int32_t* params, int32_t
     return is64(r) ? mhx_f64::api_run_autocovariance(R64(r), params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid)
                    : mhx_f32::api_run_autocovariance(R32(r), params, nparams, lags, nlags, chain_begin, chain_count, normalise, acov, nvalid);
 }
+extern "C" int mhx_run_derive(const mhx_run* src, const char* source, int32_t nout, const void* data, size_t ndata, mhx_run** out)
+{
+    NEED(src, "mhx_run_derive");
+    return is64(src) ? mhx_f64::api_run_derive(reinterpret_cast<const mhx_f64::mhx_run*>(src), source, nout, CD(data), ndata,
+                                               reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_run_derive(reinterpret_cast<const mhx_f32::mhx_run*>(src), source, nout, CF(data), ndata,
+                                               reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
+extern "C" int mhx_ctx_derive(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const char* source,
+                              int32_t nout, const void* data, size_t ndata, mhx_run** out)
+{
+    NEED(ctx, "mhx_ctx_derive");
+    return is64(ctx) ? mhx_f64::api_ctx_derive(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, source, nout, CD(data), ndata,
+                                               reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_ctx_derive(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, source, nout, CF(data), ndata,
+                                               reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
 extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                      const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
 {
@@ -464,33 +496,33 @@ extern "C" int mhx_run_cross_moments(mhx_run* r, const int32_t* params, int32_t 
 }
 extern "C" int mhx_emcee_half_step(mhx_run* r, int half, int begin, int count)
 {
-    NEED(r, "mhx_emcee_half_step");
+    NEED_SAMPLER(r, "mhx_emcee_half_step");
     return is64(r) ? mhx_f64::api_emcee_half_step(R64(r), half, begin, count) : mhx_f32::api_emcee_half_step(R32(r), half, begin, count);
 }
 extern "C" int mhx_emcee_end_sweep(mhx_run* r)
 {
-    NEED(r, "mhx_emcee_end_sweep");
+    NEED_SAMPLER(r, "mhx_emcee_end_sweep");
     return is64(r) ? mhx_f64::api_emcee_end_sweep(R64(r)) : mhx_f32::api_emcee_end_sweep(R32(r));
 }
 extern "C" int mhx_emcee_device_state(mhx_run* r, void** xw, int32_t* pitch, void** lp, uint32_t** acc_count, uint8_t** last_acc)
 {
-    NEED(r, "mhx_emcee_device_state");
+    NEED_SAMPLER(r, "mhx_emcee_device_state");
     return is64(r) ? mhx_f64::api_emcee_device_state(R64(r), reinterpret_cast<double**>(xw), pitch, reinterpret_cast<double**>(lp), acc_count, last_acc)
                    : mhx_f32::api_emcee_device_state(R32(r), reinterpret_cast<float**>(xw), pitch, reinterpret_cast<float**>(lp), acc_count, last_acc);
 }
 extern "C" int mhx_emcee_exchange_plan(mhx_run* r, int half, int world, size_t* stride, void** stream)
 {
-    NEED(r, "mhx_emcee_exchange_plan");
+    NEED_SAMPLER(r, "mhx_emcee_exchange_plan");
     return is64(r) ? mhx_f64::api_emcee_exchange_plan(R64(r), half, world, stride, stream) : mhx_f32::api_emcee_exchange_plan(R32(r), half, world, stride, stream);
 }
 extern "C" int mhx_emcee_exchange_pack(mhx_run* r, int half, int rank, int world, void* part)
 {
-    NEED(r, "mhx_emcee_exchange_pack");
+    NEED_SAMPLER(r, "mhx_emcee_exchange_pack");
     return is64(r) ? mhx_f64::api_emcee_exchange_pack(R64(r), half, rank, world, part) : mhx_f32::api_emcee_exchange_pack(R32(r), half, rank, world, part);
 }
 extern "C" int mhx_emcee_exchange_unpack(mhx_run* r, int half, int rank, int world, const void* stage, size_t stride)
 {
-    NEED(r, "mhx_emcee_exchange_unpack");
+    NEED_SAMPLER(r, "mhx_emcee_exchange_unpack");
     return is64(r) ? mhx_f64::api_emcee_exchange_unpack(R64(r), half, rank, world, stage, stride)
                    : mhx_f32::api_emcee_exchange_unpack(R32(r), half, rank, world, stage, stride);
 }

@@ -39,6 +39,7 @@
 #include "mhx_hpd_kernels.h"
 #include "mhx_hist_kernels.h"
 #include "mhx_acf_kernels.h"
+#include "mhx_derive_kernels.h"     // (its constants: the frame itself is compiled at run time only)
 #ifdef MHX_TOOLS_BUILD
 #include "mhx_jit_embed_tools.inc"   // generated: the device headers as string literals for hiprtc, probes included
 #else
@@ -314,7 +315,7 @@ static const opt_name k_opt_names[] = {
     {"EMCEE_MFMA", 0}, {"EMCEE_MFMA_WAVES", 0}, {"EMCEE_SCALAR", 0}, {"EMCEE_SCAL_MODE", 0}, {"EMCEE_SCAL_WPB", 0}, {"EMCEE_SCAL_REC", 0},
     {"EMCEE_FUSED", 0}, {"EMCEE_PERSIST", 0}, {"EMCEE_PRELOAD", 0}, {"EMCEE_DEFER", 0}, {"EMCEE_SWEEP_DEFER", 0}, {"EMCEE_WAVES", 0},
     {"EMCEE_REC_STORE", 0}, {"EMCEE_ROW_STORE", 0}, {"EMCEE_COOP_REC", 0},
-    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0}, {"HPD_SCRATCH_MB", 0}, {"ACF_R", 0},
+    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0}, {"HPD_SCRATCH_MB", 0}, {"ACF_R", 0}, {"DERIVE_DRAWS", 0},
 #ifdef MHX_TOOLS_BUILD
     {"ZIG_PROBE", 1}, {"ZIG_FORCE_FAIL", 1}, {"JIT_DEFS", 1}, {"JIT_FLAGS", 1}, {"EMCEE_PROBE", 1}, {"EMCEE_STAMPS", 1}, {"EMCEE_STAMPS_FILE", 1},
     {"FAULT_SLAB", 1}, {"RAM_PROF", 1}, {"HPD_STOP_AFTER", 1},
@@ -504,11 +505,11 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
                              k_src_mhx_emcee_kernels_h, k_src_mhx_ram_kernels_h, k_src_mhx_mala_kernels_h,
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
                              k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
-                             k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h};
+                             k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h, k_src_mhx_derive_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
-                              "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h"};
+                              "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h", "mhx_derive_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -826,7 +827,9 @@ int api_target_eval(mhx_ctx* ctx, const mhx_target* t, const mhx_real* x, int n,
 
 // ---------------------------------------------------------------------------------------------
 // runs
-enum run_kind { RUN_RWMH = 0, RUN_EMCEE = 1, RUN_RAM = 2, RUN_MALA = 3 };
+// RUN_DERIVED (mhx_api_derive.inc): a sample tensor and nothing else -- no target, no sampler state; dim, n, n_saved, d_samples and
+// ctx are its only fields in use.  The entry points that step or read sampler state refuse it in mhx_abi.cpp (api_run_is_derived).
+enum run_kind { RUN_RWMH = 0, RUN_EMCEE = 1, RUN_RAM = 2, RUN_MALA = 3, RUN_DERIVED = 4 };
 // The kernel form of a run.  The numbers are frozen: they travel as mhx_stats.kernel_variant (described at include/mhx.h:403), in
 // ckpt_header.variant, and the host mirrors and bench.py read them.
 enum kernel_form {
@@ -1884,6 +1887,8 @@ int api_run_get_samples(mhx_run* r, mhx_real* samples, uint8_t* accepted)
     if (!r) return mhx_fail(MHX_EINVAL, "mhx_run_get_samples: run is NULL");
     if (r->n_saved <= 0 || r->moments_mode)
         return mhx_fail(MHX_ESTATE, "mhx_run_get_samples: the last mhx_run_sample kept no sample tensor");
+    if (accepted && !r->d_accepted)
+        return mhx_fail(MHX_EINVAL, "mhx_run_get_samples: a derived run holds no accept flags (they are its source's): pass accepted = NULL");
     HIP_TRY(hipSetDevice(r->ctx->device));
     const size_t N = (size_t)r->n_saved, n = (size_t)r->n, d1 = (size_t)r->dim + 1;
     if (samples) COPY_SYNC(r->ctx->stream, samples, r->d_samples, N * d1 * n * sizeof(mhx_real), hipMemcpyDeviceToHost);
@@ -2060,6 +2065,7 @@ int api_run_stats(mhx_run* r, mhx_stats* out)
 const char* api_run_form_name(const mhx_run* r)
 {
     if (!r) return "";
+    if (r->kind == RUN_DERIVED) return "derived";
     switch (r->variant) {
     case KF_GENERIC: return "generic";
     case KF_REG: return "reg";
@@ -2087,6 +2093,8 @@ int api_run_host_stats(mhx_run* r, mhx_host_stats* out)
     *out = r->host_stats;
     return MHX_OK;
 }
+
+bool api_run_is_derived(const mhx_run* r) { return r && r->kind == RUN_DERIVED; }
 
 int api_run_shape(const mhx_run* r, int32_t* dim, int32_t* nchains)
 {
@@ -2188,5 +2196,6 @@ struct dev_array {
 #include "mhx_api_hpd.inc"
 #include "mhx_api_hist.inc"
 #include "mhx_api_acf.inc"
+#include "mhx_api_derive.inc"
 
 }  // namespace MHX_NS

@@ -1,0 +1,105 @@
+// derived quantities host side (included by mhx_api.hip after mhx_api_acf.inc): the checks, the run-time module of the map, the
+// derived run and its tensor, one launch (mhx_derive_kernels.h, DESIGN.md section 6.5.5)
+
+// The outputs of the draws a lane maps together stay in registers until they are stored: (nout + 1) reals per draw.  More than this
+// many outputs are refused; up to it the draws per lane shrink so that the outputs stay within about a quarter of the register file.
+#define MHX_DERIVE_MAX_NOUT 128
+// draws a lane maps together where the outputs allow it: DESIGN.md section 7 has the measurement; option DERIVE_DRAWS picks another
+#define MHX_DERIVE_DRAWS 4
+
+static int derive_draws_per_lane(const mhx_ctx* ctx, int nout)
+{
+    const int asked = opt_int(ctx, "DERIVE_DRAWS", 0);
+    const int fit = std::max(1, 128 / ((nout + 1) * (MHX_REAL64 ? 2 : 1)));
+    return std::min(asked >= 1 && asked <= 16 ? asked : MHX_DERIVE_DRAWS, fit);      // (the option never lifts the register cap)
+}
+
+// the module's source: the device math, the map, the frame; with the defines it is the kernel key (jit_compile)
+static std::string derive_source(const char* source)
+{
+    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"derived.hip\"\n";
+    s += source;
+    s += "\n#define MHX_HAVE_DERIVED 1\n#include \"mhx_derive_kernels.h\"\n";
+    return s;
+}
+
+// v is checked, nothing else is.  Nothing is left behind unless the call succeeds: the run and its tensor are owned here until then.
+static int derive_checked(const draws_view& v, const char* source, int32_t nout, const mhx_real* data, size_t ndata, mhx_run** out)
+{
+    const char* who = v.who;
+    mhx_ctx* ctx = v.ctx;
+    if (!source || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", who);
+    if (nout < 1) return mhx_fail(MHX_EINVAL, "%s: nout = %d, a map has at least one output", who, (int)nout);
+    if (nout > MHX_DERIVE_MAX_NOUT)
+        return mhx_fail(MHX_EINVAL, "%s: nout = %d, at most %d outputs per map (they are held in registers): split the map", who, (int)nout,
+                        MHX_DERIVE_MAX_NOUT);
+    if (ndata && !data) return mhx_fail(MHX_EINVAL, "%s: data is NULL", who);
+    if (ndata > 0x7fffffffull) return mhx_fail(MHX_EINVAL, "%s: the data block is too large", who);
+    if (v.C > 0x7fffffffl) return mhx_fail(MHX_EINVAL, "%s: %ld chains, a run holds fewer than 2^31", who, v.C);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int U = derive_draws_per_lane(ctx, nout);
+    jit_module* m = nullptr;
+    hipFunction_t fn = nullptr;
+    int rc = jit_compile(ctx, derive_source(source), {"MHX_JIT_DERIVE_NOUT=" + std::to_string(nout), "MHX_JIT_DERIVE_DRAWS=" + std::to_string(U)}, &m);
+    if (rc == MHX_EJIT) {
+        // a diagnostic on the caller's text (derive_source names it derived.hip): the source is the argument at fault, the compiler's
+        // log stays in the message.  Any other failure of the compile (no compiler, a module that does not load) stays MHX_EJIT.
+        const std::string log = mhx_last_error();
+        if (log.find("derived.hip") != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the map does not compile: %.1900s", who, log.c_str());
+        return rc;
+    }
+    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_derive", &fn);
+    if (rc) return rc;
+    std::unique_ptr<mhx_run> r(new mhx_run);
+    r->dtype = ctx->dtype;
+    r->ctx = ctx;
+    r->kind = RUN_DERIVED;
+    r->dim = nout;
+    r->n = (int)v.C;
+    const size_t bytes = (size_t)v.N * ((size_t)nout + 1) * (size_t)v.C * sizeof(mhx_real);
+    rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, bytes, who, "derived sample tensor");
+    if (rc) { (void)hipGetLastError(); return rc; }
+    dev_array<mhx_real> d_data;
+    if (!d_data.alloc(ndata ? ndata : 1)) {                 // (one dummy element keeps the pointer valid)
+        (void)hipGetLastError();
+        return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of data block", who, ndata * sizeof(mhx_real));
+    }
+    if (ndata) HIP_TRY(hipMemcpyAsync(d_data.p, data, ndata * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
+    const mhx_real* src = v.tensor;
+    mhx_real* dst = r->d_samples;
+    long N = v.N, C = v.C;
+    int d = v.d1 - 1, nd = (int)ndata;
+    const mhx_real* dd = d_data.p;
+    const long strip = (long)U * MHX_DERIVE_ROUNDS, nstrips = (N + strip - 1) / strip;
+    void* params[] = {&src, &dst, &N, &C, &d, &dd, &nd};
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)((C + MHX_DERIVE_THREADS - 1) / MHX_DERIVE_THREADS), (unsigned)std::min(nstrips, 65535l), 1,
+                                  MHX_DERIVE_THREADS, 1, 1, 0, ctx->stream, params, nullptr));
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    r->n_saved = v.N;
+    r->stats.kernel_ms = ms;                                // the map's launch; no transitions, no accepts
+    r->stats.kernel_variant = -1;                           // none of enum kernel_form: mhx_run_form_name says "derived"
+    r->stats.launches = 1;
+    r->stats.dtype = r->dtype;
+    r->stats.factor_band = -1;
+    *out = r.release();
+    return MHX_OK;
+}
+
+int api_ctx_derive(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const char* source, int32_t nout,
+                   const mhx_real* data, size_t ndata, mhx_run** out)
+{
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_derive", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    return rc ? rc : derive_checked(v, source, nout, data, ndata, out);
+}
+
+int api_run_derive(const mhx_run* src, const char* source, int32_t nout, const mhx_real* data, size_t ndata, mhx_run** out)
+{
+    draws_view v;
+    int rc = draws_of_run("mhx_run_derive", src, &v);
+    return rc ? rc : derive_checked(v, source, nout, data, ndata, out);
+}

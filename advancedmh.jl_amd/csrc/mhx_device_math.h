@@ -72,6 +72,14 @@ MHX_NS_BEGIN
     MHX_DEV void mhx_user_proposal_params(const MHX_X& x, const MHX_P& p, const int d,                         \
                                           const mhx_real* __restrict__ data, const int ndata)
 
+// a map of the saved draws in HIP source form (include/mhx.h, mhx_run_derive): reads one draw x[0 .. d-1]
+// (x[d] is its lp) and writes y.set(j, value), j = 0 .. nout-1, the derived quantities of that draw.  x[k] loads row k when it is
+// named, so a map of 3 of 100 parameters reads 3 rows; an output the source does not set is NaN.  One text serves both widths.
+#define MHX_DERIVED(x, y, d, data, ndata)                                                                      \
+    template <class MHX_X, class MHX_Y>                                                                        \
+    MHX_DEV void mhx_user_derived(const MHX_X& x, const MHX_Y& y, const int d,                                 \
+                                  const mhx_real* __restrict__ data, const int ndata)
+
 // wave-uniform base pointer + 32-bit per-lane BYTE offset: lowers to the scalar-base addressing mode
 // (global_load/store v_off, ..., s[base:base+1]) instead of a 64-bit vector address per access
 MHX_DEV mhx_real mhx_ld_off(const mhx_real* base, mhx_u32 byte_off)

@@ -114,6 +114,11 @@ void mhx_jit_unlock();
     int api_run_autocovariance(mhx_run* r, const int32_t* params, int32_t nparams, const int32_t* lags, int32_t nlags, \
                                int64_t chain_begin, int64_t chain_count, int32_t normalise, double* acov,              \
                                int64_t* nvalid);                                                                       \
+    int api_run_derive(const mhx_run* src, const char* source, int32_t nout, const REAL* data, size_t ndata,           \
+                       mhx_run** out);                                                                                 \
+    int api_ctx_derive(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,           \
+                       const char* source, int32_t nout, const REAL* data, size_t ndata, mhx_run** out);               \
+    bool api_run_is_derived(const mhx_run* r);                                                                         \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \
     int api_emcee_device_state(mhx_run* r, REAL** xw, int32_t* pitch, REAL** lp, uint32_t** acc_count,                 \

@@ -456,6 +456,16 @@ class HipLogDensity(_TargetSpec):
         return h
 
 
+class HipMap:
+    """A map of the saved draws as HIP source (Run.derive):  MHX_DERIVED(x, y, d, data, ndata) { y.set(0, x[1] * x[1]); }  -- x[0 .. d-1]
+    one draw, x[d] its lp, y.set(j, value) output j < nout -- written against `mhx_real` / `MHX_R(literal)` so that it compiles for
+    either dtype.  The hand-written form of what mhx.trace.trace_map records."""
+
+    def __init__(self, source, nout, data=None):
+        self.source, self.nout = source, int(nout)
+        self.data = None if data is None else np.asarray(data, dtype=np.float64).ravel()
+
+
 class DensityModel:
     """DensityModel(logdensity) -- src/AdvancedMH.jl:52-54.  `logdensity` is a catalogue log-density, HipLogDensity(source, dim),
     or a Python callable of the parameter vector together with `dim`: the callable is traced once (mhx/trace.py) and lowered
@@ -1302,6 +1312,24 @@ class Chains:
         return dict(parameters=[self.names[i] for i in idx], tau=tau, window=np.array([r[1] for r in res], dtype=np.int64),
                     truncated=np.array([r[2] for r in res], dtype=bool), converged=converged, nvalid=nvalid)
 
+    def derive(self, fn, names=None, lp=False):
+        """The chain of derived quantities -- sigma ** 2, exp(beta), mu[1] - mu[0], an indicator where(theta > 0, 1.0, 0.0) -- of
+        every draw, mapped on the device from the run's sample buffer (Run.derive): `chain.derive(lambda t: t.sigma ** 2,
+        names=["sigma2"]).describe()`.  fn gets the parameters as a vector that answers to their names (with lp=True: fn(theta, lp))
+        and returns one number or a list of them; `names` names the outputs.  The result is a Chains over a derived run
+        (chain.state), with the same start and thin and this chain's accept flags: describe, hpd, cor, corner, density, autocor and
+        rhat work on it as on any chain.  Needs the live run."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "derive needs the live run (chain.state)")
+        run = self.state.derive(fn, names=self.params(), lp=lp)
+        if names is None:
+            names = ["derived"] if run.dim == 1 else ["derived[%d]" % (j + 1) for j in range(run.dim)]
+        names = [str(n) for n in ([names] if isinstance(names, str) else names)]
+        if len(names) != run.dim:
+            raise L.ArgumentError(L.MHX_EINVAL, "derive: %d names for %d outputs" % (len(names), run.dim))
+        value, _ = run.samples()
+        return Chains(value, names + ["lp"], self.start, self.thin, accepted=self.accepted, stats=dict(self.stats), state=run)
+
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
         return "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
@@ -1827,6 +1855,31 @@ class Run:
         """the correlation matrix of the same rows"""
         return correlation_from_covariance(self.cov(params))
 
+    def derive(self, fn, nout=None, names=None, lp=False):
+        """Map every saved draw through `fn` on the device (mhx_run_derive) and return the result as a DerivedRun: a run of dim = nout
+        that holds the tensor [n_saved][nout + 1][nchains] -- the outputs, then this run's lp row -- and answers every statistic
+        method (quantiles, hpd, cov, histogram, diagnostics, ...) without a host copy.  It is a snapshot: sampling this run again does
+        not change it.  fn: a Python callable of the parameter vector (with lp=True: of the vector and the draw's lp) that returns
+        one number or a list of them -- traced once by mhx.trace.trace_map, `names` (default: the model's parameter names) making
+        the vector answer to theta.<name> --, a TracedMap, or a HipMap(source, nout, data).  nout: checked against the map's."""
+        if names is None and getattr(self, "model", None) is not None:
+            names = getattr(self.model, "param_names", None)
+        if not isinstance(fn, (HipMap, _trace.TracedMap)):
+            if not callable(fn):
+                raise L.ArgumentError(L.MHX_EINVAL, "derive: a callable, a TracedMap or a HipMap is needed, got %r" % (fn,))
+            try:
+                fn = _trace.trace_map(fn, self.dim, names=names, lp=lp)
+            except _trace.TraceError as e:
+                raise L.ArgumentError(L.MHX_EINVAL, "derive: the callable cannot be traced: %s" % e) from e
+        if isinstance(fn, _trace.TracedMap) and fn.dim != self.dim:
+            raise L.ArgumentError(L.MHX_EINVAL, "derive: the map was traced for %d parameters, the run has %d" % (fn.dim, self.dim))
+        if nout is not None and int(nout) != fn.nout:
+            raise L.ArgumentError(L.MHX_EINVAL, "derive: nout = %d, the map has %d outputs" % (int(nout), fn.nout))
+        data = None if fn.data is None else self.ctx.arr(fn.data)
+        h = C.c_void_p()
+        L.check(L.lib().mhx_run_derive(self.h, fn.source.encode(), fn.nout, L.rptr(data), 0 if data is None else data.size, C.byref(h)))
+        return DerivedRun(h, self, fn.nout)
+
     def close(self):
         if self.h:
             L.lib().mhx_run_destroy(self.h)
@@ -1837,6 +1890,29 @@ class Run:
             self.close()
         except Exception:
             pass
+
+
+class DerivedRun(Run):
+    """What Run.derive returns: the handle of a derived run (include/mhx.h, mhx_run_derive) -- a device sample tensor and nothing else.
+    Every statistic method of Run works on it; what steps or reads sampler state (init, sample, state, set_params, save_state,
+    factor, ...) raises the library's refusal (MHX_ESTATE, "... is a derived run").  `source` keeps the run it came from alive (they
+    share a context)."""
+
+    def __init__(self, handle, source, nout):
+        self.h = handle
+        self.source = source
+        self.ctx, self.real = source.ctx, source.real
+        self.model = self.sampler = None
+        self.n, self.dim = source.n, int(nout)
+        self.seed = source.seed
+        self.kind = "derived"
+        self._keep = []
+
+    def samples(self, want_accepted=False):
+        """(tensor [n_saved][nout + 1][nchains], None): a derived run holds no accept flags -- they are its source's"""
+        if want_accepted:
+            return Run.samples(self, True)                  # the library's refusal
+        return Run.samples(self, False)
 
 
 def combine_diagnostics(sum_m, sum_m2, sum_v, n_chains, n_samples):

@@ -31,7 +31,7 @@ import math
 import numpy as np
 
 __all__ = ["log", "exp", "sqrt", "abs", "fma", "where", "minimum", "maximum", "square", "sum_over", "trace", "Traced", "Sym", "Vec", "NamedVec", "TraceError",
-           "trace_proposal", "TracedProposal"]
+           "trace_proposal", "TracedProposal", "trace_map", "TracedMap"]
 
 
 class TraceError(TypeError):
@@ -770,6 +770,75 @@ def trace(f, dim, gradient=True, names=None):
     if out.g is not g:
         raise TraceError("the returned value belongs to another trace")
     return Traced(g, out.i, dim, gradient)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# derived quantities (mhx_run_derive): a map of every saved draw
+
+
+class TracedMap(Traced):
+    """The recorded map of a draw to its derived quantities: `.source` (MHX_DERIVED), `.nout`, `.dim`, `.lp` (whether the map reads
+    the draw's lp), `.data` (the rows of its sum_over loops or None), `.evaluate(x)` ([nout] float64 of the same program in numpy
+    float64, for checks; with lp the draw's lp is x[dim], or the second argument)."""
+
+    def __init__(self, g, outs, dim, lp=False):
+        self.g, self.dim, self.lp = g, int(dim), bool(lp)
+        self._ld = {}
+        self.grad = None
+        self.outs = list(outs)
+        self.nout = len(self.outs)
+        self.data = np.concatenate(g.data) if g.data else None
+        lines, name = self._body(self.outs)
+        src = ["// traced by mhx.trace (advancedmh.jl_amd/mhx/trace.py): a map of the draws, %d outputs, %d operations in the source%s" % (
+                   self.nout, self._nops, "" if self.data is None else "; data block of %d reals" % self.data.size),
+               "MHX_DERIVED(x, y, d, data, ndata)", "{"] + lines
+        src += ["    y.set(%d, %s);" % (j, name(i)) for j, i in enumerate(self.outs)] + ["}"]
+        self.source = "\n".join(src) + "\n"
+
+    def evaluate(self, x, lp=None):
+        x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+        if lp is not None:
+            x = np.concatenate([x[:self.dim], [float(lp)]])
+        if x.size < self.dim + (1 if self.lp else 0):
+            raise TraceError("evaluate: %d values for a map of %d parameters%s" % (x.size, self.dim, " and lp" if self.lp else ""))
+        return np.array(self._run(x, self.outs), dtype=np.float64)
+
+
+def trace_map(fn, dim, names=None, lp=False):
+    """Run `fn` once on a vector of `dim` traced parameters -- the Vec (with `names`: the NamedVec) a log-density gets; with lp=True
+    the call is fn(theta, lp), lp the draw's log-density -- and return the recorded map (a `TracedMap`).  `fn` returns one traced
+    number, or a list, tuple or Vec of them; plain numbers are constants.  Everything `trace` takes is taken here."""
+    dim = int(dim)
+    if dim < 1:
+        raise TraceError("dim must be >= 1")
+    if names is not None and len(names) != dim:
+        raise TraceError("names: %d given for %d parameters" % (len(names), dim))
+    g = _Graph()
+    g.node("c", _const_key(0.0))        # node 0, as in trace
+    x = [Sym(g, g.node("x", k)) for k in range(dim)]
+    x = NamedVec(x, names) if names is not None else Vec(x)
+    _ACTIVE.append(g)
+    try:
+        out = fn(x, Sym(g, g.node("x", dim))) if lp else fn(x)        # (x[dim] is the draw's lp)
+    finally:
+        _ACTIVE.pop()
+    if isinstance(out, Vec):
+        out = list(out.items)
+    elif not isinstance(out, (list, tuple)):
+        out = [out]
+    if not out:
+        raise TraceError("a map must return at least one number")
+    outs = []
+    for j, v in enumerate(out):
+        if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
+            v = Sym(g, g.node("c", _const_key(v)))
+        if not isinstance(v, Sym):
+            raise TraceError("output %d of the map is %r, not a number or a traced number%s" % (
+                j, type(v).__name__, " (a condition: use where(cond, 1.0, 0.0))" if isinstance(v, (Cond, bool, np.bool_)) else ""))
+        if v.g is not g:
+            raise TraceError("output %d of the map belongs to another trace" % j)
+        outs.append(v.i)
+    return TracedMap(g, outs, dim, lp)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -33,6 +33,8 @@ print(chain.describe())
 print(chain.describe(rhat_kind="rank"))
 # the correlation matrix MCMCChains' `cor(chain)` gives, from cross moments taken on the device's fp64 matrix cores (mhx_run_cross_moments)
 print(chain.cor())
+# a derived quantity, as one writes it on an MCMCChains object: every draw mapped on the device (mhx_run_derive), the same tables for it
+print(chain.derive(lambda t: t.sigma ** 2, names=["sigma2"]).describe())
 print("data: mean %.4f std %.4f;  acceptance rate %.3f;  kernel variant %d" % (
     data.mean(), data.std(), chain.accepted[1:].mean(), chain.stats["kernel_variant"]))
 

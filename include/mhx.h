@@ -89,6 +89,7 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   HPD_SCRATCH_MB (bound, in MiB, on the device scratch of a call of mhx_*_hpd: the rows go in batches that fit;
  *                   default 1024; a positive number, fractions allowed; read at every call)
  *                   ACF_R (8 | 16 | 32 lags per tile of mhx_*_autocovariance; default: the fastest measured per width; read at every call)
+ *                   DERIVE_DRAWS (1..16 draws a lane of mhx_*_derive maps together; default 4; never more than the outputs leave registers for; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
  * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
@@ -815,6 +816,43 @@ int mhx_run_autocovariance(mhx_run *run, const int32_t *params, int32_t nparams,
 int mhx_ctx_autocovariance(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                            const int32_t *params, int32_t nparams, const int32_t *lags, int32_t nlags,
                            int64_t chain_begin, int64_t chain_count, int32_t normalise, double *acov, int64_t *nvalid);
+
+/* Derived quantities: every saved draw of `src` mapped through a user function on the device -- MCMCChains'
+ * one-liners on a Chains object (sigma^2, exp(beta[3]), mu[1] - mu[0], an indicator), Turing's generated_quantities.  `source` is HIP
+ * source of the form
+ *     MHX_DERIVED(x, y, d, data, ndata) { y.set(0, x[1] * x[1]); y.set(1, x[d]); }
+ * x[0 .. d-1] is one draw of the d = dim parameters of `src`, x[d] its lp (a row is loaded only where it is named; an index outside
+ * [0, d] reads x[d]); y.set(j, value), j < nout, writes output j (another j is ignored; an output that is not set is NaN); data /
+ * ndata: `ndata` reals of the context's dtype, copied by the call, NULL / 0 for none.  mhx_real, MHX_R(literal), mhx_log, mhx_exp,
+ * mhx_sqrt, mhx_abs, mhx_fma, MHX_INF and MHX_NAN are there as for mhx_target_from_hip_source, so one text serves both widths; the
+ * arithmetic is the engine's (no contraction: a host restatement reproduces it bit for bit).  No random numbers.
+ * *out is a DERIVED RUN: an mhx_run of dim = nout and the chains of `src` that holds a device sample tensor
+ * [n_saved][nout + 1][nchains] -- rows 0 .. nout-1 the outputs, row nout the lp row of `src`, copied -- and nothing else: no target, no
+ * sampler state, no accept flags.  It is a snapshot: sampling `src` again, or destroying it, does not change it.  It is destroyed by
+ * mhx_run_destroy, lives on the context of `src` (destroy it first), and may itself be a `src`.  On a derived run
+ *   work      mhx_run_device_samples (accepted = NULL), mhx_run_get_samples (accepted must be NULL: MHX_EINVAL otherwise),
+ *             mhx_run_stats (no transitions; kernel_ms = the map's launch, kernel_variant = -1), mhx_run_form_name ("derived"),
+ *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_group_attach, and every post-run statistic:
+ *             mhx_run_diagnostics, _ess_bulk_tail, _rank_diagnostics, _rank_scores, _order_statistics, _select_histogram, _cross_moments,
+ *             _hpd, _histogram, _histogram2d, _autocovariance
+ *   refuse    with MHX_ESTATE and a message that says the run is derived, before anything else is looked at: mhx_run_init, _sample,
+ *             _sample_to_host, _get_state, _set_state, _state_size, _save_state, _load_state; mhx_ram_set_factor, _set_factor_all,
+ *             _get_factor, _get_diag_range, _get_adapt_state, _get_step_stats, _watch_factors, _get_watched_factors; mhx_emcee_half_step,
+ *             _end_sweep, _device_state, _exchange_plan, _exchange_pack, _exchange_unpack (and with them mhx_comm_allgather_walkers and
+ *             the mhx_group_init / _sample / _sample_to_host of a group it is attached to)
+ * The map is compiled at run time, once per (source, nout, dtype, draws per lane), through the context's module table and the on-disk
+ * code-object cache as every run-time kernel: a second call with the same source and nout compiles nothing (mhx_ctx_jit_counts).
+ * MHX_ESTATE: `src` holds no device sample tensor (moments mode, save_samples = 0, a host-streamed run); MHX_EINVAL: source or out
+ * NULL, nout < 1 or > 128 (the outputs of a draw are held in registers: split the map), data NULL with ndata > 0, and a source that
+ * does not compile -- the compiler's log is in mhx_last_error, as for mhx_target_from_hip_source, but the code is MHX_EINVAL: the
+ * source is this call's argument (a compile that fails for another reason, no compiler or a module that does not load, is MHX_EJIT);
+ * MHX_ENOMEM: the tensor cannot be allocated.  *out is written only when the call succeeds and no
+ * partial object is left behind otherwise.  Blocking. */
+int mhx_run_derive(const mhx_run *src, const char *source, int32_t nout, const void *data, size_t ndata, mhx_run **out);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_order_statistics): d = dim1 - 1,
+ * the last row is copied as lp; the derived run lives on ctx */
+int mhx_ctx_derive(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                   const char *source, int32_t nout, const void *data, size_t ndata, mhx_run **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
