@@ -480,6 +480,23 @@ extern "C" int mhx_ctx_derive(mhx_ctx* ctx, const void* d_tensor, int64_t n_samp
                      : mhx_f32::api_ctx_derive(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, source, nout, CF(data), ndata,
                                                reinterpret_cast<mhx_f32::mhx_run**>(out));
 }
+extern "C" int mhx_run_predict(const mhx_run* src, const char* source, int32_t nout, const void* data, size_t ndata, uint64_t seed, mhx_run** out)
+{
+    NEED(src, "mhx_run_predict");
+    return is64(src) ? mhx_f64::api_run_predict(reinterpret_cast<const mhx_f64::mhx_run*>(src), source, nout, CD(data), ndata, seed,
+                                                reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_run_predict(reinterpret_cast<const mhx_f32::mhx_run*>(src), source, nout, CF(data), ndata, seed,
+                                                reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
+extern "C" int mhx_ctx_predict(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, int64_t first_chain,
+                               const char* source, int32_t nout, const void* data, size_t ndata, uint64_t seed, mhx_run** out)
+{
+    NEED(ctx, "mhx_ctx_predict");
+    return is64(ctx) ? mhx_f64::api_ctx_predict(C64(ctx), CD(d_tensor), n_samples, dim1, nchains, first_chain, source, nout, CD(data), ndata,
+                                                seed, reinterpret_cast<mhx_f64::mhx_run**>(out))
+                     : mhx_f32::api_ctx_predict(C32(ctx), CF(d_tensor), n_samples, dim1, nchains, first_chain, source, nout, CF(data), ndata,
+                                                seed, reinterpret_cast<mhx_f32::mhx_run**>(out));
+}
 extern "C" int mhx_ctx_cross_moments(mhx_ctx* ctx, const void* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                                      const int32_t* params, int32_t nparams, const double* shift, double* sum, double* cross)
 {

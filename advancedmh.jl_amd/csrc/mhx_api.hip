@@ -827,8 +827,8 @@ int api_target_eval(mhx_ctx* ctx, const mhx_target* t, const mhx_real* x, int n,
 
 // ---------------------------------------------------------------------------------------------
 // runs
-// RUN_DERIVED (mhx_api_derive.inc): a sample tensor and nothing else -- no target, no sampler state; dim, n, n_saved, d_samples and
-// ctx are its only fields in use.  The entry points that step or read sampler state refuse it in mhx_abi.cpp (api_run_is_derived).
+// RUN_DERIVED (mhx_api_derive.inc): a sample tensor and nothing else -- no target, no sampler state; dim, n, n_saved, d_samples, ctx
+// and the seed and first_id inherited from its source (what a predictive map of it keys its streams by) are its only fields in use.  The entry points that step or read sampler state refuse it in mhx_abi.cpp (api_run_is_derived).
 enum run_kind { RUN_RWMH = 0, RUN_EMCEE = 1, RUN_RAM = 2, RUN_MALA = 3, RUN_DERIVED = 4 };
 // The kernel form of a run.  The numbers are frozen: they travel as mhx_stats.kernel_variant (described at include/mhx.h:403), in
 // ckpt_header.variant, and the host mirrors and bench.py read them.
@@ -2123,6 +2123,7 @@ struct draws_view {
     long N, C;
     int d1;
     const char* who;
+    uint64_t seed, first_id;                        // of the run the draws came from (0 for a caller's tensor): what a derived run inherits
     unsigned long long S() const { return (unsigned long long)N * (unsigned long long)C; }      // draws of a row
 };
 
@@ -2131,7 +2132,7 @@ static int draws_of_ctx(const char* who, mhx_ctx* ctx, const mhx_real* d_tensor,
 {
     if (!ctx || !d_tensor) return mhx_fail(MHX_EINVAL, "%s: bad argument", who);
     if (n_samples < 1 || dim1 < 1 || nchains < 1) return mhx_fail(MHX_EINVAL, "%s: tensor of %lld x %d x %lld", who, (long long)n_samples, (int)dim1, (long long)nchains);
-    *v = draws_view{ctx, d_tensor, (long)n_samples, (long)nchains, dim1, who};
+    *v = draws_view{ctx, d_tensor, (long)n_samples, (long)nchains, dim1, who, 0, 0};
     return MHX_OK;
 }
 
@@ -2141,7 +2142,7 @@ static int draws_of_run(const char* who, const mhx_run* r, draws_view* v)
     if (!r) return mhx_fail(MHX_EINVAL, "%s: run is NULL", who);
     if (r->moments_mode || r->n_saved < 1 || !r->d_samples)
         return mhx_fail(MHX_ESTATE, "%s: the run holds no device sample tensor (moments mode, save_samples = 0 or a host-streamed run)", who);
-    *v = draws_view{r->ctx, r->d_samples, (long)r->n_saved, (long)r->n, r->dim + 1, who};
+    *v = draws_view{r->ctx, r->d_samples, (long)r->n_saved, (long)r->n, r->dim + 1, who, r->seed, r->first_id};
     return MHX_OK;
 }
 

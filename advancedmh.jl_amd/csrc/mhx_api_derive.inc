@@ -1,5 +1,5 @@
-// derived quantities host side (included by mhx_api.hip after mhx_api_acf.inc): the checks, the run-time module of the map, the
-// derived run and its tensor, one launch (mhx_derive_kernels.h, DESIGN.md section 6.5.5)
+// derived quantities and predictive draws host side (included by mhx_api.hip after mhx_api_acf.inc): the checks, the run-time module
+// of the map, the derived run and its tensor, one launch (mhx_derive_kernels.h, DESIGN.md sections 6.5.5 and 6.5.6)
 
 // The outputs of the draws a lane maps together stay in registers until they are stored: (nout + 1) reals per draw.  More than this
 // many outputs are refused; up to it the draws per lane shrink so that the outputs stay within about a quarter of the register file.
@@ -7,24 +7,49 @@
 // draws a lane maps together where the outputs allow it: DESIGN.md section 7 has the measurement; option DERIVE_DRAWS picks another
 #define MHX_DERIVE_DRAWS 4
 
-static int derive_draws_per_lane(const mhx_ctx* ctx, int nout)
+// Draws a lane of a PREDICTIVE map maps together: 1, from the cross-compiled resource usage (DESIGN.md section 6.5.6 has the table).
+// The frame unrolls the map once per draw of the group to have their row loads in flight together; a generator call is some hundred
+// dependent VALU instructions per output, which the other waves of the SIMD cover, and each further draw costs registers and a copy
+// of every attempt loop: the test map with two Gamma draws is 1788 instructions, 131 VGPRs and 3 waves per SIMD at 1 in fp64, 4901 /
+// 155 / 3 at 2, 7823 / 192 / 2 at 4.  Option DERIVE_DRAWS picks another, within the same register cap.
+#define MHX_PREDICT_DRAWS 1
+
+// what differs between the two kinds of map: the name the compiler knows the caller's text by, the frame's define and entry, the
+// default draws per lane -- and, where `rng`, two more kernel arguments and the limit on n_saved
+struct derive_kind {
+    const char* file;
+    const char* have;
+    const char* entry;
+    int draws;
+    bool rng;
+};
+static const derive_kind k_derived = {"derived.hip", "MHX_HAVE_DERIVED", "mhx_jit_derive", MHX_DERIVE_DRAWS, false};
+static const derive_kind k_predictive = {"predictive.hip", "MHX_HAVE_PREDICTIVE", "mhx_jit_predict", MHX_PREDICT_DRAWS, true};
+
+static int derive_draws_per_lane(const mhx_ctx* ctx, const derive_kind& kind, int nout)
 {
     const int asked = opt_int(ctx, "DERIVE_DRAWS", 0);
     const int fit = std::max(1, 128 / ((nout + 1) * (MHX_REAL64 ? 2 : 1)));
-    return std::min(asked >= 1 && asked <= 16 ? asked : MHX_DERIVE_DRAWS, fit);      // (the option never lifts the register cap)
+    return std::min(asked >= 1 && asked <= 16 ? asked : kind.draws, fit);           // (the option never lifts the register cap)
 }
 
 // the module's source: the device math, the map, the frame; with the defines it is the kernel key (jit_compile)
-static std::string derive_source(const char* source)
+static std::string derive_source(const derive_kind& kind, const char* source)
 {
-    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"derived.hip\"\n";
+    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"";
+    s += kind.file;
+    s += "\"\n";
     s += source;
-    s += "\n#define MHX_HAVE_DERIVED 1\n#include \"mhx_derive_kernels.h\"\n";
+    s += "\n#define ";
+    s += kind.have;
+    s += " 1\n#include \"mhx_derive_kernels.h\"\n";
     return s;
 }
 
 // v is checked, nothing else is.  Nothing is left behind unless the call succeeds: the run and its tensor are owned here until then.
-static int derive_checked(const draws_view& v, const char* source, int32_t nout, const mhx_real* data, size_t ndata, mhx_run** out)
+// seed: the predictive streams' (a derived map has none); the run that is made inherits v's seed and first_id either way.
+static int derive_checked(const draws_view& v, const derive_kind& kind, const char* source, int32_t nout, const mhx_real* data, size_t ndata,
+                          uint64_t seed, mhx_run** out)
 {
     const char* who = v.who;
     mhx_ctx* ctx = v.ctx;
@@ -36,19 +61,21 @@ static int derive_checked(const draws_view& v, const char* source, int32_t nout,
     if (ndata && !data) return mhx_fail(MHX_EINVAL, "%s: data is NULL", who);
     if (ndata > 0x7fffffffull) return mhx_fail(MHX_EINVAL, "%s: the data block is too large", who);
     if (v.C > 0x7fffffffl) return mhx_fail(MHX_EINVAL, "%s: %ld chains, a run holds fewer than 2^31", who, v.C);
+    if (kind.rng && (unsigned long long)v.N > (1ull << 32))
+        return mhx_fail(MHX_EINVAL, "%s: %ld saved draws, a predictive map numbers them in 32 bits (at most 2^32)", who, v.N);
     HIP_TRY(hipSetDevice(ctx->device));
-    const int U = derive_draws_per_lane(ctx, nout);
+    const int U = derive_draws_per_lane(ctx, kind, nout);
     jit_module* m = nullptr;
     hipFunction_t fn = nullptr;
-    int rc = jit_compile(ctx, derive_source(source), {"MHX_JIT_DERIVE_NOUT=" + std::to_string(nout), "MHX_JIT_DERIVE_DRAWS=" + std::to_string(U)}, &m);
+    int rc = jit_compile(ctx, derive_source(kind, source), {"MHX_JIT_DERIVE_NOUT=" + std::to_string(nout), "MHX_JIT_DERIVE_DRAWS=" + std::to_string(U)}, &m);
     if (rc == MHX_EJIT) {
-        // a diagnostic on the caller's text (derive_source names it derived.hip): the source is the argument at fault, the compiler's
+        // a diagnostic on the caller's text (derive_source names it derived.hip / predictive.hip): the source is the argument at fault, the compiler's
         // log stays in the message.  Any other failure of the compile (no compiler, a module that does not load) stays MHX_EJIT.
         const std::string log = mhx_last_error();
-        if (log.find("derived.hip") != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the map does not compile: %.1900s", who, log.c_str());
+        if (log.find(kind.file) != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the map does not compile: %.1900s", who, log.c_str());
         return rc;
     }
-    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_derive", &fn);
+    if (rc == MHX_OK) rc = jit_function(m, kind.entry, &fn);
     if (rc) return rc;
     std::unique_ptr<mhx_run> r(new mhx_run);
     r->dtype = ctx->dtype;
@@ -56,6 +83,8 @@ static int derive_checked(const draws_view& v, const char* source, int32_t nout,
     r->kind = RUN_DERIVED;
     r->dim = nout;
     r->n = (int)v.C;
+    r->seed = v.seed;
+    r->first_id = v.first_id;
     const size_t bytes = (size_t)v.N * ((size_t)nout + 1) * (size_t)v.C * sizeof(mhx_real);
     rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, bytes, who, "derived sample tensor");
     if (rc) { (void)hipGetLastError(); return rc; }
@@ -71,7 +100,8 @@ static int derive_checked(const draws_view& v, const char* source, int32_t nout,
     int d = v.d1 - 1, nd = (int)ndata;
     const mhx_real* dd = d_data.p;
     const long strip = (long)U * MHX_DERIVE_ROUNDS, nstrips = (N + strip - 1) / strip;
-    void* params[] = {&src, &dst, &N, &C, &d, &dd, &nd};
+    unsigned long long stream_seed = seed, first_id = v.first_id;
+    void* params[] = {&src, &dst, &N, &C, &d, &dd, &nd, &stream_seed, &first_id};        // (mhx_jit_derive takes the first seven)
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)((C + MHX_DERIVE_THREADS - 1) / MHX_DERIVE_THREADS), (unsigned)std::min(nstrips, 65535l), 1,
                                   MHX_DERIVE_THREADS, 1, 1, 0, ctx->stream, params, nullptr));
@@ -94,12 +124,30 @@ int api_ctx_derive(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, in
 {
     draws_view v;
     int rc = draws_of_ctx("mhx_ctx_derive", ctx, d_tensor, n_samples, dim1, nchains, &v);
-    return rc ? rc : derive_checked(v, source, nout, data, ndata, out);
+    return rc ? rc : derive_checked(v, k_derived, source, nout, data, ndata, 0, out);
 }
 
 int api_run_derive(const mhx_run* src, const char* source, int32_t nout, const mhx_real* data, size_t ndata, mhx_run** out)
 {
     draws_view v;
     int rc = draws_of_run("mhx_run_derive", src, &v);
-    return rc ? rc : derive_checked(v, source, nout, data, ndata, out);
+    return rc ? rc : derive_checked(v, k_derived, source, nout, data, ndata, 0, out);
+}
+
+int api_ctx_predict(mhx_ctx* ctx, const mhx_real* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, int64_t first_chain,
+                    const char* source, int32_t nout, const mhx_real* data, size_t ndata, uint64_t seed, mhx_run** out)
+{
+    draws_view v;
+    int rc = draws_of_ctx("mhx_ctx_predict", ctx, d_tensor, n_samples, dim1, nchains, &v);
+    if (rc) return rc;
+    v.seed = seed;                                          // (a caller's tensor has no run to inherit from)
+    v.first_id = (uint64_t)first_chain;
+    return derive_checked(v, k_predictive, source, nout, data, ndata, seed, out);
+}
+
+int api_run_predict(const mhx_run* src, const char* source, int32_t nout, const mhx_real* data, size_t ndata, uint64_t seed, mhx_run** out)
+{
+    draws_view v;
+    int rc = draws_of_run("mhx_run_predict", src, &v);
+    return rc ? rc : derive_checked(v, k_predictive, source, nout, data, ndata, seed, out);
 }

@@ -28,10 +28,12 @@
 #if MHX_REAL64
 typedef double mhx_real;
 #define MHX_R(x) x
+#define MHX_RW(x64, x32) x64                             // a constant that was derived per width (the traced Gamma draws)
 #define MHX_NS mhx_f64
 #else
 typedef float mhx_real;
 #define MHX_R(x) x##f
+#define MHX_RW(x64, x32) x32##f
 #define MHX_NS mhx_f32
 #endif
 #define MHX_RB ((unsigned)sizeof(mhx_real))              // bytes per real
@@ -79,6 +81,28 @@ MHX_NS_BEGIN
     template <class MHX_X, class MHX_Y>                                                                        \
     MHX_DEV void mhx_user_derived(const MHX_X& x, const MHX_Y& y, const int d,                                 \
                                   const mhx_real* __restrict__ data, const int ndata)
+
+// a map of the saved draws that draws random numbers (include/mhx.h, mhx_run_predict; DESIGN.md sections 3.16 and 6.5.6): MHX_DERIVED
+// plus `rng`, the stream of this (chain, saved draw).  Draw k -- k = 0, 1, 2, ... a compile-time constant below 2^20, each k used once --
+// is one call:
+//   rng.draw(k, family, p0, p1)                      family one of MHX_FAMILY_NORMAL, _UNIFORM, _LAPLACE, _CAUCHY, _EXPONENTIAL (p1 unused:
+//                                                    pass 0); the parameters as in Distributions.jl, any mhx_real expression
+//   rng.gamma(k, family, alpha, theta, d, c, inva)   MHX_FAMILY_GAMMA or MHX_FAMILY_INVERSE_GAMMA: alpha a constant, and with it the
+//                                                    Marsaglia-Tsang constants of mhx_fam_comp: a' = alpha < 1 ? alpha + 1 : alpha,
+//                                                    d = a' - 1/3, c = 1 / sqrt(9 d), inva = 1 / alpha, each computed in double from
+//                                                    alpha as rounded to mhx_real and rounded once (mhx.trace emits them as
+//                                                    literals, MHX_RW(fp64 value, fp32 value), so that one text serves both widths)
+// Both return the draw, or NaN where the parameters are not those of a distribution (mhx_fam_valid).  The key is the schedule of
+// seed ^ MHX_PREDICT_SALT; the counter is (global chain id low, high, index t of the saved draw, stream << 28 | block) with block k of
+// stream MHX_STREAM_FAMILY (a Normal draw: mu + sigma * normal 0 of that block's Box-Muller pair) and, for the Gamma families, blocks
+// k << 8 | attempt of streams MHX_STREAM_FAMILY + 1 and + 2 (the attempt loop runs while any active lane of the wave is undecided).
+// A draw is a pure function of (seed, chain id, t, k, parameters): a draw that is not called, or whose value is not used, costs nothing
+// and changes no other draw.
+#define MHX_PREDICT_SALT 0x5052454449435421ull
+#define MHX_PREDICTIVE(x, rng, y, d, data, ndata)                                                              \
+    template <class MHX_X, class MHX_G, class MHX_Y>                                                           \
+    MHX_DEV void mhx_user_predictive(const MHX_X& x, const MHX_G& rng, const MHX_Y& y, const int d,            \
+                                     const mhx_real* __restrict__ data, const int ndata)
 
 // wave-uniform base pointer + 32-bit per-lane BYTE offset: lowers to the scalar-base addressing mode
 // (global_load/store v_off, ..., s[base:base+1]) instead of a 64-bit vector address per access

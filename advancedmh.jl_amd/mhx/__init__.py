@@ -6,7 +6,7 @@ from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposa
                   InverseGamma, IsoGaussian, Laplace, LogDensityModel, MALA, MCMCDistributed, MCMCHIP, MCMCSerial, MCMCThreads, MetropolisHastings, MvNormal, NamedProposals, Normal, RandomWalkProposal,
                   RobustAdaptiveMetropolis, Run, RWMH, StaticMH, StaticProposal, StructArray, combine_diagnostics, StretchProposal,
                   correlation_from_covariance, covariance_from_moments, hpd_ranks, Corner, density_binning_bound, density_from_counts, histogram_edges,
-                  silverman_bandwidth, ACF_TILE, AutocorTable, autocorrelation, integrated_time, HipMap, DerivedRun,
+                  silverman_bandwidth, ACF_TILE, AutocorTable, autocorrelation, integrated_time, HipMap, HipPredictive, DerivedRun,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
                   logdensity, pack_lower, sample, unpack_lower, zeros)
 from . import trace

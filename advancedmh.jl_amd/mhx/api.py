@@ -466,6 +466,13 @@ class HipMap:
         self.data = None if data is None else np.asarray(data, dtype=np.float64).ravel()
 
 
+class HipPredictive(HipMap):
+    """A predictive map of the saved draws as HIP source (Run.predict):  MHX_PREDICTIVE(x, rng, y, d, data, ndata) { y.set(0, rng.draw(0,
+    MHX_FAMILY_NORMAL, x[0], x[1])); }  -- HipMap's x, y, d and data, and rng, the stream of this (chain, saved draw): rng.draw(k, family,
+    p0, p1) / rng.gamma(k, family, alpha, theta, d, c, 1 / alpha) as documented at the macro (csrc/mhx_device_math.h).  The hand-written
+    form of what mhx.trace.trace_predictive records."""
+
+
 class DensityModel:
     """DensityModel(logdensity) -- src/AdvancedMH.jl:52-54.  `logdensity` is a catalogue log-density, HipLogDensity(source, dim),
     or a Python callable of the parameter vector together with `dim`: the callable is traced once (mhx/trace.py) and lowered
@@ -1330,6 +1337,22 @@ class Chains:
         value, _ = run.samples()
         return Chains(value, names + ["lp"], self.start, self.thin, accepted=self.accepted, stats=dict(self.stats), state=run)
 
+    def predict(self, fn, names=None, seed=None):
+        """The chain of posterior predictive draws: `chain.predict(lambda t: mhx.Normal(t.mu, t.sigma), names=["y_rep"]).describe()`.
+        As derive, for a function that draws: it returns distributions (one draw from each) or numbers computed from
+        mhx.trace.draw(dist) values and the parameters; every (chain, saved draw) has a stream of its own, keyed by `seed` (default:
+        the run's) -- Run.predict.  The same call gives the same draws.  Needs the live run."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "predict needs the live run (chain.state)")
+        run = self.state.predict(fn, names=self.params(), seed=seed)
+        if names is None:
+            names = ["predicted"] if run.dim == 1 else ["predicted[%d]" % (j + 1) for j in range(run.dim)]
+        names = [str(n) for n in ([names] if isinstance(names, str) else names)]
+        if len(names) != run.dim:
+            raise L.ArgumentError(L.MHX_EINVAL, "predict: %d names for %d outputs" % (len(names), run.dim))
+        value, _ = run.samples()
+        return Chains(value, names + ["lp"], self.start, self.thin, accepted=self.accepted, stats=dict(self.stats), state=run)
+
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
         return "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
@@ -1862,22 +1885,47 @@ class Run:
         not change it.  fn: a Python callable of the parameter vector (with lp=True: of the vector and the draw's lp) that returns
         one number or a list of them -- traced once by mhx.trace.trace_map, `names` (default: the model's parameter names) making
         the vector answer to theta.<name> --, a TracedMap, or a HipMap(source, nout, data).  nout: checked against the map's."""
-        if names is None and getattr(self, "model", None) is not None:
-            names = getattr(self.model, "param_names", None)
-        if not isinstance(fn, (HipMap, _trace.TracedMap)):
-            if not callable(fn):
-                raise L.ArgumentError(L.MHX_EINVAL, "derive: a callable, a TracedMap or a HipMap is needed, got %r" % (fn,))
-            try:
-                fn = _trace.trace_map(fn, self.dim, names=names, lp=lp)
-            except _trace.TraceError as e:
-                raise L.ArgumentError(L.MHX_EINVAL, "derive: the callable cannot be traced: %s" % e) from e
-        if isinstance(fn, _trace.TracedMap) and fn.dim != self.dim:
-            raise L.ArgumentError(L.MHX_EINVAL, "derive: the map was traced for %d parameters, the run has %d" % (fn.dim, self.dim))
-        if nout is not None and int(nout) != fn.nout:
-            raise L.ArgumentError(L.MHX_EINVAL, "derive: nout = %d, the map has %d outputs" % (int(nout), fn.nout))
-        data = None if fn.data is None else self.ctx.arr(fn.data)
+        fn, data = self._map("derive", fn, nout, names, lp, False)
         h = C.c_void_p()
         L.check(L.lib().mhx_run_derive(self.h, fn.source.encode(), fn.nout, L.rptr(data), 0 if data is None else data.size, C.byref(h)))
+        return DerivedRun(h, self, fn.nout)
+
+    def _map(self, who, fn, nout, names, lp, predictive):
+        """the map of derive / predict, traced where it is a callable, and its data block as the library takes it"""
+        if names is None and getattr(self, "model", None) is not None:
+            names = getattr(self.model, "param_names", None)
+        got = fn
+        if isinstance(fn, (HipMap, _trace.TracedMap)):      # a recorded or hand-written map: of this entry's kind?
+            if isinstance(fn, (HipPredictive, _trace.TracedPredictive)) != predictive:
+                fn = None
+        elif callable(fn):
+            try:
+                fn = (_trace.trace_predictive if predictive else _trace.trace_map)(fn, self.dim, names=names, lp=lp)
+            except _trace.TraceError as e:
+                raise L.ArgumentError(L.MHX_EINVAL, "%s: the callable cannot be traced: %s" % (who, e)) from e
+        else:
+            fn = None
+        if fn is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: a callable, a %s or a %s is needed, got %r" % (
+                who, "TracedPredictive" if predictive else "TracedMap", "HipPredictive" if predictive else "HipMap", got))
+        if isinstance(fn, _trace.TracedMap) and fn.dim != self.dim:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: the map was traced for %d parameters, the run has %d" % (who, fn.dim, self.dim))
+        if nout is not None and int(nout) != fn.nout:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: nout = %d, the map has %d outputs" % (who, int(nout), fn.nout))
+        return fn, None if fn.data is None else self.ctx.arr(fn.data)
+
+    def predict(self, fn, nout=None, names=None, lp=False, seed=None):
+        """Posterior predictive draws on the device (mhx_run_predict): derive for a map that draws random
+        numbers, with a DerivedRun as the result.  fn: a Python callable that returns distributions (`lambda t: mhx.Normal(t.mu,
+        t.sigma)`: one draw from each), numbers computed from `mhx.trace.draw(dist)` values and the parameters, or a mix -- traced
+        once by mhx.trace.trace_predictive --, a TracedPredictive, or a HipPredictive(source, nout, data).  seed: the key of the
+        streams, default this run's own (the salt of the spec keeps them apart from the sampler's); every (chain, saved draw, draw
+        index) has its own numbers and the same call gives the same bits."""
+        fn, data = self._map("predict", fn, nout, names, lp, True)
+        seed = self.seed if seed is None else int(seed)
+        h = C.c_void_p()
+        L.check(L.lib().mhx_run_predict(self.h, fn.source.encode(), fn.nout, L.rptr(data), 0 if data is None else data.size,
+                                        seed & 0xffffffffffffffff, C.byref(h)))
         return DerivedRun(h, self, fn.nout)
 
     def close(self):

@@ -31,7 +31,7 @@ import math
 import numpy as np
 
 __all__ = ["log", "exp", "sqrt", "abs", "fma", "where", "minimum", "maximum", "square", "sum_over", "trace", "Traced", "Sym", "Vec", "NamedVec", "TraceError",
-           "trace_proposal", "TracedProposal", "trace_map", "TracedMap"]
+           "trace_proposal", "TracedProposal", "trace_map", "TracedMap", "draw", "trace_predictive", "TracedPredictive"]
 
 
 class TraceError(TypeError):
@@ -46,6 +46,7 @@ class _Graph:
         self.index = {}
         self.loops, self.data, self.data_len, self.in_loop = [], [], 0, None      # sum_over: rows, offsets into the data block
         self.loop_group = {}            # loop node -> group key (the loops of one group are emitted as one)
+        self.draws = None               # trace_predictive: [(family, p0, p1)] per draw index, None where the parameter is traced
 
     def node(self, op, *args):
         key = (op,) + args
@@ -546,6 +547,8 @@ class Traced:
             return []
         if op == "loop":
             return [key[2]]
+        if op == "draw":                                      # (draw index, family, p0, p1)
+            return list(key[3:])
         if op == "sel":
             d = list(key[2:])
             self._cond_nodes(key[1], d)
@@ -591,6 +594,8 @@ class Traced:
             return "mhx_fma(%s, %s, %s)" % tuple(name(v) for v in a)
         if op == "sel":
             return "%s ? %s : %s" % (self._cond_src(a[0], name), name(a[1]), name(a[2]))
+        if op == "draw":
+            return self._draw_src(a, name)
         raise AssertionError(op)
 
     def _body(self, roots):
@@ -686,6 +691,8 @@ class Traced:
             return _fma_float(float(val[a[0]]), float(val[a[1]]), float(val[a[2]]))
         if op == "sel":
             return val[a[1]] if cond(a[0]) else val[a[2]]
+        if op == "draw":
+            return self._draw_fn(a[0], a[1], (val[a[2]], val[a[3]]))
         raise AssertionError(op)
 
     def _run(self, x, roots):
@@ -781,6 +788,8 @@ class TracedMap(Traced):
     the draw's lp), `.data` (the rows of its sum_over loops or None), `.evaluate(x)` ([nout] float64 of the same program in numpy
     float64, for checks; with lp the draw's lp is x[dim], or the second argument)."""
 
+    _what, _head = "a map of the draws", "MHX_DERIVED(x, y, d, data, ndata)"
+
     def __init__(self, g, outs, dim, lp=False):
         self.g, self.dim, self.lp = g, int(dim), bool(lp)
         self._ld = {}
@@ -789,9 +798,9 @@ class TracedMap(Traced):
         self.nout = len(self.outs)
         self.data = np.concatenate(g.data) if g.data else None
         lines, name = self._body(self.outs)
-        src = ["// traced by mhx.trace (advancedmh.jl_amd/mhx/trace.py): a map of the draws, %d outputs, %d operations in the source%s" % (
-                   self.nout, self._nops, "" if self.data is None else "; data block of %d reals" % self.data.size),
-               "MHX_DERIVED(x, y, d, data, ndata)", "{"] + lines
+        src = ["// traced by mhx.trace (advancedmh.jl_amd/mhx/trace.py): %s, %d outputs, %d operations in the source%s" % (
+                   self._what, self.nout, self._nops, "" if self.data is None else "; data block of %d reals" % self.data.size),
+               self._head, "{"] + lines
         src += ["    y.set(%d, %s);" % (j, name(i)) for j, i in enumerate(self.outs)] + ["}"]
         self.source = "\n".join(src) + "\n"
 
@@ -808,6 +817,10 @@ def trace_map(fn, dim, names=None, lp=False):
     """Run `fn` once on a vector of `dim` traced parameters -- the Vec (with `names`: the NamedVec) a log-density gets; with lp=True
     the call is fn(theta, lp), lp the draw's log-density -- and return the recorded map (a `TracedMap`).  `fn` returns one traced
     number, or a list, tuple or Vec of them; plain numbers are constants.  Everything `trace` takes is taken here."""
+    return _trace_map(fn, dim, names, lp, TracedMap)
+
+
+def _trace_map(fn, dim, names, lp, cls):
     dim = int(dim)
     if dim < 1:
         raise TraceError("dim must be >= 1")
@@ -815,17 +828,21 @@ def trace_map(fn, dim, names=None, lp=False):
         raise TraceError("names: %d given for %d parameters" % (len(names), dim))
     g = _Graph()
     g.node("c", _const_key(0.0))        # node 0, as in trace
+    if cls is TracedPredictive:
+        g.draws = []
     x = [Sym(g, g.node("x", k)) for k in range(dim)]
     x = NamedVec(x, names) if names is not None else Vec(x)
     _ACTIVE.append(g)
     try:
         out = fn(x, Sym(g, g.node("x", dim))) if lp else fn(x)        # (x[dim] is the draw's lp)
+        if isinstance(out, Vec):
+            out = list(out.items)
+        elif not isinstance(out, (list, tuple)):
+            out = [out]
+        if g.draws is not None:                                       # an output that is a distribution is a draw from it
+            out = [draw(v) if hasattr(v, "family") or hasattr(v, "nu") else v for v in out]
     finally:
         _ACTIVE.pop()
-    if isinstance(out, Vec):
-        out = list(out.items)
-    elif not isinstance(out, (list, tuple)):
-        out = [out]
     if not out:
         raise TraceError("a map must return at least one number")
     outs = []
@@ -838,7 +855,7 @@ def trace_map(fn, dim, names=None, lp=False):
         if v.g is not g:
             raise TraceError("output %d of the map belongs to another trace" % j)
         outs.append(v.i)
-    return TracedMap(g, outs, dim, lp)
+    return cls(g, outs, dim, lp)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1005,3 +1022,85 @@ def trace_composite(entries):
         _lower_components(g, out, first, sets, table, where)
         first += n
     return TracedComposite(g, sets, table, dim)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# posterior predictive draws (mhx_run_predict, DESIGN.md sections 3.16 and 6.5.6): a map of the saved draws that draws
+
+MAX_DRAWS = 1 << 20                     # the Gamma blocks are numbered draw << 8 | attempt in 28 bits
+
+
+def draw(dist):
+    """One draw from `dist` -- anything with `.family` (an mhx family id) and `.params()`, as a function proposal returns; TDist(1) is
+    Cauchy(0, 1) -- inside a predictive trace (trace_predictive, Run.predict): a traced number that can be returned, combined with
+    others, or fed into the parameters of a later draw.  Parameters are numbers or traced expressions; the shape of a Gamma family
+    is a number.  The k-th call during the trace is draw index k, whether or not its value is used."""
+    if not _ACTIVE:
+        raise TraceError("draw: no predictive trace is active (draw is for the function given to trace_predictive / Run.predict)")
+    g = _ACTIVE[-1]
+    if g.draws is None:
+        raise TraceError("draw: this is not a predictive trace (a log-density, a derived map and a proposal's parameter map have no "
+                         "random stream): use trace_predictive / Run.predict")
+    if g.in_loop is not None:
+        raise TraceError("draw inside sum_over is not supported (the draw index must be a compile-time constant)")
+    k = len(g.draws)
+    if k >= MAX_DRAWS:
+        raise TraceError("more than 2^20 draws in one map (the Gamma blocks are numbered draw << 8 | attempt)")
+    sets, table = [], []
+    _lower_components(g, [dist], k, sets, table, "draw: ")
+    fam = table[0][0]
+    traced = {j: i for _, j, i in sets}
+    consts = [None if j in traced else table[0][1 + j] for j in range(2)]
+    if fam in (_FAM_GAMMA, _FAM_INVERSE_GAMMA):
+        al = consts[0]
+        al32 = float(np.float32(al)) if math.isfinite(al) else al
+        if not (math.isfinite(al) and al > 0.0 and al32 > 0.0 and math.isfinite(al32) and math.isfinite(1.0 / al32)):
+            raise TraceError("draw: component %d: %s(alpha, theta) needs a finite alpha > 0 that stays one in both widths, got %r" % (
+                k, _FAMILY_NAMES[fam], al))
+    g.draws.append((fam, consts[0], consts[1]))
+    args = [traced[j] if j in traced else g.node("c", _const_key(consts[j])) for j in range(2)]
+    return Sym(g, g.node("draw", k, fam, args[0], args[1]))
+
+
+def gamma_constants(alpha, width):
+    """(alpha, d, c, 1 / alpha) of a Gamma family's row as api_rwmh_create_components derives them: from alpha AS ROUNDED to the width
+    (64 or 32), in double, each rounded once to the width"""
+    R = np.float64 if width == 64 else np.float32
+    al = float(R(alpha))
+    ae = al + 1.0 if al < 1.0 else al
+    dd = ae - 1.0 / 3.0
+    return tuple(float(R(v)) for v in (al, dd, 1.0 / math.sqrt(9.0 * dd), 1.0 / al))
+
+
+class TracedPredictive(TracedMap):
+    """The recorded predictive map: a TracedMap whose program holds draw nodes.  `.source` is MHX_PREDICTIVE(x, rng, y, d, data, ndata),
+    `.ndraws` the number of draw indices, `.draws` [(family, (p0, p1))] per index with None where the parameter is traced.
+    `.evaluate(x, draw_fn, lp=None)` runs the program in numpy float64 with draw_fn(k, family, (p0, p1)) supplying draw k."""
+    _what, _head = "a predictive map of the draws", "MHX_PREDICTIVE(x, rng, y, d, data, ndata)"
+
+    def __init__(self, g, outs, dim, lp=False):
+        self.draws = [(f, (p0, p1)) for f, p0, p1 in g.draws]
+        self.ndraws = len(self.draws)
+        TracedMap.__init__(self, g, outs, dim, lp)
+
+    def _draw_src(self, a, name):
+        k, fam, p0, p1 = a
+        if fam not in (_FAM_GAMMA, _FAM_INVERSE_GAMMA):
+            return "rng.draw(%d, %d, %s, %s)" % (k, fam, name(p0), name(p1))
+        alpha = float.fromhex(self.g.nodes[p0][1])
+        c64, c32 = gamma_constants(alpha, 64), gamma_constants(alpha, 32)
+        return "rng.gamma(%d, %d, %s, %s, %s)" % (k, fam, name(p0), name(p1), ", ".join(
+            "MHX_RW(%s, %s)" % (c64[j].hex(), c32[j].hex()) for j in (1, 2, 3)))
+
+    def evaluate(self, x, draw_fn, lp=None):
+        self._draw_fn = draw_fn
+        try:
+            return TracedMap.evaluate(self, x, lp)
+        finally:
+            del self._draw_fn
+
+
+def trace_predictive(fn, dim, names=None, lp=False):
+    """trace_map for a function that may call `draw`: returns the recorded predictive map (a `TracedPredictive`).  An output that is
+    itself a distribution is shorthand for draw(dist), so `lambda t: Normal(t.mu, t.sigma)` is a complete predictive map."""
+    return _trace_map(fn, dim, names, lp, TracedPredictive)

@@ -89,7 +89,7 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   HPD_SCRATCH_MB (bound, in MiB, on the device scratch of a call of mhx_*_hpd: the rows go in batches that fit;
  *                   default 1024; a positive number, fractions allowed; read at every call)
  *                   ACF_R (8 | 16 | 32 lags per tile of mhx_*_autocovariance; default: the fastest measured per width; read at every call)
- *                   DERIVE_DRAWS (1..16 draws a lane of mhx_*_derive maps together; default 4; never more than the outputs leave registers for; read at every call)
+ *                   DERIVE_DRAWS (1..16 draws a lane of mhx_*_derive / mhx_*_predict maps together; default 4 / 1; never more than the outputs leave registers for; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
  * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
@@ -832,7 +832,7 @@ int mhx_ctx_autocovariance(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples
  * mhx_run_destroy, lives on the context of `src` (destroy it first), and may itself be a `src`.  On a derived run
  *   work      mhx_run_device_samples (accepted = NULL), mhx_run_get_samples (accepted must be NULL: MHX_EINVAL otherwise),
  *             mhx_run_stats (no transitions; kernel_ms = the map's launch, kernel_variant = -1), mhx_run_form_name ("derived"),
- *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_group_attach, and every post-run statistic:
+ *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_run_predict, mhx_group_attach, and every post-run statistic:
  *             mhx_run_diagnostics, _ess_bulk_tail, _rank_diagnostics, _rank_scores, _order_statistics, _select_histogram, _cross_moments,
  *             _hpd, _histogram, _histogram2d, _autocovariance
  *   refuse    with MHX_ESTATE and a message that says the run is derived, before anything else is looked at: mhx_run_init, _sample,
@@ -853,6 +853,34 @@ int mhx_run_derive(const mhx_run *src, const char *source, int32_t nout, const v
  * the last row is copied as lp; the derived run lives on ctx */
 int mhx_ctx_derive(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                    const char *source, int32_t nout, const void *data, size_t ndata, mhx_run **out);
+
+/* Posterior predictive draws: mhx_run_derive for a map that draws random numbers (DESIGN.md sections 3.16 and 6.5.6) -- Turing's
+ * predict / generated_quantities with a rand in it: y_rep ~ Normal(mu, sigma) for every saved draw.  `source` is HIP source of the form
+ *     MHX_PREDICTIVE(x, rng, y, d, data, ndata) { y.set(0, rng.draw(0, MHX_FAMILY_NORMAL, x[0], x[1])); }
+ * x, y, d, data and ndata as for MHX_DERIVED; rng is the stream of this (chain, saved draw).  Draw k -- k = 0, 1, 2, ... a compile-time
+ * constant below 2^20, each used once -- is rng.draw(k, family, p0, p1) for Normal, Uniform, Laplace, Cauchy and Exponential (p1 = 0)
+ * with the parameters of Distributions.jl, or rng.gamma(k, family, alpha, theta, d, c, 1 / alpha) for Gamma and InverseGamma with a
+ * constant shape and the Marsaglia-Tsang constants of csrc/mhx_device_math.h (documented there at the macro; mhx.trace.trace_predictive
+ * emits them).  A parameter is any mhx_real expression: of x, of data, of an earlier draw.
+ * The arithmetic: key = the Philox schedule of seed ^ MHX_PREDICT_SALT (0x5052454449435421); counter = (global chain id low word, high
+ * word, index t of the saved draw, stream << 28 | block), the id first_id + chain as the samplers form it.  Draw k takes block k of
+ * stream 8 (MHX_STREAM_FAMILY): a Normal draw is mu + sigma * (normal 0 of that block's Box-Muller pair) -- NOT the shared normal stream
+ * of the proposals --, the other families spend the block as the proposal components do; the Gamma families take blocks k << 8 | attempt
+ * of streams 9 and 10.  Parameters that are not a distribution's (a scale <= 0, a >= b, NaN, Inf) give NaN where the reference would
+ * throw; a NaN propagates through what reads it.  A draw is a pure function of (seed, global chain id, t, k, parameters): the same call
+ * twice gives the same bits, whatever the grid, the chain blocks or DERIVE_DRAWS (default 1 for these maps).
+ * `seed` is taken as given (the host layers pass the run's own unless told otherwise; with the salt the map does not replay the words
+ * the run's proposals consumed).  *out is a derived run exactly as mhx_run_derive makes it -- row nout the lp row of `src`, a snapshot,
+ * the same entries work on it and the same refuse it, it may be the `src` of either call.  A derived run inherits seed and first_id
+ * from its source, so a predictive map of a derived run uses the original chains' ids.  Errors as mhx_run_derive (a compiler
+ * diagnostic names the text predictive.hip); also MHX_EINVAL for n_saved > 2^32 (t is one counter word).  Blocking. */
+int mhx_run_predict(const mhx_run *src, const char *source, int32_t nout, const void *data, size_t ndata,
+                    uint64_t seed, mhx_run **out);
+/* the same on a caller's device tensor; first_chain: the global id of the tensor's chain 0 (what the derived run inherits as first_id,
+ * with seed) */
+int mhx_ctx_predict(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                    int64_t first_chain, const char *source, int32_t nout, const void *data, size_t ndata,
+                    uint64_t seed, mhx_run **out);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
