@@ -632,12 +632,6 @@ static int kernel_lds_limit(const void* fn, size_t lds_bytes, const char* what)
         return mhx_fail(MHX_EHIP, "%s: %zu bytes of LDS refused", what, lds_bytes);
     return MHX_OK;
 }
-// the kernel `name` of a run-time module, allowed `lds_bytes` of dynamic LDS
-static int jit_kernel(jit_module* m, const char* name, hipFunction_t* fn, size_t lds_bytes, const char* what)
-{
-    const int rc = jit_function(m, name, fn);
-    return rc ? rc : kernel_lds_limit((const void*)*fn, lds_bytes, what);
-}
 
 // ---------------------------------------------------------------------------------------------
 // targets
@@ -851,6 +845,54 @@ enum kernel_form {
     KF_COMPOSITE = 15,      // ... and whose kind, symmetric flag and parameter map vary per block of components (a composite proposal)
 };
 
+// One kernel of a run, ready to launch: everything the host needs for it, filled ONCE, in the branch of a create function that
+// chooses the run's form, and launched by `launch` below.  No sampling call works a grid, a block size or an
+// LDS size out again, and a new kernel form adds one record where it is chosen.
+#define MHX_LAUNCH_MAX_TAIL 10
+struct launch_rec {
+    const void* fn = nullptr;            // the kernel: a pre-built __global__ function, or
+    hipFunction_t mod_fn = nullptr;      // ... a kernel of a run-time module
+    unsigned block = 64;                 // threads per block
+    size_t lds = 0;                      // dynamic LDS bytes: the size rec_bind had the kernel allowed IS the size launched
+    int per_block = 64;                  // chains (walkers) per block
+    unsigned grid_round = 1;             // the grid is rounded up to a multiple of this (8: the kernels with an XCD-aware block -> chain map)
+    void* tail[MHX_LAUNCH_MAX_TAIL] = {};   // the arguments after the per-launch block: ADDRESSES of members of the run, whose values are
+    int ntail = 0;                          // fixed for its life (tp, d_pvec, d_fam, ...)
+    const char* what = "";               // for messages
+    explicit operator bool() const { return fn || mod_fn; }
+};
+static launch_rec rec_shape(const char* what, unsigned block, int per_block, size_t lds, std::initializer_list<const void*> tail, unsigned grid_round = 1)
+{
+    launch_rec k;
+    k.what = what; k.block = block; k.per_block = per_block; k.lds = lds; k.grid_round = grid_round;
+    for (const void* p : tail) k.tail[k.ntail++] = const_cast<void*>(p);
+    return k;
+}
+// the record's kernel: a pre-built function / the kernel `name` of a run-time module, allowed the record's own LDS size
+static int rec_bind(launch_rec* k, const void* fn)
+{
+    k->fn = fn; k->mod_fn = nullptr;
+    return kernel_lds_limit(fn, k->lds, k->what);
+}
+static int rec_bind(launch_rec* k, jit_module* m, const char* name)
+{
+    k->fn = nullptr;
+    const int rc = jit_function(m, name, &k->mod_fn);
+    return rc ? rc : kernel_lds_limit((const void*)k->mod_fn, k->lds, k->what);
+}
+// launch it for `n_items` chains (walkers), `grid_y` ensembles; `args_block`: the kernel's first argument, the per-launch block
+static int launch(const launch_rec& k, hipStream_t s, long n_items, unsigned grid_y, void* args_block)
+{
+    if (!k) return mhx_fail(MHX_ESTATE, "%s: the run holds no such kernel", k.what);
+    void* params[1 + MHX_LAUNCH_MAX_TAIL] = {args_block};
+    for (int i = 0; i < k.ntail; ++i) params[1 + i] = k.tail[i];
+    unsigned grid = (unsigned)((n_items + k.per_block - 1) / k.per_block);
+    grid = (grid + k.grid_round - 1) / k.grid_round * k.grid_round;
+    if (k.mod_fn) HIP_TRY(hipModuleLaunchKernel(k.mod_fn, grid, grid_y, 1, k.block, 1, 1, (unsigned)k.lds, s, params, nullptr));
+    else HIP_TRY(hipLaunchKernel(k.fn, dim3(grid, grid_y), dim3(k.block), params, k.lds, s));
+    return MHX_OK;
+}
+
 struct mhx_run : mhx_handle_hdr {
     mhx_ctx* ctx = nullptr;
     const mhx_target* target = nullptr;
@@ -867,19 +909,19 @@ struct mhx_run : mhx_handle_hdr {
     mhx_real* d_pvec = nullptr;
     // emcee
     mhx_real stretch = MHX_R(2.0);
-    size_t dense_lds = 0;                // dynamic LDS bytes of the dense cooperative RWMH kernel
     mhx_real* d_xw = nullptr;               // walker-major copy [W][round4(dim)]: the state while the cooperative kernel runs
     mhx_real* d_pmean = nullptr;            // drifting walk: mu[dim] then 2 L^-1 mu [dim]
-    mhx_real* d_mfma_img = nullptr;         // streamed matrix-core kernel: the operand images [target][proposal] in global memory
-    bool mfma_stream = false;
+    mhx_real* d_mfma_img = nullptr;         // streamed matrix-core kernels: the operand images [target][proposal] in global memory
+    mhx_real* d_mfma_img2 = nullptr;        // ... the second of them (inside d_mfma_img: not freed)
     mhx_real* d_qx = nullptr;               // static proposal: logpdf of the proposal at each chain's state (up to its constant)
     mhx_fam_comp* d_fam = nullptr;          // KF_FAMILY: the component table [dim]
-    bool fam_reg = false;                   // ... stepped by the specialised register form (jit_step), else by the state-in-HBM form
+    bool fam_reg = false;                   // ... stepped by the specialised register form, else by the state-in-HBM form (sizes d_cond_p; stats)
     int fam_symmetric = 0;                  // ... a random walk declared symmetric: no ratio
     // KF_COND (mhx_api_cond.inc): d_fam, fam_reg and fam_symmetric as above, and
     std::string cond_src;                   // the parameter map's source (MHX_PROPOSAL_PARAMS)
     mhx_real* d_cond_data = nullptr;        // its data block
     int cond_ndata = 0;
+    int cond_static = 0;                    // MHX_FLAG_STATIC_PROPOSAL, as the state-in-HBM form's argument
     mhx_real* d_cond_p = nullptr;           // [2 dim][n] p(x) of the check kernel; the state-in-HBM form: [4 dim][n], p(x) then p(y)
     int* d_cond_bad = nullptr;              // chains whose p(x) the last check found invalid
     hipFunction_t jit_cond_check = nullptr;
@@ -933,31 +975,29 @@ struct mhx_run : mhx_handle_hdr {
     size_t mom_cap = 0, mom_cap2 = 0;
     uint64_t mom_n = 0;                  // states folded in so far
     bool moments_mode = false;
-    void (*reg_fn_mom)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;
-    hipFunction_t jit_step_mom = nullptr;
     std::vector<std::string> coop_defs;  // defines of the cooperative kernel (its moments twin differs in MHX_JIT_MOM)
-    // kernel choice
+    // kernel choice: the form (variant) and the launch records of its kernels.  The records' trailing arguments point INTO this
+    // struct (k_tp and the members named at launch_rec::tail): a run is never copied or moved
+    const mhx_real* k_tp = nullptr;      // target->dparams, as a kernel argument (run_alloc_state)
+    launch_rec step;                     // the step kernel (an ensemble: the half-step, or the sequential sweep)
+    launch_rec step_k8;                  // KF_WAVE: the K = 8 build of the wave-per-chain kernel
+    launch_rec step_mom;                 // KF_COOP / KF_COOP_JIT: the running-moments twin (pre-built, or built by the first MHX_SAVE_MOMENTS call)
+    launch_rec sweep;                    // an ensemble: the stretch move as ONE launch per sweep (mhx_emcee_coop_sweep_body); state double-buffered
+    launch_rec persist;                  // ... a small one as one persistent block (mhx_emcee_persist_body): a whole call per launch
+    bool sweep_mixed = false;            // ... the sweep kernel's blocks take walkers of both halves (scalar-factor form), not one half each
     int normal_gen = MHX_GEN_BOX_MULLER; // how stream bits become standard normals (MHX_FLAG_ZIGGURAT: the table ziggurat, fp64)
-    size_t reg_lds = 0;                  // dynamic LDS of the register kernel: the tail of a state that does not fit beside the candidate
-    bool coop_pairs = false;             // the cooperative kernel as generator / consumer wave pairs: 512-thread blocks (not the moments twin)
-    size_t coop_lds = 0;                 // dynamic LDS of the cooperative kernel (ziggurat: layer table + the step's normals)
-    int coop_tr = 0;                     // ... and whether it holds the row-transposition buffer of the one / two-chains-per-wave shapes
+    bool coop_pairs = false;             // the cooperative kernel as generator / consumer wave pairs (the form's name; not the moments twin)
+    int coop_tr = 0;                     // the cooperative kernel's LDS holds the row-transposition buffer of the one / two-chains-per-wave shapes
     int coop_L = 1;                      // lanes per chain (reduction shape of the separable targets)
     int emcee_band = -1;                 // bandwidth of the precision factor the cooperative stretch move exploits (-1: dense form)
     int coop_waves = MHX_EMCEE_COOP_WAVES;  // waves per block of the cooperative stretch move (tuning knob MHX_EMCEE_WAVES)
     size_t emcee_stamp_words = 0;        // MHX_EMCEE_STAMPS (tools): 64-bit words of the stamp buffer in d_ybuf
     int emcee_wpb = 64;                  // walkers per block of the scalar-factor form
-    hipFunction_t jit_persist = nullptr; // a small ensemble as one persistent block (mhx_emcee_persist_body): a whole call per launch
-    size_t persist_lds = 0;
-    hipFunction_t jit_sweep = nullptr;   // the stretch move as ONE launch per sweep (mhx_emcee_coop_sweep_body); state double-buffered:
-    mhx_real *d_xw2 = nullptr, *d_lp2 = nullptr;   // ... the buffers the next sweep writes (swapped with d_xw / d_lp after every launch)
-    size_t sweep_lds = 0;
+    mhx_real *d_xw2 = nullptr, *d_lp2 = nullptr;   // the buffers the next launch of `sweep` writes (swapped with d_xw / d_lp after every launch)
     bool emcee_preload = false;          // the half-step kernel takes its hot arguments as preloaded scalars (MHX_JIT_PRELOAD)
     int variant = KF_GENERIC;            // kernel_form
-    void (*reg_fn)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;
-    void (*reg_fn8)(const mhx_rwmh_args, const mhx_real*, const mhx_real*) = nullptr;   // KF_WAVE: the K = 8 build of the wave-per-chain kernel
     int wave_k = 4;                      // KF_WAVE: candidates per round of the next call (8 after a call that accepted < 1 step in 8)
-    hipFunction_t jit_step = nullptr, jit_init = nullptr;
+    hipFunction_t jit_init = nullptr;    // a user target's initial kernel (256 threads, no LDS)
     mhx_stats stats{};
     mhx_host_stats host_stats{};         // what the last mhx_run_sample_to_host moved
 
@@ -974,6 +1014,7 @@ struct mhx_run : mhx_handle_hdr {
 static int run_alloc_state(mhx_run* r)
 {
     const size_t n = (size_t)r->n, d = (size_t)r->dim;
+    r->k_tp = r->target->dparams;
     HIP_TRY(hipMalloc(&r->d_x, d * n * sizeof(mhx_real)));
     HIP_TRY(hipMalloc(&r->d_lp, n * sizeof(mhx_real)));
     HIP_TRY(hipMalloc(&r->d_acc, n * sizeof(uint32_t)));
@@ -1164,6 +1205,10 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     // ---- kernel choice
     r->variant = KF_GENERIC;
     const int tk = t->kind, pk = r->prop_kind;
+    // a launch record of this sampler: kernel(args, tparams, pvec)
+    auto rec = [&](const char* what, unsigned block, int per_block, size_t lds, unsigned grid_round = 1) {
+        return rec_shape(what, block, per_block, lds, {&r->k_tp, &r->d_pvec}, grid_round);
+    };
     // (fp32, round 6: 256 layers, one Philox word per normal -- on the cooperative kernel, the register kernel and MALA's register kernel
     // like fp64; the check at the end of this function refuses a run whose kernel has no ziggurat form)
     if ((cfg->flags & MHX_FLAG_ZIGGURAT) && d >= (1 << 20))      // the retry blocks are numbered (normal index << 8 | attempt) in 28 bits
@@ -1179,8 +1224,9 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     if (tk == MHX_TARGET_IID_NORMAL && d == 2 && pk != MHX_PROP_DENSE && walk == MHX_WALK_PLAIN &&
         !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_ZIGGURAT)) &&
         (cfg->reduce_lanes == 64 || (cfg->reduce_lanes == 0 && t->nparams >= 8 && chains_of_whole_run(ctx, r->n) <= 2048))) {
-        r->reg_fn = pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 4> : k_rwmh_wave<MHX_PROP_DIAG, 4>;
-        r->reg_fn8 = pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 8> : k_rwmh_wave<MHX_PROP_DIAG, 8>;
+        r->step = r->step_k8 = rec("wave-per-chain kernel", 64, 1, 0);
+        if ((rc = rec_bind(&r->step, (const void*)(pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 4> : k_rwmh_wave<MHX_PROP_DIAG, 4>)))) return rc;
+        if ((rc = rec_bind(&r->step_k8, (const void*)(pk == MHX_PROP_ISO ? k_rwmh_wave<MHX_PROP_ISO, 8> : k_rwmh_wave<MHX_PROP_DIAG, 8>)))) return rc;
         r->variant = KF_WAVE;
         r->coop_L = 64;
     } else if (tk == MHX_TARGET_IID_NORMAL && cfg->reduce_lanes > 1) {
@@ -1226,9 +1272,10 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_mfma_kernels.h"),
                              {"MHX_JIT_RWMH_MFMA=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_PK=" + std::to_string(pk),
                               "MHX_JIT_TK=" + std::to_string(tk), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
-            r->dense_lds = nimg * mfma_image_reals(d) * sizeof(mhx_real);
-            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_mfma", &r->jit_step, r->dense_lds, "matrix-core kernel");
-            if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; }
+            // 16 chains per wave, the images resident in LDS
+            launch_rec k = rec("matrix-core kernel", 64 * MHX_MFMA_WAVES, 16 * MHX_MFMA_WAVES, nimg * mfma_image_reals(d) * sizeof(mhx_real));
+            if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_rwmh_mfma");
+            if (rc == MHX_OK) { r->step = k; r->variant = KF_MFMA; r->coop_L = 4; }
         }
         if (r->variant == KF_GENERIC && mfma_stream_fits(ctx, d, cfg->reduce_lanes)) {
             // the images do not fit a block's LDS: they stay in global memory (built once, here) and every block walks them
@@ -1243,12 +1290,15 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
                               std::string("MHX_JIT_XMEM=") + (smode == 2 ? "1" : "0")}, &m,
                              {"-mllvm", "-pragma-unroll-threshold=4000000"});
             hipFunction_t fimg = nullptr;
-            r->dense_lds = mfma_ring_bytes(d, smode == 1);
+            // the same geometry, the LDS is the ring; the kernel takes the two images after the usual arguments
+            launch_rec k = rec_shape("streamed matrix-core kernel", 64 * MHX_MFMA_WAVES, 16 * MHX_MFMA_WAVES, mfma_ring_bytes(d, smode == 1),
+                                     {&r->k_tp, &r->d_pvec, &r->d_mfma_img, &r->d_mfma_img2});
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mfma_image", &fimg);
-            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_mfma_stream", &r->jit_step, r->dense_lds, "streamed matrix-core kernel");
+            if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_rwmh_mfma_stream");
             if (rc == MHX_OK) {
                 const size_t reals = mfma_image_reals(d);
                 HIP_TRY(hipMalloc(&r->d_mfma_img, 2 * reals * sizeof(mhx_real)));
+                r->d_mfma_img2 = r->d_mfma_img + reals;
                 HIP_TRY(hipMemsetAsync(r->d_mfma_img, 0, 2 * reals * sizeof(mhx_real), ctx->stream));
                 const mhx_real* srcs[2] = {tk == MHX_TARGET_CORR_GAUSS ? t->dparams : nullptr, pk == MHX_PROP_DENSE ? r->d_pvec : nullptr};
                 for (int im = 0; im < 2 && rc == MHX_OK; ++im) {
@@ -1259,8 +1309,7 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
                 }
                 if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(ctx->stream));
             }
-            if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->mfma_stream = true; }
-            else { r->jit_step = nullptr; }
+            if (rc == MHX_OK) { r->step = k; r->variant = KF_MFMA; r->coop_L = 4; }
         }
         // reduce_lanes = 4 asked for explicitly and a matrix-core kernel was tried but did not come up: the error is the
         // caller's, like every other explicit reduce_lanes (no silent change of the summation shape)
@@ -1274,9 +1323,9 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_dense_kernels.h"),
                          {"MHX_JIT_RWMH_DENSE=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_L=" + std::to_string(L),
                           "MHX_JIT_PK=" + std::to_string(pk), "MHX_JIT_TK=" + std::to_string(tk)}, &m);
-        r->dense_lds = dense_coop_lds_bytes(d, L, nimg);
-        if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_dense", &r->jit_step, r->dense_lds, "dense cooperative kernel");
-        if (rc == MHX_OK) { r->variant = KF_DENSE_COOP; r->coop_L = L; }
+        launch_rec k = rec("dense cooperative kernel", 64 * MHX_EMCEE_COOP_WAVES, (64 / L) * MHX_EMCEE_COOP_WAVES, dense_coop_lds_bytes(d, L, nimg));
+        if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_rwmh_dense");
+        if (rc == MHX_OK) { r->step = k; r->variant = KF_DENSE_COOP; r->coop_L = L; }
         else if (cfg->reduce_lanes > 1) return rc;
         L = 1;                                                        // not the separable cooperative path below
         }
@@ -1294,7 +1343,20 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         if (zig && MHX_ZIG_LDS_BYTES(NBL) > MHX_LDS_PER_BLOCK)
             return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: %d blocks per lane need %d bytes of LDS per block (limit %d); use more lanes per chain",
                             NBL, (int)MHX_ZIG_LDS_BYTES(NBL), (int)MHX_LDS_PER_BLOCK);
-        if (zig) r->coop_lds = MHX_ZIG_LDS_BYTES(NBL);
+        // The kernel's LDS: the ziggurat's slab (layer table + the step's normals).  One or two chains per wave: rows of the
+        // [dim][chains] arrays move through LDS, CB = 4 * (64 / L) chains at a time (mhx_rwmh_coop_body); the ziggurat's slab holds that
+        // buffer, the Box-Muller kernels get one of their own
+        size_t coop_lds = zig ? MHX_ZIG_LDS_BYTES(NBL) : 0;
+        int coop_tr = 0;
+        if (L >= 32) {
+            const size_t need = (size_t)d * (size_t)(4 * (64 / L)) * sizeof(mhx_real);
+            if (zig) coop_tr = 1;
+            else if (need <= 65536) { coop_lds = (need + 15) & ~(size_t)15; coop_tr = 1; }
+        }
+        // 256-thread blocks of whole waves of 64 / L chains; L >= 32: the kernel's XCD-aware block -> chain map wants whole rounds of 8.
+        // The moments twin has this shape too; wave pairs the same grid (a block's 4 pairs serve the chains of the one-wave body's 4
+        // waves) in 512-thread blocks
+        const launch_rec coop = rec("cooperative kernel", 256, 4 * (64 / L), coop_lds, L >= 32 ? 8 : 1);
         // Generator / consumer wave pairs (mhx_rwmh_coop_pairs_body): where the fp64 ziggurat form runs ONE wave per SIMD, a plain walk
         // with one scale, one step per fix-up group (10 to 13 blocks per lane).  Option COOP_PAIRS: 0 = the one-wave body, 1 = pairs,
         // unset = the library's choice (MHX_COOP_PAIRS_DEFAULT); a shape outside the rule keeps the one-wave body whatever the option
@@ -1305,10 +1367,15 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
         if (!opt_on(ctx, "NO_PREBUILT") && !waves_override && !walk)
             for (const auto& pb : k_prebuilt_coop)
                 if (pb.L == L && pb.NBL == NBL && pb.TK == tk && pb.PK == pk && pb.gen == (zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER)) {
-                    r->reg_fn = pb.fn; r->reg_fn_mom = pb.fn_mom; r->variant = KF_COOP; r->normal_gen = pb.gen;
-                    if (pairs && pb.fn_pairs) { r->reg_fn = pb.fn_pairs; r->coop_pairs = true; }
-                    for (auto f : {r->reg_fn, pb.fn_mom})
-                        if (f && (rc = kernel_lds_limit((const void*)f, r->coop_lds, "cooperative kernel (ziggurat)"))) return rc;
+                    r->variant = KF_COOP; r->normal_gen = pb.gen;
+                    r->coop_pairs = pairs && pb.fn_pairs;
+                    r->step = coop;
+                    if (r->coop_pairs) r->step.block = 512;
+                    if ((rc = rec_bind(&r->step, (const void*)(r->coop_pairs ? pb.fn_pairs : pb.fn)))) return rc;
+                    if (pb.fn_mom) {
+                        r->step_mom = coop;
+                        if ((rc = rec_bind(&r->step_mom, (const void*)pb.fn_mom))) return rc;
+                    }
                 }
         // the kernel's defines; its running-moments twin (mhx_run_sample, MHX_SAVE_MOMENTS) is built from this list with MHX_JIT_MOM=1
         r->coop_defs = {"MHX_JIT_RWMH_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
@@ -1328,21 +1395,21 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             }
 #endif
             rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_kernels.h"), defs, &m);
-            if (rc == MHX_OK) rc = jit_kernel(m, pairs ? "mhx_jit_rwmh_coop_pairs" : "mhx_jit_rwmh_coop", &r->jit_step, r->coop_lds, "cooperative kernel (ziggurat)");
-            if (rc == MHX_OK) r->coop_pairs = pairs;
-            if (rc == MHX_OK) { r->variant = KF_COOP_JIT; r->normal_gen = zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER; }
+            launch_rec k = coop;
+            if (pairs) k.block = 512;
+            if (rc == MHX_OK) rc = rec_bind(&k, m, pairs ? "mhx_jit_rwmh_coop_pairs" : "mhx_jit_rwmh_coop");
+            if (rc == MHX_OK) {
+                r->step = k; r->coop_pairs = pairs;
+                r->variant = KF_COOP_JIT; r->normal_gen = zig ? MHX_GEN_ZIGGURAT : MHX_GEN_BOX_MULLER;
+            }
             else if (cfg->reduce_lanes > 1 || zig) return rc;      // the caller asked for this shape explicitly
         }
         if (r->variant != KF_GENERIC) {
-            // one or two chains per wave: rows of the [dim][chains] arrays move through LDS, CB = 4 * (64 / L) chains at a time
-            // (mhx_rwmh_coop_body); the ziggurat's slab holds that buffer, the Box-Muller kernels get one of their own
-            if (L >= 32) {
-                const size_t need = (size_t)d * (size_t)(4 * (64 / L)) * sizeof(mhx_real);
-                if (zig) r->coop_tr = 1;
-                else if (need <= 65536) { r->coop_lds = (need + 15) & ~(size_t)15; r->coop_tr = 1; }
-            }
             r->coop_L = L;
-        } else if (cfg->reduce_lanes > 1) return mhx_fail(MHX_EINVAL, "reduce_lanes=%d: no pre-built kernel and JIT disabled", L);
+            r->coop_tr = coop_tr;
+        } else if (cfg->reduce_lanes > 1) {
+            return mhx_fail(MHX_EINVAL, "reduce_lanes=%d: no pre-built kernel and JIT disabled", L);
+        }
     }
     if (r->variant == KF_GENERIC && walk) {
         // no cooperative kernel for this target / proposal family: the state-in-HBM kernel evaluates the ratio
@@ -1352,7 +1419,11 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
     if (r->variant == KF_GENERIC && !(r->flags & MHX_FLAG_GENERIC)) {
         if (tk != MHX_TARGET_USER && !(cfg->flags & MHX_FLAG_ZIGGURAT))
             for (const auto& pb : k_prebuilt_reg)
-                if (pb.D == d && pb.TK == tk && pb.PK == pk) { r->reg_fn = pb.fn; r->variant = KF_REG; }
+                if (pb.D == d && pb.TK == tk && pb.PK == pk) {          // a lane per chain, one wave per block
+                    r->step = rec("register kernel", 64, 64, 0);
+                    if ((rc = rec_bind(&r->step, (const void*)pb.fn))) return rc;
+                    r->variant = KF_REG;
+                }
         // The candidate must be whole in a lane's registers (an arbitrary log-density reads all of it); the state need not be: above
         // MHX_REG_XR_ALL dimensions only its first MHX_REG_XR_CAP coordinates stay in registers, the tail lives in LDS
         // (mhx_rwmh_reg_body<..., XR>).  That carries the kernel to twice its old dimension limit -- an fp64 user log-density at
@@ -1387,19 +1458,25 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
             if (zslab) rdefs.push_back("MHX_JIT_ZSLAB=1");
             if (rwaves > 1) rdefs.push_back("MHX_JIT_REG_WAVES=" + std::to_string(rwaves));
             rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_kernels.h"), rdefs, &m, xo);
-            r->reg_lds = (size_t)(d - xr) * 64 * sizeof(mhx_real);
-            if (zig_reg) r->reg_lds = MHX_REG_ZIG_LDS_BYTES(d, xr) + (zslab ? MHX_REG_ZIG_SLAB_BYTES(d) : 0);
-            if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_rwmh_reg", &r->jit_step, r->reg_lds, "register kernel");
-            if (rc == MHX_OK) { r->variant = KF_REG_JIT; if (zig_reg) r->normal_gen = MHX_GEN_ZIGGURAT; }
+            // its LDS: the tail of a state that does not fit beside the candidate, or the ziggurat's table (and slab)
+            launch_rec k = rec("register kernel", 64, 64, zig_reg ? MHX_REG_ZIG_LDS_BYTES(d, xr) + (zslab ? MHX_REG_ZIG_SLAB_BYTES(d) : 0)
+                                                                  : (size_t)(d - xr) * 64 * sizeof(mhx_real));
+            if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_rwmh_reg");
+            if (rc == MHX_OK) { r->step = k; r->variant = KF_REG_JIT; if (zig_reg) r->normal_gen = MHX_GEN_ZIGGURAT; }
             else if (tk == MHX_TARGET_USER) return rc;      // no pre-built kernel can run a user source
             // built-in target: the generic kernel below computes the same chain; keep the message
         }
     }
+    jit_module* umod = nullptr;
     if (tk == MHX_TARGET_USER) {
         jit_module* m = nullptr;
         if ((rc = jit_generic_rwmh(t, &m))) return rc;
         if ((rc = jit_function(m, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
-        if (r->variant == KF_GENERIC && (rc = jit_function(m, "mhx_jit_rwmh_generic", &r->jit_step))) return rc;
+        umod = m;
+    }
+    if (r->variant == KF_GENERIC) {      // the state-in-HBM kernel: pre-built, or of the user target's module
+        r->step = rec("state-in-HBM kernel", 256, 256, 0);
+        if ((rc = umod ? rec_bind(&r->step, umod, "mhx_jit_rwmh_generic") : rec_bind(&r->step, (const void*)k_rwmh_generic))) return rc;
     }
     if ((cfg->flags & MHX_FLAG_ZIGGURAT) && r->normal_gen != MHX_GEN_ZIGGURAT)
         return mhx_fail(MHX_EINVAL, "MHX_FLAG_ZIGGURAT: this run's kernel (variant %d) has no ziggurat form -- it exists on the cooperative "
@@ -1510,19 +1587,23 @@ int api_rwmh_create_components(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh
                          {"MHX_JIT_FAM_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
                           "MHX_JIT_FAM_LIST=" + pattern, std::string("MHX_JIT_FAM_STATIC=") + (stat ? "1" : "0"),
                           std::string("MHX_JIT_FAM_SYM=") + (r->fam_symmetric ? "1" : "0")}, &m, xo);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_fam_reg", &r->jit_step);
+        // kernel(args, tparams, fam): a lane per chain, one wave per block
+        r->step = rec_shape("family register kernel", 64, 64, 0, {&r->k_tp, &r->d_fam});
+        if (rc == MHX_OK) rc = rec_bind(&r->step, m, "mhx_jit_fam_reg");
         if (rc) return rc;
         r->fam_reg = true;
     }
+    // ... else kernel(args, tparams, fam, symmetric): the state in HBM
+    if (!r->fam_reg) r->step = rec_shape("family state-in-HBM kernel", 256, 256, 0, {&r->k_tp, &r->d_fam, &r->fam_symmetric});
     if (tk == MHX_TARGET_USER) {
         jit_module* m = nullptr;
         if ((rc = jit_generic_rwmh(t, &m))) return rc;
         if ((rc = jit_function(m, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
         if (!r->fam_reg) {
             if ((rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_family_kernels.h"), {"MHX_JIT_FAM_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
-            if ((rc = jit_function(m, "mhx_jit_fam_generic", &r->jit_step))) return rc;
+            if ((rc = rec_bind(&r->step, m, "mhx_jit_fam_generic"))) return rc;
         }
-    }
+    } else if (!r->fam_reg && (rc = rec_bind(&r->step, (const void*)k_fam_generic))) return rc;
     if (!r->fam_reg) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
     *out = r.release();
     return MHX_OK;
@@ -1597,11 +1678,21 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
 
 #define MHX_MAX_STEPS_PER_LAUNCH 65536ull
 
+// Move the save cursor past a launch of `chunk` transitions that begins after r->tau: the next transition to record, the slot it
+// lands in, and (a running-moments call, RWMH only) the states folded in so far
+static void save_cursor_skip(mhx_run* r, uint64_t chunk, int thinning, uint32_t* save_next, int* save_slot)
+{
+    const uint64_t last = r->tau + chunk;
+    if (*save_next == MHX_NO_SAVE || (uint64_t)*save_next > last) return;
+    const uint64_t k = (last - *save_next) / (uint64_t)thinning + 1;
+    *save_next += (uint32_t)(k * (uint64_t)thinning);
+    *save_slot += (int)k;
+    if (r->moments_mode) r->mom_n += k;
+}
+
 static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int save_slot, int thinning)
 {
     mhx_ctx* ctx = r->ctx;
-    const mhx_real* tp = r->target->dparams;
-    const mhx_real* pv = r->d_pvec;
     uint64_t done = 0;
     while (done < nsteps) {
         const uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
@@ -1611,87 +1702,15 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->variant == KF_COND || r->variant == KF_COMPOSITE) {
-            int rc = cond_launch(r, a);
-            if (rc) return rc;
-        } else if (r->variant == KF_FAMILY) {
-            const mhx_fam_comp* fam = r->d_fam;
-            int sym = r->fam_symmetric;
-            if (r->fam_reg) {
-                void* params[] = {&a, &tp, &fam};
-                HIP_TRY(hipModuleLaunchKernel(r->jit_step, (unsigned)((r->n + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, params, nullptr));
-            } else if (r->target->kind == MHX_TARGET_USER) {
-                void* params[] = {&a, &tp, &fam, &sym};
-                int rc = launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, ctx->stream, params);
-                if (rc) return rc;
-            } else {
-                hipLaunchKernelGGL(k_fam_generic, dim3((unsigned)((r->n + 255) / 256)), dim3(256), 0, ctx->stream, a, tp, fam, sym);
-            }
-        } else if (r->variant == KF_COOP || r->variant == KF_COOP_JIT) {
-            const long threads = (((long)r->n + (64 / r->coop_L) - 1) / (64 / r->coop_L)) * 64;   // whole waves
-            unsigned grid = (unsigned)((threads + 255) / 256);
-            if (r->coop_L >= 32) grid = (grid + 7u) & ~7u;          // the kernel's XCD-aware block -> chain map wants whole rounds of 8
-            if (r->moments_mode && r->reg_fn_mom) {
-                hipLaunchKernelGGL(r->reg_fn_mom, dim3(grid), dim3(256), r->coop_lds, ctx->stream, a, tp, pv);
-            } else if (r->moments_mode) {
-                void* params[] = {&a, &tp, &pv};
-                HIP_TRY(hipModuleLaunchKernel(r->jit_step_mom, grid, 1, 1, 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
-            } else if (r->variant == KF_COOP) {
-                // (wave pairs: the same grid -- a block's 4 pairs serve the chains of the one-wave body's 4 waves)
-                hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(r->coop_pairs ? 512 : 256), r->coop_lds, ctx->stream, a, tp, pv);
-            } else {
-                void* params[] = {&a, &tp, &pv};
-                HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, r->coop_pairs ? 512 : 256, 1, 1, (unsigned)r->coop_lds, ctx->stream, params, nullptr));
-            }
-        } else if (r->variant == KF_MFMA && r->mfma_stream) {
-            const unsigned grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
-            mhx_real* gA = r->d_mfma_img;
-            mhx_real* gL = r->d_mfma_img + mfma_image_reals(r->dim);
-            void* params[] = {&a, &tp, &pv, &gA, &gL};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds,
-                                          ctx->stream, params, nullptr));
-        } else if (r->variant == KF_MFMA) {
-            const unsigned grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
-            void* params[] = {&a, &tp, &pv};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds,
-                                          ctx->stream, params, nullptr));
-        } else if (r->variant == KF_DENSE_COOP) {
-            const long per_block = (64 / r->coop_L) * MHX_EMCEE_COOP_WAVES;          // chains per block
-            const unsigned grid = (unsigned)(((long)r->n + per_block - 1) / per_block);
-            void* params[] = {&a, &tp, &pv};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_EMCEE_COOP_WAVES, 1, 1, (unsigned)r->dense_lds,
-                                          ctx->stream, params, nullptr));
-        } else if (r->variant == KF_WAVE) {                      // a wave per chain; candidates per round: by the last call's acceptance
-            const int k = opt_int(r->ctx, "WAVE_K", r->wave_k);
-            hipLaunchKernelGGL(k == 8 ? r->reg_fn8 : r->reg_fn, dim3((unsigned)r->n), dim3(64), 0, ctx->stream, a, tp, pv);
-        } else if (r->variant == KF_REG) {
-            const unsigned grid = (unsigned)((r->n + 63) / 64);
-            hipLaunchKernelGGL(r->reg_fn, dim3(grid), dim3(64), 0, ctx->stream, a, tp, pv);
-        } else if (r->variant == KF_REG_JIT) {
-            const unsigned grid = (unsigned)((r->n + 63) / 64);
-            void* params[] = {&a, &tp, &pv};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64, 1, 1, (unsigned)r->reg_lds, ctx->stream, params, nullptr));
-        } else if (r->target->kind == MHX_TARGET_USER) {
-            const unsigned grid = (unsigned)((r->n + 255) / 256);
-            void* params[] = {&a, &tp, &pv};
-            int rc = launch_module(r->jit_step, grid, 256, ctx->stream, params);
-            if (rc) return rc;
-        } else {
-            const unsigned grid = (unsigned)((r->n + 255) / 256);
-            hipLaunchKernelGGL(k_rwmh_generic, dim3(grid), dim3(256), 0, ctx->stream, a, tp, pv);
-        }
+        // the record: the running-moments twin, the K = 8 build of the wave-per-chain kernel (candidates per round: by the last call's
+        // acceptance, or option WAVE_K), else the run's step kernel
+        const launch_rec& k = r->moments_mode && r->step_mom ? r->step_mom
+                            : (r->step_k8 && opt_int(ctx, "WAVE_K", r->wave_k) == 8 ? r->step_k8 : r->step);
+        int rc = launch(k, ctx->stream, r->n, 1, &a);
+        if (rc) return rc;
         HIP_TRY(hipGetLastError());
         r->stats.launches++;
-        // advance the save cursor past this chunk
-        if (save_next != MHX_NO_SAVE) {
-            const uint64_t last = r->tau + chunk;
-            if ((uint64_t)save_next <= last) {
-                const uint64_t k = (last - save_next) / (uint64_t)thinning + 1;
-                save_next += (uint32_t)(k * (uint64_t)thinning);
-                save_slot += (int)k;
-                if (r->moments_mode) r->mom_n += k;
-            }
-        }
+        save_cursor_skip(r, chunk, thinning, &save_next, &save_slot);
         r->tau += chunk;
         done += chunk;
     }
@@ -1803,13 +1822,16 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
         if (r->kind != RUN_RWMH || (r->variant != KF_GENERIC && r->variant != KF_COOP && r->variant != KF_COOP_JIT))
             return mhx_fail(MHX_EINVAL, "running moments need an RWMH run on the cooperative or the generic kernel "
                                     "(separable target, or MHX_FLAG_GENERIC); this run uses kernel variant %d", r->variant);
-        if (((r->variant == KF_COOP && !r->reg_fn_mom) || r->variant == KF_COOP_JIT) && !r->jit_step_mom) {
+        if ((r->variant == KF_COOP || r->variant == KF_COOP_JIT) && !r->step_mom) {
             jit_module* m = nullptr;
             std::vector<std::string> defs = r->coop_defs;
             for (auto& df : defs) if (df == "MHX_JIT_MOM=0") df = "MHX_JIT_MOM=1";
             int rcj = jit_compile(ctx, jit_source(r->target, "mhx_rwmh_kernels.h"), defs, &m);
-            if (rcj == MHX_OK) rcj = jit_kernel(m, "mhx_jit_rwmh_coop", &r->jit_step_mom, r->coop_lds, "cooperative kernel (moments)");
+            launch_rec k = r->step;          // the step kernel's grid and LDS, never as wave pairs: 256-thread blocks
+            k.what = "cooperative kernel (moments)"; k.block = 256;
+            if (rcj == MHX_OK) rcj = rec_bind(&k, m, "mhx_jit_rwmh_coop");
             if (rcj) return rcj;
+            r->step_mom = k;
         }
         const size_t bytes = ((size_t)r->dim + 1) * (size_t)r->n * sizeof(mhx_real);
         int rc = ensure_buffer((void**)&r->d_mom_mean, &r->mom_cap, bytes, "mhx_run_sample", "running-moment buffer");

@@ -48,33 +48,10 @@ static int cond_check(mhx_run* r)
     return MHX_OK;
 }
 
-static int cond_launch(mhx_run* r, const mhx_rwmh_args& a0)
-{
-    mhx_rwmh_args a = a0;
-    const mhx_real* tp = r->target->dparams;
-    const mhx_fam_comp* fam = r->d_fam;
-    const mhx_real* cdata = r->d_cond_data;
-    int ncdata = r->cond_ndata;
-    if (r->fam_reg) {
-        void* params[] = {&a, &tp, &fam, &cdata, &ncdata};
-        HIP_TRY(hipModuleLaunchKernel(r->jit_step, (unsigned)((r->n + 63) / 64), 1, 1, 64, 1, 1, 0, r->ctx->stream, params, nullptr));
-        return MHX_OK;
-    }
-    mhx_real* pbuf = r->d_cond_p;
-    if (r->variant == KF_COMPOSITE) {
-        const int* ctab = r->d_cmp_tab;
-        int nblocks = r->cmp_nblocks;
-        void* params[] = {&a, &tp, &fam, &cdata, &ncdata, &pbuf, &ctab, &nblocks};
-        return launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, r->ctx->stream, params);
-    }
-    int stat = (r->flags & MHX_FLAG_STATIC_PROPOSAL) ? 1 : 0, sym = r->fam_symmetric;
-    void* params[] = {&a, &tp, &fam, &cdata, &ncdata, &pbuf, &stat, &sym};
-    return launch_module(r->jit_step, (unsigned)((r->n + 255) / 256), 256, r->ctx->stream, params);
-}
-
 // What mhx_rwmh_create_conditional and mhx_rwmh_create_composite share once the run's tables are on the device: the chain state,
 // the module (the register form when `fits` and the shape allows it -- `reg_flag` and `reg_defines` beside the dimension and the
-// target kind --, else the state-in-HBM form), the check kernel, the parameter buffer and the initial kernel of a user target.
+// target kind --, else the state-in-HBM form) and its launch record, the check kernel, the parameter buffer and the initial kernel of a
+// user target.
 static int cond_build(mhx_run* r, const bool fits, const char* reg_flag, const std::vector<std::string>& reg_defines, const char* reg_name,
                       const char* generic_flag, const char* generic_name, const char* check_name)
 {
@@ -96,12 +73,23 @@ static int cond_build(mhx_run* r, const bool fits, const char* reg_flag, const s
         std::vector<std::string> defs = {reg_flag, "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk)};
         defs.insert(defs.end(), reg_defines.begin(), reg_defines.end());
         rc = jit_compile(ctx, src, defs, &m, xo);
-        if (rc == MHX_OK) rc = jit_function(m, reg_name, &r->jit_step);
+        // kernel(args, tparams, fam, cdata, ncdata): a lane per chain, one wave per block
+        r->step = rec_shape("conditional register kernel", 64, 64, 0, {&r->k_tp, &r->d_fam, &r->d_cond_data, &r->cond_ndata});
+        if (rc == MHX_OK) rc = rec_bind(&r->step, m, reg_name);
         if (rc) return rc;
         r->fam_reg = true;
     } else {
         if ((rc = jit_compile(ctx, src, {generic_flag, "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
-        if ((rc = jit_function(m, generic_name, &r->jit_step))) return rc;
+        // kernel(args, tparams, fam, cdata, ncdata, pbuf, ...): then a composite run's table and block count, a conditional run's
+        // static and symmetric flags
+        r->cond_static = (r->flags & MHX_FLAG_STATIC_PROPOSAL) ? 1 : 0;
+        if (r->variant == KF_COMPOSITE)
+            r->step = rec_shape("composite state-in-HBM kernel", 256, 256, 0,
+                                {&r->k_tp, &r->d_fam, &r->d_cond_data, &r->cond_ndata, &r->d_cond_p, &r->d_cmp_tab, &r->cmp_nblocks});
+        else
+            r->step = rec_shape("conditional state-in-HBM kernel", 256, 256, 0,
+                                {&r->k_tp, &r->d_fam, &r->d_cond_data, &r->cond_ndata, &r->d_cond_p, &r->cond_static, &r->fam_symmetric});
+        if ((rc = rec_bind(&r->step, m, generic_name))) return rc;
         HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
     }
     if ((rc = jit_function(m, check_name, &r->jit_cond_check))) return rc;

@@ -112,16 +112,21 @@ static int emcee_create_mfma(mhx_run* r, const mhx_target* t, const int d)
     std::vector<std::string> defs = {"MHX_JIT_EMCEE_MFMA=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_EMCEE_MFMA_WAVES=" + std::to_string(r->coop_waves)};
     if (const char* rs = opt(r->ctx, "EMCEE_REC_STORE")) defs.push_back(std::string("MHX_EMCEE_REC_STORE=") + rs);
     int rc = jit_compile(ctx, "#include \"mhx_emcee_mfma_kernels.h\"\n", defs, &m);
-    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_mfma_half", &r->jit_step);
-    if (rc) { (void)hipFree(r->d_mfma_img); r->d_mfma_img = nullptr; r->jit_step = nullptr; return rc; }
+    // kernel(args, image) for the half step and the sweep: 16 walkers per wave.  More than one wave per block: the waves share ONE
+    // fetch of the operand image through LDS (mhx_emcee_mfma_kernels.h)
+    launch_rec half = rec_shape("matrix-core stretch move", 64 * r->coop_waves, 16 * r->coop_waves, r->coop_waves > 1 ? img.size() * sizeof(mhx_real) : 0,
+                                {&r->d_mfma_img});
+    launch_rec sweep = half;
+    if (rc == MHX_OK) rc = rec_bind(&half, m, "mhx_jit_emcee_mfma_half");
+    if (rc) { (void)hipFree(r->d_mfma_img); r->d_mfma_img = nullptr; return rc; }
+    r->step = half;
     // (this form's sweep kernel pays up to 20 480 walkers at d = 50: 16 384 1.18 -> 1.48e9 moves/s, 20 480 1.31 -> 1.48e9, 24 576 1.53 ->
     // 1.48e9; further out for smaller dimensions -- d = 24: +16 % at 49 152, d = 10: +13 % at 65 536; d = 64: +11 % at 16 384, -9 % at 24 576)
     if (opt_int(ctx, "EMCEE_FUSED", MHX_EMCEE_FUSED_DEFAULT != 0 && (long)r->n <= std::max(16384L, std::min(61440L, 21000L * 50 / std::max(d, 16)))) != 0)
-        if (jit_function(m, "mhx_jit_emcee_mfma_sweep", &r->jit_sweep) != MHX_OK) r->jit_sweep = nullptr;
-    // more than one wave per block: the waves share ONE fetch of the operand image through LDS (mhx_emcee_mfma_kernels.h)
-    r->sweep_lds = r->coop_waves > 1 ? img.size() * sizeof(mhx_real) : 0;
-    for (hipFunction_t f : {r->jit_step, r->jit_sweep})
-        if (f && (rc = kernel_lds_limit((const void*)f, r->sweep_lds, "matrix-core stretch move"))) return rc;
+        if (hipFunction_t f = nullptr; jit_function(m, "mhx_jit_emcee_mfma_sweep", &f) == MHX_OK) {      // (a missing sweep kernel is done without)
+            if ((rc = rec_bind(&sweep, m, "mhx_jit_emcee_mfma_sweep"))) return rc;
+            r->sweep = sweep;
+        }
     r->emcee_band = -1;
     r->variant = KF_EMCEE_MFMA;
     r->coop_L = 4;
@@ -155,6 +160,8 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
     const size_t NT = (size_t)r->n;
     r->n = cfg->nwalkers;                                // ... while the kernel form is chosen for ONE ensemble's shape (restored at the exits)
     auto done = [&]() { r->n = (int)NT; *out = r.release(); return (int)MHX_OK; };
+    // a launch record of this sampler: kernel(args, tparams); every launch gets E as its second grid dimension
+    auto rec = [&](const char* what, unsigned block, int per_block, size_t lds) { return rec_shape(what, block, per_block, lds, {&r->k_tp}); };
     // the prior of the initial walkers (src/emcee.jl:29-34), kept on the device like a proposal
     r->prop_kind = -1;
     if (cfg->init_kind >= 0) {
@@ -180,14 +187,15 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
         if (cfg->reduce_lanes > 1) return mhx_fail(MHX_EINVAL, "mhx_emcee_create: the sequential sweep runs on one lane group (reduce_lanes must be 0 or 1)");
         r->variant = KF_EMCEE_SEQ;
         r->coop_L = 1;
+        r->step = rec("sequential stretch move", 64, 1, 0);        // one wave per ensemble, launched for ONE item
         if (t->kind == MHX_TARGET_USER) {
             jit_module* m = nullptr;
             rc = jit_compile(ctx, jit_source(t, "mhx_emcee_kernels.h"),
                              {"MHX_JIT_EMCEE=1", "MHX_JIT_DIM=0", "MHX_JIT_TK=" + std::to_string(t->kind), "MHX_JIT_L=1"}, &m);
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_seq", &r->jit_step);
+            if (rc == MHX_OK) rc = rec_bind(&r->step, m, "mhx_jit_emcee_seq");
             if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_init", &r->jit_init);
             if (rc) return rc;
-        }
+        } else if ((rc = rec_bind(&r->step, (const void*)k_emcee_seq))) return rc;
         HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)cfg->dim * (size_t)E * sizeof(mhx_real)));
         return done();
     }
@@ -234,7 +242,7 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
             int rcm = emcee_create_mfma(r.get(), t, d);
             if (rcm == MHX_OK) {
                 HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
-                if (r->jit_sweep) {
+                if (r->sweep) {
                     HIP_TRY(hipMalloc(&r->d_xw2, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
                     HIP_TRY(hipMalloc(&r->d_lp2, NT * sizeof(mhx_real)));
                 }
@@ -332,19 +340,20 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
             xopts.push_back("-mllvm"); xopts.push_back("-amdgpu-kernarg-preload-count=9");
         }
         rc = jit_compile(ctx, jit_source(t, "mhx_emcee_kernels.h"), defs, &m, xopts);
-        if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_half", &r->jit_step);
         if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_emcee_init", &r->jit_init);
         const int xp = (d + 3) & ~3, u = 16 / (int)sizeof(mhx_real), ys = ((xp / u) | 1) * u;      // mhx_emcee_sgeom::YS
-        if (rc == MHX_OK && scal) {
-            r->dense_lds = (size_t)(r->emcee_wpb * ys + L * 64) * sizeof(mhx_real);
-            rc = kernel_lds_limit((const void*)r->jit_step, r->dense_lds, "scalar-factor stretch move");
-        } else if (rc == MHX_OK && L > 1) {
-            if (dense_coop_lds_bytes(d, L, 1, r->coop_waves) > MHX_LDS_PER_BLOCK) rc = mhx_fail(MHX_EINVAL, "emcee: the factor image of dim %d with %d lanes per walker exceeds the LDS", d, L);
-            else {
-                r->dense_lds = dense_coop_lds_bytes(d, L, 1, r->coop_waves);
-                rc = kernel_lds_limit((const void*)r->jit_step, r->dense_lds, "cooperative stretch move");
-            }
-        }
+        // The half step.  Scalar-factor form: wpb walkers per block of L waves, their candidates and a row class per wave in LDS;
+        // lane-group form: 64 / L walkers per wave, coop_waves waves, candidate rows and the factor image in LDS; a lane per walker:
+        // one wave per block, no LDS.  The sweep kernel runs the same blocks (the scalar-factor form: wpb / 2 walkers of EACH half)
+        launch_rec half = scal    ? rec("scalar-factor stretch move", 64 * r->coop_waves, r->emcee_wpb, (size_t)(r->emcee_wpb * ys + L * 64) * sizeof(mhx_real))
+                          : L > 1 ? rec("cooperative stretch move", 64 * r->coop_waves, (64 / L) * r->coop_waves, dense_coop_lds_bytes(d, L, 1, r->coop_waves))
+                                  : rec("stretch move", 64, 64, 0);
+        launch_rec sweep = half, persist;
+        sweep.what = "stretch move sweep";
+        if (scal) sweep.per_block = r->emcee_wpb / 2;
+        if (rc == MHX_OK && !scal && L > 1 && half.lds > MHX_LDS_PER_BLOCK)
+            rc = mhx_fail(MHX_EINVAL, "emcee: the factor image of dim %d with %d lanes per walker exceeds the LDS", d, L);
+        if (rc == MHX_OK) rc = rec_bind(&half, m, "mhx_jit_emcee_half");
         // one launch per sweep (mhx_emcee_coop_sweep_body): the lane-group form with three candidate rows per walker in LDS.  By
         // default for a banded factor only: with the dense image the second half's three full row products cost more than the
         // launch they save (rotated C3: 16.2 us per sweep against 2 x 7.1); MHX_EMCEE_FUSED=0|1 forces it off / on (tuning knob)
@@ -354,12 +363,12 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
         const bool fused_size_band = MHX_EMCEE_FUSED_DEFAULT != 0 && (long)r->n <= std::min(61440L, (long)MHX_EMCEE_FUSED_MAX_W * 50 / std::max(d, 20));
         // (a sweep kernel that is missing, or refused its LDS, is done without: the half-step launches stay)
         auto try_sweep = [&](size_t lds) {
-            r->sweep_lds = lds;
-            if (lds > MHX_LDS_PER_BLOCK || jit_kernel(m, "mhx_jit_emcee_sweep", &r->jit_sweep, lds, "stretch move sweep") != MHX_OK) r->jit_sweep = nullptr;
+            sweep.lds = lds;
+            if (lds > MHX_LDS_PER_BLOCK || rec_bind(&sweep, m, "mhx_jit_emcee_sweep") != MHX_OK) sweep.mod_fn = nullptr;
         };
         if (rc == MHX_OK && !scal && L > 1 && opt_int(ctx, "EMCEE_FUSED", fused_size_band && bw >= 0) != 0) {
             const size_t rows = (size_t)r->coop_waves * (64 / L) * (size_t)(((d + 3) & ~3) + 4) * sizeof(mhx_real);
-            try_sweep(r->dense_lds + 2 * rows);
+            try_sweep(half.lds + 2 * rows);
         }
         // ... and the scalar-factor form (mhx_emcee_scal_sweep_body; DPP operand mode, the latency shape of <= 32 walkers per block)
         if (rc == MHX_OK && scal && scal_mode == 1 && r->emcee_wpb == 32 && L >= 2 && opt_int(ctx, "EMCEE_FUSED", fused_size) != 0)
@@ -370,19 +379,28 @@ int api_emcee_create(mhx_ctx* ctx, const mhx_target* t, const mhx_emcee_cfg* cfg
         // ... and, for an ensemble of at most 1024 walkers whose rows fit the LDS of one block, the whole call in ONE launch of one
         // persistent block (mhx_emcee_persist_body, KF_EMCEE_PERSIST); MHX_EMCEE_PERSIST=0 keeps the sweep launches (tuning knob).  The 64 KB
         // of registers a 1024-thread block leaves each lane hold the walker and its candidate up to d = 24 in fp64 (48 in fp32)
-        bool persist = false;
-        r->persist_lds = (size_t)r->n * (size_t)(((jd + 3) & ~3) + 1) * sizeof(mhx_real);
-        if (rc == MHX_OK && persist_threads > 0 && jit_kernel(m, "mhx_jit_emcee_persist", &r->jit_persist, r->persist_lds, "persistent-block ensemble") == MHX_OK)
-            persist = true;
-        else r->jit_persist = nullptr;
-        if (rc == MHX_OK) { r->variant = scal ? KF_EMCEE_SCAL : (L > 1 ? KF_COOP_JIT : (jd > 0 ? (persist ? KF_EMCEE_PERSIST : KF_REG_JIT) : KF_GENERIC)); r->coop_L = L; }
-        else if (user || cfg->reduce_lanes > 1) return rc;
-        else { r->jit_step = nullptr; r->jit_init = nullptr; r->coop_L = 1; }
+        // (one block of whole waves per ensemble, launched for ONE item; every walker's row in LDS)
+        persist = rec("persistent-block ensemble", (unsigned)persist_threads, 1, (size_t)r->n * (size_t)(((jd + 3) & ~3) + 1) * sizeof(mhx_real));
+        if (!(rc == MHX_OK && persist_threads > 0 && rec_bind(&persist, m, "mhx_jit_emcee_persist") == MHX_OK))
+            persist.mod_fn = nullptr;
+        if (rc == MHX_OK) {
+            r->step = half; r->sweep = sweep; r->persist = persist; r->sweep_mixed = scal;
+            r->variant = scal ? KF_EMCEE_SCAL : (L > 1 ? KF_COOP_JIT : (jd > 0 ? (persist ? KF_EMCEE_PERSIST : KF_REG_JIT) : KF_GENERIC));
+            r->coop_L = L;
+        } else if (user || cfg->reduce_lanes > 1) {
+            return rc;
+        } else {
+            r->jit_init = nullptr; r->coop_L = 1;
+        }
+    }
+    if (!r->step) {                      // the pre-built half step: run-time dimension, a lane per walker
+        r->step = rec("stretch move", 64, 64, 0);
+        if ((rc = rec_bind(&r->step, (const void*)k_emcee_half))) return rc;
     }
     if (r->variant == KF_GENERIC) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * NT * sizeof(mhx_real)));
     // the compile-time-dimension kernels (cooperative, register) keep the walkers walker-major
     if (r->variant == KF_COOP_JIT || r->variant == KF_REG_JIT || r->variant == KF_EMCEE_SCAL || r->variant == KF_EMCEE_PERSIST) HIP_TRY(hipMalloc(&r->d_xw, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
-    if (r->jit_sweep) {
+    if (r->sweep) {
         HIP_TRY(hipMalloc(&r->d_xw2, NT * (size_t)mhx_xw_pitch(d) * sizeof(mhx_real)));
         HIP_TRY(hipMalloc(&r->d_lp2, NT * sizeof(mhx_real)));
     }
@@ -419,29 +437,24 @@ static int emcee_init(mhx_run* r, const mhx_real* init)
 static int emcee_launch_half(mhx_run* r, mhx_emcee_args a, int h, int begin, int count)
 {
     mhx_ctx* ctx = r->ctx;
-    const mhx_real* tp = r->target->dparams;
     a.half = h;
     a.t_begin = begin;
     a.t_count = count;
     if (count <= 0) return MHX_OK;
-    const bool coop = r->coop_L > 1;
-    const int per_block = r->variant == KF_EMCEE_SCAL ? r->emcee_wpb : (64 / r->coop_L) * (coop ? r->coop_waves : 1);      // walkers per block
-    const unsigned grid = (unsigned)((count + per_block - 1) / per_block), E = (unsigned)r->n_ens;
-    if (r->variant == KF_EMCEE_MFMA) {
-        const mhx_real* img = r->d_mfma_img;
-        void* params[] = {&a, &img};
-        HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, E, 1, 64 * r->coop_waves, 1, 1, (unsigned)r->sweep_lds, ctx->stream, params, nullptr));
-        r->stats.launches += 1;
-        return MHX_OK;
-    }
-    if (r->jit_step) {
-        void* params[] = {&a, &tp};
-        void* params_pl[] = {&a.xw, &a.lp, &a.seed, &a.ensemble_id, &a.sweep, &a.half, &a.nwalkers, &a.t_begin, &a.t_count, &a, &tp};
-        HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, E, 1, coop ? 64 * r->coop_waves : 64, 1, 1,
-                                      coop ? (unsigned)r->dense_lds : 0u, ctx->stream, r->emcee_preload ? params_pl : params, nullptr));
+    const unsigned E = (unsigned)r->n_ens;
+    int rc;
+    if (r->emcee_preload && r->step.mod_fn) {
+        // MHX_JIT_PRELOAD, the one argument list that differs per launch: the hot arguments first, as scalars of their own (the kernel has
+        // them preloaded), then the block and tparams -- a copy of the record with that list
+        launch_rec k = r->step;
+        k.ntail = 0;
+        for (const void* p : std::initializer_list<const void*>{&a.lp, &a.seed, &a.ensemble_id, &a.sweep, &a.half, &a.nwalkers, &a.t_begin, &a.t_count, &a, &r->k_tp})
+            k.tail[k.ntail++] = const_cast<void*>(p);
+        rc = launch(k, ctx->stream, count, E, &a.xw);
     } else {
-        hipLaunchKernelGGL(k_emcee_half, dim3(grid, E), dim3(64), 0, ctx->stream, a, tp);
+        rc = launch(r->step, ctx->stream, count, E, &a);
     }
+    if (rc) return rc;
     r->stats.launches += 1;
     return MHX_OK;
 }
@@ -476,19 +489,13 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        const mhx_real* tp = r->target->dparams;
-        if (r->jit_step) {
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, 1, E, 1, 64, 1, 1, 0, r->ctx->stream, params, nullptr));
-        } else {
-            hipLaunchKernelGGL(k_emcee_seq, dim3(1, E), dim3(64), 0, r->ctx->stream, a, tp);
-        }
+        if (int rc = launch(r->step, r->ctx->stream, 1, E, &a)) return rc;
         HIP_TRY(hipGetLastError());
         r->stats.launches += 1;
         r->tau += nsteps;
         return MHX_OK;
     }
-    if (r->variant == KF_EMCEE_PERSIST && r->jit_persist && !opt(r->ctx, "EMCEE_DEFER")) {      // a small ensemble: the whole call in one persistent block
+    if (r->persist && !opt(r->ctx, "EMCEE_DEFER")) {      // a small ensemble: the whole call in one persistent block
         uint64_t done = 0;
         while (done < nsteps) {
             const uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
@@ -498,18 +505,9 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
             a.save_next = save_next;
             a.save_slot = save_slot;
             a.thinning = thinning;
-            const mhx_real* tp = r->target->dparams;
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_persist, 1, E, 1, (unsigned)(((W + 63) / 64) * 64), 1, 1, (unsigned)r->persist_lds, r->ctx->stream, params, nullptr));   // a block (a CU) per ensemble
+            if (int rc = launch(r->persist, r->ctx->stream, 1, E, &a)) return rc;      // a block (a CU) per ensemble
             r->stats.launches += 1;
-            if (save_next != MHX_NO_SAVE) {
-                const uint64_t lastt = r->tau + chunk;
-                if ((uint64_t)save_next <= lastt) {
-                    const uint64_t k = (lastt - save_next) / (uint64_t)thinning + 1;
-                    save_next += (uint32_t)(k * (uint64_t)thinning);
-                    save_slot += (int)k;
-                }
-            }
+            save_cursor_skip(r, chunk, thinning, &save_next, &save_slot);
             r->tau += chunk;
             done += chunk;
         }
@@ -526,7 +524,7 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
     // MHX_EMCEE_SWEEP_DEFER=1 (tuning knob, off): sweep launches of the lane-group form record a sweep at the top of the NEXT launch, from
     // the rows every group loads anyway (mhx_emcee_coop_sweep_body) -- measured SLOWER, 8.34 against 7.60 us per sweep on one box: 6.7 MB
     // of stores at the head of the launch sit in front of the row loads the whole chain waits for
-    const bool sweep_defer = E == 1 && r->jit_sweep && r->variant == KF_COOP_JIT && opt_on(r->ctx, "EMCEE_SWEEP_DEFER");
+    const bool sweep_defer = E == 1 && r->sweep && r->variant == KF_COOP_JIT && opt_on(r->ctx, "EMCEE_SWEEP_DEFER");
     for (uint64_t s = 0; s < nsteps; ++s) {
         mhx_emcee_args a = emcee_args(r);
         a.sweep = (uint32_t)(r->tau + 1);
@@ -536,7 +534,7 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
             ++save_slot;
             save_next += (uint32_t)thinning;
         }
-        if (r->jit_sweep && !deferred) {
+        if (r->sweep && !deferred) {
             // the whole sweep in one launch: reads (d_xw, d_lp), writes every walker's new row to (d_xw2, d_lp2); then they swap
             a.save_slot = slot;
             if (sweep_defer) {                               // the record of a sweep leaves at the top of the NEXT launch (lane-group form)
@@ -545,14 +543,11 @@ static int emcee_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sa
                 owed_b = slot;
             }
             a.all_rows = s == 0 ? 1 : 0;                     // the other buffer holds nothing of this state yet
-            // lane-group form: blocks of one half each, the second half's first; scalar-factor form: mixed blocks, wpb / 2 walkers of each half
-            const bool scal = r->variant == KF_EMCEE_SCAL, coop = scal || r->coop_L > 1;
-            const int per_block = scal ? r->emcee_wpb / 2 : (coop ? (64 / r->coop_L) * r->coop_waves : 64);
-            const unsigned grid = scal ? (unsigned)((W - halfW + per_block - 1) / per_block)
-                                                : (unsigned)((halfW + per_block - 1) / per_block + (W - halfW + per_block - 1) / per_block);
-            const mhx_real* tp = r->variant == KF_EMCEE_MFMA ? r->d_mfma_img : r->target->dparams;
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_sweep, grid, E, 1, coop ? 64 * r->coop_waves : 64, 1, 1, (unsigned)r->sweep_lds, r->ctx->stream, params, nullptr));
+            // blocks of one half each, the second half's first: each half takes whole blocks; the scalar-factor form: mixed blocks, as
+            // many as the larger half needs
+            const long pb = r->sweep.per_block;
+            const long items = r->sweep_mixed ? W - halfW : ((halfW + pb - 1) / pb + (W - halfW + pb - 1) / pb) * pb;
+            if (int rc = launch(r->sweep, r->ctx->stream, items, E, &a)) return rc;
             std::swap(r->d_xw, r->d_xw2);
             std::swap(r->d_lp, r->d_lp2);
             r->stats.launches += 1;

@@ -46,7 +46,7 @@ static int mala_mfma_images(mhx_run* r, jit_module* m)
     mhx_real* dst = r->d_mfma_img;
     void* pa[] = {(void*)&src, &dst};
     rc = launch_module(fimg, 1, 256, r->ctx->stream, pa);
-    mhx_real* dstT = r->d_mfma_img + ra;
+    mhx_real* dstT = r->d_mfma_img2 = r->d_mfma_img + ra;
     void* pt[] = {(void*)&src, &dstT};
     if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, r->ctx->stream, pt);
     if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(r->ctx->stream));
@@ -81,6 +81,8 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
     const bool want_reg = !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && (r->dim <= regmax || split) &&
                           !(t->kind == MHX_TARGET_IID_NORMAL && t->nparams > 4096);
     r->variant = KF_GENERIC;
+    // a launch record of this sampler: kernel(args, tparams)
+    auto rec = [&](const char* what, unsigned block, int per_block, size_t lds) { return rec_shape(what, block, per_block, lds, {&r->k_tp}); };
     // MHX_FLAG_ZIGGURAT (round 5): the noise by the table ziggurat -- the lane-per-chain register kernel's form (both widths, any target
     // with a gradient, d within that kernel's reach); the cooperative / matrix-core / state-in-HBM kernels draw Box-Muller
     const bool zig = (cfg->flags & MHX_FLAG_ZIGGURAT) != 0;
@@ -128,14 +130,14 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
         jit_module* m = nullptr;
         std::vector<std::string> defs = {mfma_s ? "MHX_JIT_MALA_MFMA_STREAM=1" : "MHX_JIT_MALA_MFMA_LEAN=1", "MHX_JIT_DIM=" + std::to_string(r->dim)};
         if (mfma_l) defs.push_back(std::string("MHX_JIT_PAIR=") + (lean_pair ? "1" : "0"));
-        r->dense_lds = mfma_s ? mala_ring : lean_ring;
         rc = jit_compile(ctx, jit_source(t, "mhx_mala_mfma_kernels.h"), defs, &m, {"-mllvm", "-pragma-unroll-threshold=4000000"});
-        if (rc == MHX_OK) rc = jit_kernel(m, mfma_s ? "mhx_jit_mala_mfma_stream" : "mhx_jit_mala_mfma_lean", &r->jit_step, r->dense_lds,
-                                          mfma_s ? "streamed matrix-core MALA kernel" : "lean matrix-core MALA kernel");
+        // 16 chains per wave, the LDS is the ring; kernel(args, tparams, image of A, image of A^T)
+        launch_rec k = rec_shape(mfma_s ? "streamed matrix-core MALA kernel" : "lean matrix-core MALA kernel", 64 * MHX_MFMA_WAVES, 16 * MHX_MFMA_WAVES,
+                                 mfma_s ? mala_ring : lean_ring, {&r->k_tp, &r->d_mfma_img, &r->d_mfma_img2});
+        if (rc == MHX_OK) rc = rec_bind(&k, m, mfma_s ? "mhx_jit_mala_mfma_stream" : "mhx_jit_mala_mfma_lean");
         if (rc == MHX_OK) rc = mala_mfma_images(r.get(), m);
-        if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->mfma_stream = true; }
+        if (rc == MHX_OK) { r->step = k; r->variant = KF_MFMA; r->coop_L = 4; }
         else if (cfg->reduce_lanes > 1) return rc;
-        else r->jit_step = nullptr;
     }
     if (mfma) {
         jit_module* m = nullptr;
@@ -144,10 +146,10 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
         const int waves = wenv ? std::max(1, atoi(wenv)) : (MHX_REAL64 ? 1 : (NS <= 16 ? 2 : 1));
         rc = jit_compile(ctx, jit_source(t, "mhx_mala_mfma_kernels.h"),
                          {"MHX_JIT_MALA_MFMA=1", "MHX_JIT_DIM=" + std::to_string(r->dim), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
-        if (rc == MHX_OK) rc = jit_kernel(m, "mhx_jit_mala_mfma", &r->jit_step, mfma_lds, "matrix-core MALA kernel");
-        if (rc == MHX_OK) { r->variant = KF_MFMA; r->coop_L = 4; r->dense_lds = mfma_lds; }
+        launch_rec k = rec("matrix-core MALA kernel", 64 * MHX_MFMA_WAVES, 16 * MHX_MFMA_WAVES, mfma_lds);      // both images resident in LDS
+        if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_mala_mfma");
+        if (rc == MHX_OK) { r->step = k; r->variant = KF_MFMA; r->coop_L = 4; }
         else if (cfg->reduce_lanes > 1) return rc;
-        else r->jit_step = nullptr;
     }
     if (separable && !zig && !(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && (cfg->reduce_lanes > 1 || (cfg->reduce_lanes == 0 && r->dim > regmax))) {
         const int nblk = (r->dim + 3) / 4;
@@ -166,10 +168,10 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
             rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"),
                              {"MHX_JIT_MALA_COOP=1", "MHX_JIT_L=" + std::to_string(L), "MHX_JIT_NBL=" + std::to_string(NBL),
                               "MHX_JIT_TK=" + std::to_string(t->kind), "MHX_JIT_WAVES=" + std::to_string(waves)}, &m);
-            if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_mala_coop", &r->jit_step);
-            if (rc == MHX_OK) { r->variant = KF_COOP_JIT; r->coop_L = L; }
+            launch_rec k = rec("cooperative MALA kernel", 256, 4 * (64 / L), 0);      // whole waves of 64 / L chains
+            if (rc == MHX_OK) rc = rec_bind(&k, m, "mhx_jit_mala_coop");
+            if (rc == MHX_OK) { r->step = k; r->variant = KF_COOP_JIT; r->coop_L = L; }
             else if (cfg->reduce_lanes > 1) return rc;
-            else r->jit_step = nullptr;
         } else if (cfg->reduce_lanes > 1) {
             return mhx_fail(MHX_EINVAL, "mhx_mala_create: reduce_lanes=%d leaves %d blocks per lane (max %d)", L, NBL, nbl_max);
         }
@@ -184,14 +186,16 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
                                          "MHX_JIT_XR=" + std::to_string(xr)};
         if (zig) defs.push_back("MHX_JIT_GEN=1");
         rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"), defs, &m, {"-mllvm", "-amdgpu-unroll-threshold-private=100000"});
-        r->reg_lds = xr < r->dim ? (size_t)3 * (r->dim - xr) * 64 * sizeof(mhx_real) : 0;
-        if (zig) { r->reg_lds = MHX_MALA_ZIG_LDS_BYTES(r->dim, xr); r->normal_gen = MHX_GEN_ZIGGURAT; }      // one wave per block: mala_advance launches by reg_lds
-        if (rc == MHX_OK) rc = jit_kernel(m, zig ? "mhx_jit_mala_zig" : (xr < r->dim ? "mhx_jit_mala_split" : "mhx_jit_mala"), &r->jit_step, r->reg_lds,
-                                          "MALA register kernel");
+        // the forms that use LDS -- the split form (the tails of state, gradient and noise) and the ziggurat form (its table) -- run one
+        // wave per block, the plain form four
+        const size_t lds = zig ? MHX_MALA_ZIG_LDS_BYTES(r->dim, xr) : (xr < r->dim ? (size_t)3 * (r->dim - xr) * 64 * sizeof(mhx_real) : 0);
+        if (zig) r->normal_gen = MHX_GEN_ZIGGURAT;
+        launch_rec k = lds ? rec("MALA register kernel", 64, 64, lds) : rec("MALA register kernel", 256, 256, 0);
+        if (rc == MHX_OK) rc = rec_bind(&k, m, zig ? "mhx_jit_mala_zig" : (xr < r->dim ? "mhx_jit_mala_split" : "mhx_jit_mala"));
         if (rc == MHX_OK && user) rc = jit_function(m, "mhx_jit_mala_init", &r->jit_init);
-        if (rc == MHX_OK) r->variant = KF_REG_JIT;
+        if (rc == MHX_OK) { r->step = k; r->variant = KF_REG_JIT; }
         else if (zig) return rc;                                         // (no other kernel of this sampler has the ziggurat)
-        else { r->jit_step = nullptr; r->jit_init = nullptr; }           // the run-time-dimension kernel computes the same chain
+        else r->jit_init = nullptr;                                      // the run-time-dimension kernel computes the same chain
     }
     if (user && r->variant == KF_GENERIC) {
         // the user source must also define MHX_LOGDENSITY_AND_GRADIENT (the reference's
@@ -200,8 +204,12 @@ int api_mala_create(mhx_ctx* ctx, const mhx_target* t, const mhx_mala_cfg* cfg, 
         rc = jit_compile(ctx, jit_source(t, "mhx_mala_kernels.h"),
                          {"MHX_JIT_MALA=1", "MHX_JIT_TK=" + std::to_string(t->kind)}, &m);
         if (rc) return rc;
-        if ((rc = jit_function(m, "mhx_jit_mala", &r->jit_step))) return rc;
+        r->step = rec("MALA state-in-HBM kernel", 256, 256, 0);
+        if ((rc = rec_bind(&r->step, m, "mhx_jit_mala"))) return rc;
         if ((rc = jit_function(m, "mhx_jit_mala_init", &r->jit_init))) return rc;
+    } else if (r->variant == KF_GENERIC) {
+        r->step = rec("MALA state-in-HBM kernel", 256, 256, 0);
+        if ((rc = rec_bind(&r->step, (const void*)k_mala))) return rc;
     }
     *out = r.release();
     return MHX_OK;
@@ -236,7 +244,6 @@ static int mala_init(mhx_run* r, const mhx_real* init)
 static int mala_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int save_slot, int thinning)
 {
     mhx_ctx* ctx = r->ctx;
-    const mhx_real* tp = r->target->dparams;
     uint64_t done = 0;
     while (done < nsteps) {
         const uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
@@ -246,41 +253,11 @@ static int mala_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        unsigned grid = (unsigned)((r->n + 255) / 256);
-        if (r->variant == KF_COOP_JIT) {                         // L lanes per chain: whole waves
-            const long threads = (((long)r->n + (64 / r->coop_L) - 1) / (64 / r->coop_L)) * 64;
-            grid = (unsigned)((threads + 255) / 256);
-        }
-        if (r->variant == KF_MFMA && r->mfma_stream) {
-            grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
-            mhx_real* gA = r->d_mfma_img;
-            mhx_real* gAT = r->d_mfma_img + mfma_image_reals(r->dim);
-            void* params[] = {&a, &tp, &gA, &gAT};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds, ctx->stream, params, nullptr));
-        } else if (r->variant == KF_MFMA) {
-            grid = (unsigned)(((long)r->n + 16 * MHX_MFMA_WAVES - 1) / (16 * MHX_MFMA_WAVES));
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64 * MHX_MFMA_WAVES, 1, 1, (unsigned)r->dense_lds, ctx->stream, params, nullptr));
-        } else if (r->jit_step && r->variant == KF_REG_JIT && r->reg_lds) {
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, (unsigned)((r->n + 63) / 64), 1, 1, 64, 1, 1, (unsigned)r->reg_lds, ctx->stream, params, nullptr));
-        } else if (r->jit_step) {
-            void* params[] = {&a, &tp};
-            int rc = launch_module(r->jit_step, grid, 256, ctx->stream, params);
-            if (rc) return rc;
-        } else {
-            hipLaunchKernelGGL(k_mala, dim3(grid), dim3(256), 0, ctx->stream, a, tp);
-        }
+        int rc = launch(r->step, ctx->stream, r->n, 1, &a);
+        if (rc) return rc;
         HIP_TRY(hipGetLastError());
         r->stats.launches++;
-        if (save_next != MHX_NO_SAVE) {
-            const uint64_t lastt = r->tau + chunk;
-            if ((uint64_t)save_next <= lastt) {
-                const uint64_t k = (lastt - save_next) / (uint64_t)thinning + 1;
-                save_next += (uint32_t)(k * (uint64_t)thinning);
-                save_slot += (int)k;
-            }
-        }
+        save_cursor_skip(r, chunk, thinning, &save_next, &save_slot);
         r->tau += chunk;
         done += chunk;
     }

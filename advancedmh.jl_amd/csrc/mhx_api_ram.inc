@@ -169,6 +169,24 @@ static mhx_ram_args ram_args(const mhx_run* r)
 
 static unsigned grid1d(long n, int block) { return (unsigned)((n + block - 1) / block); }
 
+// The launch record of a RAM run's step kernel -- kernel(args, tparams): a block is ONE wave of 64 / G chains (the deferred form: one
+// chain), the grid whole rounds of 8 blocks, the LDS each chain's ring and mirror.  `m`: the module of a user target, else the kernel
+// is pre-built.  ram_pick_shape reads the option RAM_G, and options are read when they are used: api_ram_create fills r->step for
+// the shape of that moment, and ram_advance asks again at every call (see there).
+static int ram_step_record(mhx_run* r, jit_module* m, launch_rec* out)
+{
+    const int d = r->dim;
+    const ram_shape* sh = ram_pick_shape(r->ctx, d);
+    if (!sh) return mhx_fail(MHX_EINVAL, "RAM: dim %d exceeds the largest kernel shape", d);
+    const int cpw = r->defer_R ? 1 : 64 / sh->G;                     // chains per wave (= block)
+    const ram_fn fn = r->defer_R ? ram_defer_fn(r->defer_R) : (r->target->kind == MHX_TARGET_CORR_GAUSS ? sh->fn_dense : sh->fn);
+    const int ring_f = r->defer_R ? MHX_RAM_RING(64, r->defer_R) : sh->ring_f;
+    size_t lds = (size_t)cpw * (size_t)(mhx_ram_rings(ring_f, d) + mhx_ram_mirror(d)) * sizeof(mhx_real);
+    if (r->defer_R) lds += (size_t)MHX_RAM_DEFER_STAGE * sizeof(mhx_real);       // the fold's coefficient staging
+    *out = rec_shape("RAM kernel", 64, cpw, lds, {&r->k_tp}, 8);
+    return m ? rec_bind(out, m, "mhx_jit_ram") : rec_bind(out, (const void*)fn);
+}
+
 int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mhx_run** out)
 {
     if (!ctx || !t || !cfg || !out) return mhx_fail(MHX_EINVAL, "mhx_ram_create: NULL argument");
@@ -212,18 +230,18 @@ int api_ram_create(mhx_ctx* ctx, const mhx_target* t, const mhx_ram_cfg* cfg, mh
         HIP_TRY(hipMalloc(&r->d_defer, per * (size_t)n * sizeof(mhx_real)));
         HIP_TRY(hipMemsetAsync(r->d_defer, 0, per * (size_t)n * sizeof(mhx_real), ctx->stream));
     }
+    jit_module* m = nullptr;
     if (t->kind == MHX_TARGET_USER) {
         const ram_shape* sh = ram_pick_shape(ctx, (int)d);
-        jit_module* m = nullptr;
         const int jg = r->defer_R ? 64 : sh->G, jr = r->defer_R ? r->defer_R : sh->R;
         std::vector<std::string> defs = {"MHX_JIT_RAM=1", "MHX_JIT_G=" + std::to_string(jg), "MHX_JIT_R=" + std::to_string(jr),
                                          "MHX_JIT_TK=" + std::to_string(t->kind)};
         if (r->defer_R) defs.push_back("MHX_JIT_DEFER_K=" + std::to_string(MHX_RAM_DEFER_K));
         rc = jit_compile(ctx, jit_source(t, "mhx_ram_kernels.h"), defs, &m);
         if (rc) return rc;
-        if ((rc = jit_function(m, "mhx_jit_ram", &r->jit_step))) return rc;
         if ((rc = jit_function(m, "mhx_jit_ram_init", &r->jit_init))) return rc;
     }
+    if ((rc = ram_step_record(r.get(), m, &r->step))) return rc;
     // S0 = I (RAM.jl:198-199) until mhx_ram_set_factor says otherwise
     if ((rc = api_ram_set_factor(r.get(), nullptr))) return rc;
     *out = r.release();
@@ -456,22 +474,18 @@ static int ram_init(mhx_run* r, const mhx_real* init)
 static int ram_advance(mhx_run* r, uint64_t nsteps, uint64_t n_adapt, uint32_t save_next, int save_slot, int thinning)
 {
     mhx_ctx* ctx = r->ctx;
-    const mhx_real* tp = r->target->dparams;
-    const int d = r->dim;
-    const ram_shape* sh = ram_pick_shape(r->ctx, d);
-    if (!sh) return mhx_fail(MHX_EINVAL, "RAM: dim %d exceeds the largest kernel shape", d);
-    const int cpw = r->defer_R ? 1 : 64 / sh->G;                     // chains per wave (= block)
-    const ram_fn fn = r->defer_R ? ram_defer_fn(r->defer_R) : (r->target->kind == MHX_TARGET_CORR_GAUSS ? sh->fn_dense : sh->fn);
-    const int ring_f = r->defer_R ? MHX_RAM_RING(64, r->defer_R) : sh->ring_f;
-    size_t lds = (size_t)cpw * (size_t)(mhx_ram_rings(ring_f, d) + mhx_ram_mirror(d)) * sizeof(mhx_real);
-    if (r->defer_R) lds += (size_t)MHX_RAM_DEFER_STAGE * sizeof(mhx_real);       // the fold's coefficient staging
-    if (const char* pad = opt(r->ctx, "RAM_LDS_PAD")) {               // tuning knob: fewer resident waves per CU (DESIGN.md 6.3)
-        lds += (size_t)atol(pad);
-        if (lds > 65536 && !r->jit_step)
-            if (int rcl = kernel_lds_limit((const void*)fn, lds, "RAM kernel")) return rcl;
+    // The record of this call.  ram_pick_shape reads the option RAM_G, a call-time option: a pre-built kernel's record is filled
+    // again at every call, from the shape picked NOW (r->step holds the one picked at create); a user target's module was compiled
+    // for the shape picked at create and keeps that record.  A pad changes this call's copy alone, and has the kernel allowed the
+    // padded size.
+    launch_rec k = r->step;
+    if (!k.mod_fn)
+        if (int rcs = ram_step_record(r, nullptr, &k)) return rcs;
+    if (const char* pad = opt(ctx, "RAM_LDS_PAD")) {                  // tuning knob: fewer resident waves per CU (DESIGN.md 6.3)
+        k.lds += (size_t)atol(pad);
+        if (k.lds > 65536 && !k.mod_fn)
+            if (int rcl = kernel_lds_limit(k.fn, k.lds, k.what)) return rcl;
     }
-    const long nwaves = ((long)r->n + cpw - 1) / cpw;
-    const unsigned grid = (unsigned)(((nwaves + 7) / 8) * 8);
     uint64_t done = 0;
     std::vector<mhx_real> eta;
     while (done < nsteps) {
@@ -504,23 +518,11 @@ static int ram_advance(mhx_run* r, uint64_t nsteps, uint64_t n_adapt, uint32_t s
         a.save_next = save_next;
         a.save_slot = save_slot;
         a.thinning = thinning;
-        if (r->jit_step) {
-            void* params[] = {&a, &tp};
-            HIP_TRY(hipModuleLaunchKernel(r->jit_step, grid, 1, 1, 64, 1, 1, (unsigned)lds, ctx->stream, params, nullptr));
-        } else {
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, ctx->stream, a, tp);
-        }
+        if (int rcl = launch(k, ctx->stream, r->n, 1, &a)) return rcl;
         HIP_TRY(hipGetLastError());
         r->stats.launches++;
         if (record_after) { int rcw = ram_watch_record(r); if (rcw) return rcw; }
-        if (save_next != MHX_NO_SAVE) {
-            const uint64_t last = r->tau + chunk;
-            if ((uint64_t)save_next <= last) {
-                const uint64_t k = (last - save_next) / (uint64_t)thinning + 1;
-                save_next += (uint32_t)(k * (uint64_t)thinning);
-                save_slot += (int)k;
-            }
-        }
+        save_cursor_skip(r, chunk, thinning, &save_next, &save_slot);
         r->tau += chunk;
         done += chunk;
     }

@@ -270,6 +270,41 @@ def test_lane_per_walker_kernel_one_launch_per_sweep(mhx, oracle, d, W, kind, re
     _same(f[0][1], ref["accepted"], "accepted vs oracle")
 
 
+def test_half_steps_with_preloaded_arguments_are_the_oracle(mhx, oracle, real):
+    """Option EMCEE_PRELOAD: the half-step kernel of the lane-per-walker form takes its hot arguments as scalars of their own ahead
+    of the argument block -- the one launch whose argument list differs.  130 walkers: halves of 65, two blocks each, the second
+    one lane.  That the option was heeded shows in the context's modules: the same run with it is ONE more module (MHX_JIT_PRELOAD
+    is among its defines), and a kernel compiled to read preloaded scalars gives the oracle's chain only if it is handed them."""
+    import mhx._lib as L
+    d, W = 5, 130
+    ctx = L.Context(0, real)
+    for k, v in (("EMCEE_FUSED", "0"), ("EMCEE_PERSIST", "0")):
+        ctx.set_option(k, v)
+    model, spl = mhx.DensityModel(mhx.IsoGaussian(d)), mhx.Ensemble(W, mhx.StretchProposal(mhx.MvNormal(mhx.zeros(d), mhx.I)))
+    plain = mhx.Run(model, spl, seed=21, reduce_lanes=1, ctx=ctx)
+    before = sum(ctx.jit_counts())
+    mhx.Run(model, spl, seed=21, reduce_lanes=1, ctx=ctx).close()
+    assert sum(ctx.jit_counts()) == before                      # (the same run again: no new module)
+    ctx.set_option("EMCEE_PRELOAD", "1")
+    run = mhx.Run(model, spl, seed=21, reduce_lanes=1, ctx=ctx)
+    assert sum(ctx.jit_counts()) == before + 1
+    plain.close()
+    init = cases.emcee_init(d, W, 2)
+    run.init(init)
+    run.sample(5, 2, 2, 0)
+    got, acc = run.samples()
+    st = run.stats()
+    assert st["kernel_variant"] == 2 and st["launches"] == 2 * 10
+    ref = oracle.emcee(oracle.iso_gauss(d), 2.0, 1, oracle.schedule(5, 2, 2), 21, 0, W, init)
+    _same(got, ref["samples"], "samples")
+    _same(acc, ref["accepted"], "accepted")
+    x, lp, cnt = run.state()
+    _same(x, ref["final_x"], "final x")
+    _same(lp, ref["final_lp"], "final lp")
+    _same(cnt, ref["accept_counts"], "accept counts")
+    run.close()
+
+
 @pytest.mark.parametrize("world", [2, 3, 8])
 @pytest.mark.parametrize("d,W,user", [(50, 100, False), (7, 33, True), (20, 64, False)])
 def test_sharded_ensemble_slices_reproduce_the_single_gpu_run(mhx, oracle, d, W, user, world, real):

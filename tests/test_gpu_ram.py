@@ -60,6 +60,24 @@ def test_ram_long_run_spans_several_launches(mhx, oracle, real):
     _same(cnt, ref["accept_counts"], "accept counts")
 
 
+def test_ram_with_an_lds_pad_is_the_same_chain(mhx, oracle, engine, real):
+    """Option RAM_LDS_PAD (fewer resident waves per CU): the launch asks for the padded LDS size -- here above 64 KB, which the
+    kernel has to be allowed first -- and the chain does not change.  20 chains at d = 6: four per wave, five waves, a grid
+    rounded up to 8 blocks, the last wave empty but for its first chains."""
+    engine.set("RAM_LDS_PAD", "70000")
+    d, C, N = 6, 20, 12
+    model = mhx.DensityModel(mhx.IsoGaussian(d))
+    chain, S, st, lo, hi, x, lp, cnt = _run(mhx, model, mhx.RobustAdaptiveMetropolis(), N, C, 13, 1, None, num_warmup=8, discard_initial=2, thinning=2)
+    ref = oracle.ram(oracle.iso_gauss(d), oracle.schedule(N, 2, 2, 8), 13, 1, C, init=None)
+    _same(chain.value, ref["samples"], "samples")
+    _same(chain.accepted, ref["accepted"], "accepted")
+    _same(S, ref["S"], "S")
+    _same(x, ref["final_x"], "final x")
+    _same(lp, ref["final_lp"], "final lp")
+    _same(cnt, ref["accept_counts"], "accept counts")
+    assert chain.stats["kernel_variant"] == 0
+
+
 def test_ram_iso_target_random_init_and_custom_factor(mhx, oracle, real):
     d, C, N = 5, 7, 30
     rng = np.random.default_rng(3)
