@@ -387,21 +387,21 @@ int api_ctx_pci_bus_id(const mhx_ctx* ctx, char* buf, size_t len)
     HIP_TRY(hipDeviceGetPCIBusId(buf, (int)len, ctx->device));
     return MHX_OK;
 }
-int api_ctx_host_pin_counts(const mhx_ctx* ctx, long* registered, long* released)
+int api_ctx_host_pin_counts(const mhx_ctx* ctx, int64_t* registered, int64_t* released)
 {
     if (registered) *registered = ctx->pins_registered;
     if (released) *released = ctx->pins_released;
     return MHX_OK;
 }
 
-int api_ctx_jit_counts(const mhx_ctx* ctx, long* compiles, long* cache_hits)
+int api_ctx_jit_counts(const mhx_ctx* ctx, int64_t* compiles, int64_t* cache_hits)
 {
     if (compiles) *compiles = ctx->jit_compiles;
     if (cache_hits) *cache_hits = ctx->jit_cache_hits;
     return MHX_OK;
 }
 
-int api_ctx_jit_compiler(const mhx_ctx* ctx, char* compiler, size_t len, long* ext_compiles)
+int api_ctx_jit_compiler(const mhx_ctx* ctx, char* compiler, size_t len, int64_t* ext_compiles)
 {
     if (compiler && len) {
         const char* jc = nullptr;

@@ -391,14 +391,15 @@ int api_ram_watch_factors(mhx_run* r, const int32_t* chains, int n)
     return MHX_OK;
 }
 
-int api_ram_get_watched_factors(mhx_run* r, mhx_real* S, long capacity, long* n_recorded, int* n_watched)
+int api_ram_get_watched_factors(mhx_run* r, mhx_real* S, int64_t capacity, int64_t* n_recorded, int32_t* n_watched)
 {
-    if (!r || r->kind != RUN_RAM) return mhx_fail(MHX_EINVAL, "mhx_ram_get_watched_factors: not a RAM run");
-    if (n_recorded) *n_recorded = r->watch_count;
-    if (n_watched) *n_watched = r->watch_n;
+    const bool ram = r && r->kind == RUN_RAM;                       // the counts are written on every path: 0 for a run that is not RAM
+    if (n_recorded) *n_recorded = ram ? r->watch_count : 0;
+    if (n_watched) *n_watched = ram ? r->watch_n : 0;
+    if (!ram) return mhx_fail(MHX_EINVAL, "mhx_ram_get_watched_factors: not a RAM run");
     if (!S) return MHX_OK;                                          // a query
     if (r->watch_n <= 0 || r->watch_count <= 0) return mhx_fail(MHX_ESTATE, "mhx_ram_get_watched_factors: nothing was recorded (mhx_ram_watch_factors, then a sampling call that keeps samples)");
-    if (capacity < r->watch_count) return mhx_fail(MHX_EINVAL, "mhx_ram_get_watched_factors: the buffer holds %ld samples, %ld were recorded", capacity, (long)r->watch_count);
+    if (capacity < r->watch_count) return mhx_fail(MHX_EINVAL, "mhx_ram_get_watched_factors: the buffer holds %ld samples, %ld were recorded", (long)capacity, (long)r->watch_count);
     HIP_TRY(hipSetDevice(r->ctx->device));
     const size_t tri = (size_t)r->dim * (size_t)(r->dim + 1) / 2;
     COPY_SYNC(r->ctx->stream, S, r->d_watch, (size_t)r->watch_count * (size_t)r->watch_n * tri * sizeof(mhx_real), hipMemcpyDeviceToHost);
@@ -433,14 +434,15 @@ static int ram_prepare_step_stats(mhx_run* r, const mhx_schedule* s, uint64_t n_
     return MHX_OK;
 }
 
-int api_ram_get_step_stats(mhx_run* r, mhx_real* log_alpha, double* eta, long capacity, long* n_recorded)
+int api_ram_get_step_stats(mhx_run* r, mhx_real* log_alpha, double* eta, int64_t capacity, int64_t* n_recorded)
 {
-    if (!r || r->kind != RUN_RAM) return mhx_fail(MHX_EINVAL, "mhx_ram_get_step_stats: not a RAM run");
-    if (n_recorded) *n_recorded = r->rec_n;
+    const bool ram = r && r->kind == RUN_RAM;                    // the count is written on every path: 0 for a run that is not RAM
+    if (n_recorded) *n_recorded = ram ? r->rec_n : 0;
+    if (!ram) return mhx_fail(MHX_EINVAL, "mhx_ram_get_step_stats: not a RAM run");
     if (!log_alpha && !eta) return MHX_OK;                       // a query of the recorded count
     if (r->rec_n <= 0) return mhx_fail(MHX_ESTATE, "mhx_ram_get_step_stats: the last sampling call recorded no samples");
     if (capacity < r->rec_n)
-        return mhx_fail(MHX_EINVAL, "mhx_ram_get_step_stats: the buffers hold %ld samples, the last call recorded %ld", capacity, (long)r->rec_n);
+        return mhx_fail(MHX_EINVAL, "mhx_ram_get_step_stats: the buffers hold %ld samples, the last call recorded %ld", (long)capacity, (long)r->rec_n);
     HIP_TRY(hipSetDevice(r->ctx->device));
     if (log_alpha) COPY_SYNC(r->ctx->stream, log_alpha, r->d_rec_loga, (size_t)r->rec_n * (size_t)r->n * sizeof(mhx_real), hipMemcpyDeviceToHost);
     if (eta) memcpy(eta, r->rec_eta.data(), (size_t)r->rec_n * sizeof(double));

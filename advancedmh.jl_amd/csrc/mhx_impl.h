@@ -5,6 +5,8 @@
 // include/mhx.h live in mhx_abi.cpp and forward to the instantiation the handle belongs to (the first word of every
 // handle is its mhx_dtype).  This header declares the api_* functions of both, so that definitions (mhx_api.hip) and
 // calls (mhx_abi.cpp) are checked against ONE set of prototypes by the C++ linker (mangled names carry the types).
+// mhx_abi.cpp's forwarder reads each parameter type off these prototypes: an api_* function takes the public entry's
+// parameters in order and in the public types (int64_t, not long), handles and real buffers as the namespace's own.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -32,9 +34,9 @@ void mhx_jit_unlock();
     int api_ctx_get_option(const mhx_ctx* ctx, const char* name, char* buf, size_t len);                               \
     int api_ctx_pci_bus_id(const mhx_ctx* ctx, char* buf, size_t len);                                                 \
     int api_run_shape(const mhx_run* r, int32_t* dim, int32_t* nchains);                                               \
-    int api_ctx_jit_counts(const mhx_ctx* ctx, long* compiles, long* cache_hits);                                      \
-    int api_ctx_jit_compiler(const mhx_ctx* ctx, char* compiler, size_t len, long* ext_compiles);                      \
-    int api_ctx_host_pin_counts(const mhx_ctx* ctx, long* registered, long* released);                                  \
+    int api_ctx_jit_counts(const mhx_ctx* ctx, int64_t* compiles, int64_t* cache_hits);                                \
+    int api_ctx_jit_compiler(const mhx_ctx* ctx, char* compiler, size_t len, int64_t* ext_compiles);                   \
+    int api_ctx_host_pin_counts(const mhx_ctx* ctx, int64_t* registered, int64_t* released);                           \
     int api_target_builtin(mhx_ctx* ctx, int kind, int dim, const REAL* params, size_t nparams, mhx_target** out);     \
     int api_target_from_hip_source(mhx_ctx* ctx, const char* src, int dim, const REAL* data, size_t ndata,             \
                                    mhx_target** out);                                                                  \
@@ -58,9 +60,9 @@ void mhx_jit_unlock();
     int api_ram_get_factor(mhx_run* r, REAL* S, uint8_t* status);                                                      \
     int api_ram_get_diag_range(mhx_run* r, REAL* diag_min, REAL* diag_max);                                            \
     int api_ram_get_adapt_state(mhx_run* r, REAL* log_alpha, double* eta, uint8_t* isaccept, uint64_t* iteration);     \
-    int api_ram_get_step_stats(mhx_run* r, REAL* log_alpha, double* eta, long capacity, long* n_recorded);             \
+    int api_ram_get_step_stats(mhx_run* r, REAL* log_alpha, double* eta, int64_t capacity, int64_t* n_recorded);       \
     int api_ram_watch_factors(mhx_run* r, const int32_t* chains, int n);                                               \
-    int api_ram_get_watched_factors(mhx_run* r, REAL* S, long capacity, long* n_recorded, int* n_watched);             \
+    int api_ram_get_watched_factors(mhx_run* r, REAL* S, int64_t capacity, int64_t* n_recorded, int32_t* n_watched);   \
     int api_run_init(mhx_run* r, const REAL* initial_params);                                                          \
     int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples);                                           \
     int api_run_get_samples(mhx_run* r, REAL* samples, uint8_t* accepted);                                             \

@@ -45,6 +45,35 @@ def test_ctypes_mirror_matches_the_header():
         assert got == want, "%s vs %s:\n%r\n%r" % (pyname, cname, got, want)
 
 
+SCALARS = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "double": C.c_double, "int": C.c_int}
+
+
+def test_ctypes_argtypes_match_the_prototypes():
+    """every prototype of the header: the symbol exists, `argtypes` has one entry per parameter, a scalar parameter has exactly its
+    ctypes scalar and a pointer parameter a pointer type (a wrong width or count would shift every argument behind it)"""
+    import mhx
+    lib = mhx.lib()
+    src = re.sub(r"/\*.*?\*/", "", HDR, flags=re.S)
+    protos = re.findall(r"\b(mhx_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S)
+    assert len(protos) >= 103
+    for name, args in protos:
+        assert hasattr(lib, name), "libmhx.so does not export %s" % name
+        args = " ".join(args.split())
+        params = [] if args in ("", "void") else _split_top(args)
+        if not params:
+            continue
+        got = getattr(lib, name).argtypes
+        assert got is not None, "%s: no argtypes in mhx/_lib.py" % name
+        assert len(got) == len(params), "%s: %d argtypes, %d parameters in include/mhx.h" % (name, len(got), len(params))
+        for i, (p, t) in enumerate(zip(params, got)):
+            if "*" in p:
+                assert t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer), "%s: parameter %d `%s` is bound as %r" % (name, i, p, t)
+            else:
+                scalar = [w for w in p.split() if w in SCALARS]
+                assert len(scalar) == 1, "%s: unparsed parameter `%s`" % (name, p)
+                assert t is SCALARS[scalar[0]], "%s: parameter %d `%s` is bound as %r" % (name, i, p, t)
+
+
 def julia_structs():
     out = {}
     for name, body in re.findall(r"^struct\s+(\w+)\s*\n(.*?)^end", JL, flags=re.S | re.M):

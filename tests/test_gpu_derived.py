@@ -9,6 +9,8 @@ Shapes: the smallest at which the frame can go wrong.  C = 1, 63, 65, 257: a lon
 plus one lane.  A lane maps 4 draws together and a strip is 8 draws (2 groups), so n_saved = 1, 2, 7 and 9: one draw, fewer than a
 group, a group plus a ragged end, a strip plus one.  d = 1 and 5 with nout = 7, 3 and 1.  Five map sources per width, and one that does not compile."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -317,6 +319,42 @@ def test_refusals(mhx, oracle, real):
         der2 = run.derive(MAP_LAST)
         assert _same_bits(der2.samples()[0], _host(oracle, MAP_LAST.source, run.samples(False)[0], 3))
         der2.close()
+    finally:
+        der.close()
+        run.close()
+
+
+def _refuse_list():
+    """the entry points include/mhx.h lists under `refuse` at mhx_run_derive, written out: "mhx_run_init, _sample, ...; mhx_ram_..." """
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mhx.h")).read()
+    text = re.search(r"refuse\s+with MHX_ESTATE[^:]*looked at:(.*?)\(and with them", hdr, flags=re.S).group(1)
+    names = []
+    for family in text.split(";"):
+        for w in re.findall(r"(?:mhx)?_\w+", family):
+            names.append(w if w.startswith("mhx_") else re.match(r"mhx_[a-z]+", names[-1]).group(0) + w)
+    return names
+
+
+def test_every_entry_on_the_headers_refuse_list_refuses_a_derived_run(mhx, real):
+    """Raw ctypes, the derived run's handle and every other argument zero: the header promises the guard runs "before anything else is
+    looked at", so NULL pointers and 0 sizes are within the contract.  MHX_ESTATE, "derived" and the entry's own name in the message."""
+    names = _refuse_list()
+    assert len(names) == len(set(names)) == 22
+    assert [sum(n.startswith(p) for n in names) for p in ("mhx_run_", "mhx_ram_", "mhx_emcee_")] == [8, 8, 6]
+    x = _tensor(real, 7, 3, 63, 5, edges=False)
+    run = plant(mhx, x)
+    der = run.derive(mhx.HipMap("MHX_DERIVED(x, y, d, data, ndata) { y.set(0, x[0] * x[0]); }\n", 1))
+    try:
+        lib = mhx.lib()
+        for name in names:
+            fn = getattr(lib, name)
+            zeros = [None if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer) else 0 for t in fn.argtypes[1:]]
+            assert fn(der.h, *zeros) == mhx.MHX_ESTATE, name
+            msg = lib.mhx_last_error().decode()
+            assert "derived" in msg and msg.startswith(name + ":"), (name, msg)
+        # the source run is untouched by all that: it still samples
+        run.sample(7, 0, 1, 0)
+        assert run.samples(False)[0].shape == (7, 4, 63)
     finally:
         der.close()
         run.close()
