@@ -526,6 +526,50 @@ MHX_DEV double mhx_zig_refine(const mhx_philox_key& ks, const double* __restrict
     return mhx_zig_slow(ks, zt, id_lo, id_hi, step, stream, n, x, layer2, 2u);
 }
 
+// The same normal by TWO lanes (2e, 2e + 1) per failed candidate: the chain of mhx_zig_refine is two Philox calls and two exponentials
+// one after the other, and each pair differs in one operand only -- so ONE Philox call gives the even lane the candidate's block and the
+// odd lane the block of rejection attempt 1 (counter word 3 is a per-lane select), ONE mhx_exp call gives f0 in the even and f1 in the
+// odd lane, and the lanes swap what they made (DPP quad_perm [1,0,3,2]: no LDS traffic).  After a swap both lanes hold the same values
+// and take the same branches: every exit is reached by both, so both are active at every swap; a pair that goes on into mhx_zig_slow
+// runs it in both lanes on the same values.  Every value comes from the same function on the same inputs as in mhx_zig_refine: the
+// same bits.  Both lanes return the normal; the caller lets the even one store it.
+MHX_DEV mhx_u32 mhx_zig_swap1(const mhx_u32 v) { return (mhx_u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false); }
+MHX_DEV double mhx_zig_swap1(const double v)
+{
+    const mhx_u64 b = mhx_d2u(v);
+    return mhx_u2d(((mhx_u64)mhx_zig_swap1((mhx_u32)(b >> 32)) << 32) | mhx_zig_swap1((mhx_u32)b));
+}
+MHX_DEV double mhx_zig_refine2(const mhx_philox_key& ks, const double* __restrict__ zt, const mhx_u32 id_lo, const mhx_u32 id_hi,
+                               const mhx_u32 step, const mhx_u32 stream, const mhx_u32 n, const bool odd)
+{
+    const mhx_u32 c3 = odd ? (((stream | MHX_STREAM_RETRY) << 28) | ((n << 8) | 1u)) : ((stream << 28) | (n >> 1));
+    const mhx_u32x4 own = mhx_philox(ks, id_lo, id_hi, step, c3);
+    mhx_u32x4 oth;
+    oth.x = mhx_zig_swap1(own.x); oth.y = mhx_zig_swap1(own.y); oth.z = mhx_zig_swap1(own.z); oth.w = mhx_zig_swap1(own.w);
+    mhx_u32x4 w, v;                                                // w: the failed candidate's block, v: attempt 1's, in both lanes
+    w.x = odd ? oth.x : own.x; w.y = odd ? oth.y : own.y; w.z = odd ? oth.z : own.z; w.w = odd ? oth.w : own.w;
+    v.x = odd ? own.x : oth.x; v.y = odd ? own.y : oth.y; v.z = odd ? own.z : oth.z; v.w = odd ? own.w : oth.w;
+    const mhx_u32 hi = (n & 1u) ? w.z : w.x, lo = (n & 1u) ? w.w : w.y;
+    mhx_u32 layer = lo & (mhx_u32)(MHX_ZIG_N - 1);
+    const mhx_u32 layer2 = v.y & (mhx_u32)(MHX_ZIG_N - 1);
+    const double xl = zt[layer], xl1 = zt[layer + 1];
+    const double xn = zt[layer2], xn1 = zt[layer2 + 1];
+    const double ax = mhx_zig_ax(hi, lo, xl);
+    double x = mhx_zig_signed(ax, lo);
+    if (ax < xl1) return x;                                        // (not a failed candidate after all: callers only send failures)
+    if (layer == 0u) return mhx_zig_slow(ks, zt, id_lo, id_hi, step, stream, n, x, layer, 1u);
+    const double xsq = x * x;
+    const double xo = odd ? xl1 : xl;
+    const double fown = mhx_exp(-0.5 * (xo * xo - xsq));
+    const double foth = mhx_zig_swap1(fown);
+    const double f0 = odd ? foth : fown, f1 = odd ? fown : foth;
+    if (mhx_fma(mhx_u01_half(v.z, v.w), f0 - f1, f1) < 1.0) return x;
+    const double ax2 = mhx_zig_ax(v.x, v.y, xn);
+    x = mhx_zig_signed(ax2, v.y);
+    if (ax2 < xn1) return x;
+    return mhx_zig_slow(ks, zt, id_lo, id_hi, step, stream, n, x, layer2, 2u);
+}
+
 // normal number n (0-based) of (id, step, stream), straight from the table in global memory: the kernels off the hot path
 MHX_DEV double mhx_zig_normal(const mhx_philox_key& ks, const mhx_u32 id_lo, const mhx_u32 id_hi, const mhx_u32 step,
                               const mhx_u32 stream, const mhx_u32 n)

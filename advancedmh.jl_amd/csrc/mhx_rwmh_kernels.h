@@ -416,6 +416,14 @@ MHX_DEV void mhx_rwmh_whiten_body(const mhx_rwmh_args& a, const mhx_real* __rest
 #define MHX_ZIG_KS(NBL) (MHX_ZIG_KS_FIT(NBL) < 1 ? 1 : (MHX_ZIG_KS_FIT(NBL) > 4 ? 4 : MHX_ZIG_KS_FIT(NBL)))
 #define MHX_ZIG_WAVE_BYTES(NBL) (MHX_ZIG_KS(NBL) * (MHX_ZIG_SLAB_BYTES(NBL) + 512) + 128)
 #define MHX_ZIG_LDS_BYTES(NBL) (MHX_ZIG_TABLE_BYTES + 4 * MHX_ZIG_WAVE_BYTES(NBL))
+#if MHX_REAL64
+// The generator / consumer wave pairs (mhx_rwmh_coop_pairs_body): MHX_ZIG_FIX2 = 1: two lanes per failed candidate in the fix-up pass of
+// the generator wave (mhx_zig_refine2), 0: one lane (mhx_zig_refine).  Same chains bit for bit either way; measured at C2 in
+// profiles/zig_fixup2/README.md.
+#ifndef MHX_ZIG_FIX2
+#define MHX_ZIG_FIX2 1
+#endif
+#endif
 // where slot sl (= 4 i + j: block i of the lane, normal j of the block) of lane `ln` lives in a step's slab of normals
 #if MHX_REAL64
 #define MHX_ZIG_SLAB_AT(sl, ln) (((((sl) >> 1) * 64 + (ln)) << 1) + ((sl) & 1))
@@ -462,7 +470,9 @@ typedef const __attribute__((address_space(3))) mhx_f2v* mhx_lds_f2v;
 // (a group of `ng` steps: zfm[s][lane] = the lane's failed slots of step step0 + s, whose normals live in zn + s * slabd)
 // (Measured and removed in round 5, profiles/r04y_fastpath_ab.log: the failure bits from the SIGN of |x| - x[layer + 1] shifted in by
 // one v_alignbit_b32 per candidate -- 47 instructions fewer per wave-step and SLOWER, one dependent chain per candidate.)
-template <int L>
+// FIX2 (fp64): two lanes per failed candidate -- queue entry e is served by lanes 2e and 2e + 1 (mhx_zig_refine2: one Philox call and
+// one exponential per fixer lane instead of two of each), a window holds 32 entries, the even lane stores.
+template <int L, bool FIX2 = false>
 MHX_DEV void mhx_zig_fixup(const mhx_philox_key& ks, const mhx_real* __restrict__ zt, mhx_real* __restrict__ zn,
                            unsigned short* __restrict__ zq, const mhx_u64* __restrict__ zfm, const int ng, const int slabd,
                            const int lane, const long wave,
@@ -474,10 +484,11 @@ MHX_DEV void mhx_zig_fixup(const mhx_philox_key& ks, const mhx_real* __restrict_
     constexpr int CPW = 64 / L;
     // Queue positions without a prefix sum over the lanes: round k takes the k-th failure of every lane that has one; the
     // lanes of a round are ranked by mbcnt over the round's ballot, the rounds follow each other in the queue.  (Nearly all
-    // lanes have 0 or 1 failure: one or two rounds.)  One pass both numbers and stores the first 64 entries -- all of them
-    // unless more than 64 candidates of the wave-step failed, in which case further windows of 64 follow.
+    // lanes have 0 or 1 failure: one or two rounds.)  One pass both numbers and stores the first WIN entries -- all of them
+    // unless more than WIN candidates of the wave-step failed, in which case further windows of WIN follow.
+    constexpr int WIN = FIX2 ? 32 : 64;          // entries per window
     int total = 0;
-    for (int win = 0; win == 0 || win < total; win += 64) {
+    for (int win = 0; win == 0 || win < total; win += WIN) {
         int base = -win;
         for (int s = 0; s < ng; ++s) {
             mhx_u64 f = fm_in_reg ? fm_reg : zfm[s * 64 + lane];      // (a group of one step: the mask never went to LDS)
@@ -488,7 +499,7 @@ MHX_DEV void mhx_zig_fixup(const mhx_philox_key& ks, const mhx_real* __restrict_
                     const int e = base + (int)__builtin_amdgcn_mbcnt_hi((mhx_u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((mhx_u32)m, 0u));
                     const int p = __ffsll((long long)f) - 1;
                     const int sl = rev_top < 0 ? p : 4 * (rev_top - (p & 15)) + (p >> 4);
-                    if (e >= 0 && e < 64) zq[e] = (unsigned short)(lane | (sl << 6) | (s << 12));
+                    if (e >= 0 && e < WIN) zq[e] = (unsigned short)(lane | (sl << 6) | (s << 12));
                 }
                 f &= f - 1ull;
                 base += __popcll(m);
@@ -496,9 +507,9 @@ MHX_DEV void mhx_zig_fixup(const mhx_philox_key& ks, const mhx_real* __restrict_
         }
         total = base + win;
         MHX_WAVE_SYNC();
-        const int nent = total - win < 64 ? total - win : 64;
-        if (lane < nent) {
-            const int ent = zq[lane];
+        const int nent = total - win < WIN ? total - win : WIN;
+        if (lane < (FIX2 ? 2 * nent : nent)) {
+            const int ent = zq[FIX2 ? lane >> 1 : lane];
             const int ol = ent & 63, sl = (ent >> 6) & 63, sg = ent >> 12;
             const mhx_u32 step = step0 + (mhx_u32)sg;
             mhx_real* const zns = zn + sg * slabd;
@@ -507,7 +518,17 @@ MHX_DEV void mhx_zig_fixup(const mhx_philox_key& ks, const mhx_real* __restrict_
             const mhx_u32 b = (mhx_u32)(ol / CPW + L * (sl >> 2));
             const mhx_u32 n = 4u * b + (mhx_u32)(sl & 3);
             // nothing but the slot number was kept: the failed candidate is re-derived from its Philox block
+#if MHX_REAL64
+            if (FIX2) {
+                const bool odd = (lane & 1) != 0;
+                const mhx_real z = mhx_zig_refine2(ks, zt, (mhx_u32)oid, (mhx_u32)(oid >> 32), step, stream, n, odd);
+                if (!odd) zns[MHX_ZIG_SLAB_AT(sl, ol)] = z;
+            } else {
+                zns[MHX_ZIG_SLAB_AT(sl, ol)] = mhx_zig_refine(ks, zt, (mhx_u32)oid, (mhx_u32)(oid >> 32), step, stream, n);
+            }
+#else
             zns[MHX_ZIG_SLAB_AT(sl, ol)] = mhx_zig_refine(ks, zt, (mhx_u32)oid, (mhx_u32)(oid >> 32), step, stream, n);
+#endif
         }
         MHX_WAVE_SYNC();
     }
@@ -1531,8 +1552,8 @@ MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __
 #else
             if (__ballot(fm != 0ull))
 #endif
-                mhx_zig_fixup<L>(ks, zt, zn0, zq, zfm, 1, SLABD, lane, wave, a.first_chain, a.nchains, step, MHX_STREAM_PROPOSAL,
-                                 true, fm, ZADDC ? NBL - 1 : -1);
+                mhx_zig_fixup<L, MHX_ZIG_FIX2 != 0>(ks, zt, zn0, zq, zfm, 1, SLABD, lane, wave, a.first_chain, a.nchains, step,
+                                                    MHX_STREAM_PROPOSAL, true, fm, ZADDC ? NBL - 1 : -1);
             __syncthreads();                     // the slab holds the step's normals, final
         }
         if (a.nsteps > 0) __syncthreads();       // the second barrier of the last step
