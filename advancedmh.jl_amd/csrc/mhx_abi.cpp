@@ -341,3 +341,5 @@ extern "C" int mhx_emcee_exchange_unpack(mhx_run* r, int half, int rank, int wor
 {
     NEED_SAMPLER(emcee_exchange_unpack, r, half, rank, world, stage, stride);
 }
+
+#include "mhx_abi_pointwise.inc"

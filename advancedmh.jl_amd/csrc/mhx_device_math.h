@@ -104,6 +104,15 @@ MHX_NS_BEGIN
     MHX_DEV void mhx_user_predictive(const MHX_X& x, const MHX_G& rng, const MHX_Y& y, const int d,            \
                                      const mhx_real* __restrict__ data, const int ndata)
 
+// the log-likelihood of one data row under one saved draw in HIP source form (include/mhx.h, mhx_run_pointwise; DESIGN.md section
+// 6.5.7): returns log p(row | draw) as an mhx_real.  x is the draw exactly as MHX_DERIVED sees it (x[k] a lazy, clamped load of row
+// k, x[d] its lp); r[j] is entry j < m of the current data row (j is clamped to [0, m), the row is the same for every lane of a
+// wave); data / ndata the usual block for closed-over constants.  One text serves both widths and the host restatement.
+#define MHX_POINTWISE(x, r, m, d, data, ndata)                                                                 \
+    template <class MHX_X, class MHX_ROW>                                                                      \
+    MHX_DEV mhx_real mhx_user_pointwise(const MHX_X& x, const MHX_ROW& r, const int m, const int d,            \
+                                        const mhx_real* __restrict__ data, const int ndata)
+
 // wave-uniform base pointer + 32-bit per-lane BYTE offset: lowers to the scalar-base addressing mode
 // (global_load/store v_off, ..., s[base:base+1]) instead of a 64-bit vector address per access
 MHX_DEV mhx_real mhx_ld_off(const mhx_real* base, mhx_u32 byte_off)
@@ -207,6 +216,38 @@ MHX_DEV mhx_u32x4 mhx_philox(const mhx_philox_key& ks, mhx_u32 c0, mhx_u32 c1, m
     return o;
 }
 
+// exp in fp64, in BOTH widths: the fp64 engine's mhx_exp (below) and what the fp64 accumulators of an fp32 run exponentiate
+// (the pointwise log-likelihood sums, mhx_pointwise_kernels.h).  Literals, not the width's MHX_LN2_* macros.
+MHX_DEV double mhx_exp_f64(double x)
+{
+    if (x != x) return x;
+    if (x > 0x1.62e42fefa39efp+9) return __builtin_inf();
+    if (x < -0x1.74910d52d3052p+9) return 0.0;
+    const double n = __builtin_rint(x * 0x1.71547652b82fep+0);
+    double r = __builtin_fma(n, -0x1.62e42feep-1, x);
+    r = __builtin_fma(n, -0x1.a39ef35793c76p-33, r);
+    double p = 0x1.61bfaa228dde5p-33;
+    p = __builtin_fma(p, r, 0x1.1f7f2776cfaf2p-29);
+    p = __builtin_fma(p, r, 0x1.ae642c82e33d5p-26);
+    p = __builtin_fma(p, r, 0x1.27e4d41966f2fp-22);
+    p = __builtin_fma(p, r, 0x1.71de3a5aa7bb7p-19);
+    p = __builtin_fma(p, r, 0x1.a01a01a9e991bp-16);
+    p = __builtin_fma(p, r, 0x1.a01a01a0196acp-13);
+    p = __builtin_fma(p, r, 0x1.6c16c16c15a68p-10);
+    p = __builtin_fma(p, r, 0x1.1111111111111p-7);
+    p = __builtin_fma(p, r, 0x1.5555555555557p-5);
+    p = __builtin_fma(p, r, 0x1.5555555555555p-3);
+    p = __builtin_fma(p, r, 0.5);
+    const double r2 = r * r;
+    double y = __builtin_fma(r2, p, r) + 1.0;
+    const int ni = (int)n;
+    const int n1 = ni / 2;
+    const int n2 = ni - n1;
+    y = y * __builtin_bit_cast(double, (mhx_u64)(n1 + 1023) << 52);
+    y = y * __builtin_bit_cast(double, (mhx_u64)(n2 + 1023) << 52);
+    return y;
+}
+
 #if MHX_REAL64
 // ---------------------------------------------------------------------------------------------
 // fp64 arithmetic spec (coefficients: tools/fit_coeffs64.py; the CPU checker restates the same literals)
@@ -291,35 +332,7 @@ MHX_DEV double mhx_log_sel(const double x)
     return r;
 }
 
-MHX_DEV double mhx_exp(double x)
-{
-    if (x != x) return x;
-    if (x > 0x1.62e42fefa39efp+9) return MHX_INF;
-    if (x < -0x1.74910d52d3052p+9) return 0.0;
-    const double n = __builtin_rint(x * MHX_LOG2E);
-    double r = mhx_fma(n, -MHX_LN2_HI, x);
-    r = mhx_fma(n, -MHX_LN2_LO, r);
-    double p = 0x1.61bfaa228dde5p-33;
-    p = mhx_fma(p, r, 0x1.1f7f2776cfaf2p-29);
-    p = mhx_fma(p, r, 0x1.ae642c82e33d5p-26);
-    p = mhx_fma(p, r, 0x1.27e4d41966f2fp-22);
-    p = mhx_fma(p, r, 0x1.71de3a5aa7bb7p-19);
-    p = mhx_fma(p, r, 0x1.a01a01a9e991bp-16);
-    p = mhx_fma(p, r, 0x1.a01a01a0196acp-13);
-    p = mhx_fma(p, r, 0x1.6c16c16c15a68p-10);
-    p = mhx_fma(p, r, 0x1.1111111111111p-7);
-    p = mhx_fma(p, r, 0x1.5555555555557p-5);
-    p = mhx_fma(p, r, 0x1.5555555555555p-3);
-    p = mhx_fma(p, r, 0.5);
-    const double r2 = r * r;
-    double y = mhx_fma(r2, p, r) + 1.0;
-    const int ni = (int)n;
-    const int n1 = ni / 2;
-    const int n2 = ni - n1;
-    y = y * mhx_u2d((mhx_u64)(n1 + 1023) << 52);
-    y = y * mhx_u2d((mhx_u64)(n2 + 1023) << 52);
-    return y;
-}
+MHX_DEV double mhx_exp(double x) { return mhx_exp_f64(x); }
 
 MHX_DEV double mhx_sqrt(double x) { return __builtin_sqrt(x); }   // correctly rounded (default HIP lowering)
 MHX_DEV double mhx_abs(double x) { return __builtin_fabs(x); }

@@ -125,6 +125,11 @@ void mhx_jit_unlock();
     int api_ctx_predict(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,          \
                         int64_t first_chain, const char* source, int32_t nout, const REAL* data, size_t ndata,         \
                         uint64_t seed, mhx_run** out);                                                                 \
+    int api_run_pointwise(const mhx_run* src, const char* source, const REAL* rows, int64_t nrows, int32_t rowlen,     \
+                          const REAL* data, size_t ndata, int32_t shift_given, double* shift, double* out5, int64_t* T); \
+    int api_ctx_pointwise(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,        \
+                          const char* source, const REAL* rows, int64_t nrows, int32_t rowlen, const REAL* data,       \
+                          size_t ndata, int32_t shift_given, double* shift, double* out5, int64_t* T);                 \
     bool api_run_is_derived(const mhx_run* r);                                                                         \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \

@@ -7,6 +7,7 @@ from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposa
                   RobustAdaptiveMetropolis, Run, RWMH, StaticMH, StaticProposal, StructArray, combine_diagnostics, StretchProposal,
                   correlation_from_covariance, covariance_from_moments, hpd_ranks, Corner, density_binning_bound, density_from_counts, histogram_edges,
                   silverman_bandwidth, ACF_TILE, AutocorTable, autocorrelation, integrated_time, HipMap, HipPredictive, DerivedRun,
+                  HipPointwise, PointwiseSums, PointwiseTable, merge_pointwise, pointwise_table, waic_from_table, dic_from_table,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
                   logdensity, pack_lower, sample, unpack_lower, zeros)
 from . import trace

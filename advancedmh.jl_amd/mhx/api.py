@@ -473,6 +473,150 @@ class HipPredictive(HipMap):
     form of what mhx.trace.trace_predictive records."""
 
 
+class HipPointwise:
+    """The log-likelihood of one data row under one draw as HIP source (Run.pointwise):  MHX_POINTWISE(x, r, m, d, data, ndata) { return
+    ...; }  -- x the draw as HipMap's, r[j] entry j < m of the current data row -- with its `rows` ([nrows] or [nrows][rowlen]).  The
+    hand-written form of what mhx.trace.trace_pointwise records; it has no host evaluator (Chains.dic needs a traced function)."""
+
+    def __init__(self, source, rows, data=None):
+        self.source = source
+        self.rows = _pointwise_rows("HipPointwise", rows)
+        self.data = None if data is None else np.asarray(data, dtype=np.float64).ravel()
+
+
+def _pointwise_rows(who, rows):
+    arr = np.asarray(rows, dtype=np.float64)
+    if arr.ndim not in (1, 2) or arr.size == 0:
+        raise L.ArgumentError(L.MHX_EINVAL, "%s: rows must be a non-empty 1-D or 2-D array" % who)
+    return np.ascontiguousarray(arr.reshape(arr.shape[0], -1))
+
+
+def _pointwise_fn(who, fn, rows, dim, names, model_names):
+    """(the function of Run.pointwise / Group.pointwise -- traced where it is a callable --, its rows [nrows][rowlen] float64)"""
+    got = fn
+    if isinstance(fn, (HipPointwise, _trace.TracedPointwise)):
+        mat = fn.rows if rows is None else _pointwise_rows(who, rows)
+        if mat.shape[1] != fn.rows.shape[1]:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: rows of %d entries, the function was written for rows of %d" % (who, mat.shape[1], fn.rows.shape[1]))
+    elif callable(fn):
+        if rows is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: a callable needs the data rows" % who)
+        mat = _pointwise_rows(who, rows)
+        try:
+            fn = _trace.trace_pointwise(fn, dim, rows, names=names if names is not None else model_names)
+        except _trace.TraceError as e:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s: the callable cannot be traced: %s" % (who, e)) from e
+    else:
+        raise L.ArgumentError(L.MHX_EINVAL, "%s: a callable, a TracedPointwise or a HipPointwise is needed, got %r" % (who, got))
+    if isinstance(fn, _trace.TracedPointwise) and fn.dim != dim:
+        raise L.ArgumentError(L.MHX_EINVAL, "%s: the function was traced for %d parameters, the run has %d" % (who, fn.dim, dim))
+    return fn, mat
+
+
+class PointwiseSums(dict):
+    """what Run.pointwise / Group.pointwise return: dict(max, sumexp, s1, s2, bad, shift -- float64 [nrows] each -- and T), the raw
+    per-row reductions of include/mhx.h (mhx_run_pointwise).  They are sums on purpose: merge_pointwise adds the members of a group."""
+
+
+def merge_pointwise(a, b):
+    """The PointwiseSums of the union of two disjoint sets of draws taken about the SAME shift (include/mhx.h: mhx_run_pointwise): s1, s2,
+    bad and T add; max = max(a, b) and sumexp = sumexp_big + sumexp_small exp(max_small - max_big), on equal maxima (two -inf among them)
+    the sums add; a NaN max (a NaN or +inf l among the draws) or a NaN sumexp makes both NaN."""
+    if not np.array_equal(a["shift"], b["shift"]):
+        raise L.ArgumentError(L.MHX_EINVAL, "merge_pointwise: the two results were taken about different shifts")
+    am, bm, asum, bsum = (np.asarray(v, dtype=np.float64) for v in (a["max"], b["max"], a["sumexp"], b["sumexp"]))
+    with np.errstate(all="ignore"):
+        a_big = am > bm
+        big_m, small_m = np.where(a_big, am, bm), np.where(a_big, bm, am)
+        big_s, small_s = np.where(a_big, asum, bsum), np.where(a_big, bsum, asum)
+        equal = am == bm
+        scale = np.where(equal, 1.0, np.exp(np.where(equal, 0.0, small_m - big_m)))       # (never -inf - -inf: equal maxima add)
+        se = big_s + small_s * scale
+        mx = big_m.copy()
+    poisoned = np.isnan(am) | np.isnan(bm) | np.isnan(se)
+    mx[poisoned] = np.nan
+    se[poisoned] = np.nan
+    return PointwiseSums(max=mx, sumexp=se, s1=a["s1"] + b["s1"], s2=a["s2"] + b["s2"], bad=a["bad"] + b["bad"],
+                         shift=np.array(a["shift"], dtype=np.float64), T=int(a["T"]) + int(b["T"]))
+
+
+class PointwiseTable(dict):
+    """what Chains.pointwise returns and pointwise_table makes: dict(lppd, mean, var, p_waic, elpd, bad -- float64 [nrows] each -- and T)
+    that prints in the style of the HPD table (the first and last rows of a long one)"""
+
+    COLUMNS = ("lppd", "mean", "var", "p_waic", "elpd", "bad")
+
+    def __str__(self):
+        n = len(self["lppd"])
+        lines = ["Pointwise log-likelihood (%d rows, %d draws)" % (n, self["T"]), "  row     " + " ".join("%11s" % c for c in self.COLUMNS)]
+        show = range(n) if n <= 12 else list(range(6)) + [None] + list(range(n - 5, n))
+        for i in show:
+            lines.append("  ..." if i is None else "  %-7d " % i + " ".join("%11.4f" % self[c][i] for c in self.COLUMNS))
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
+def pointwise_table(sums):
+    """The per-row quantities of a PointwiseSums, in float64 on the host:
+        lppd    max + log(sumexp) - log(T): the log of the MEAN of p(y_i | theta_s) over ALL T draws.  T divides, not T - bad: a draw whose
+                l is -inf is a draw with p = 0 and stays in the divisor; a NaN or +inf l makes max NaN, and with it lppd, so no count of
+                such draws is needed
+        mean    shift + s1 / n, n = T - bad the draws that entered s1 and s2 (the finite l)
+        var     (s2 - s1^2 / n) / (n - 1), the sample variance of those l; NaN where n < 2
+        p_waic  var (the WAIC-2 penalty of the row);  elpd = lppd - p_waic;  bad as returned"""
+    T = int(sums["T"])
+    mx, se, s1, s2, bad, sh = (np.asarray(sums[k], dtype=np.float64) for k in ("max", "sumexp", "s1", "s2", "bad", "shift"))
+    with np.errstate(all="ignore"):
+        lppd = mx + np.log(se) - math.log(T)
+        n = T - bad
+        mean = np.where(n >= 1, sh + s1 / n, np.nan)
+        var = np.where(n >= 2, (s2 - s1 * s1 / n) / (n - 1.0), np.nan)
+        elpd = lppd - var
+    return PointwiseTable(lppd=lppd, mean=mean, var=var, p_waic=var.copy(), elpd=elpd, bad=bad.copy(), T=T)
+
+
+class WaicResult(dict):
+    """what Chains.waic returns: dict(elpd_waic, p_waic, waic, se, n_high_variance, pointwise) that prints"""
+
+    def __str__(self):
+        s = "WAIC %.4f (se %.4f)   elpd_waic %.4f   p_waic %.4f   rows %d" % (self["waic"], self["se"], self["elpd_waic"], self["p_waic"],
+                                                                              len(self["pointwise"]["lppd"]))
+        if self["n_high_variance"]:
+            s += "\n  %d rows with p_waic > 0.4: WAIC is unreliable there" % self["n_high_variance"]
+        return s
+
+    __repr__ = __str__
+
+
+def waic_from_table(table):
+    """elpd_waic = sum_i elpd_i, p_waic = sum_i p_waic_i, waic = -2 elpd_waic, se = 2 sqrt(nrows var_i(elpd_i)) (the sample variance over
+    the rows; NaN for one row), n_high_variance = the rows with p_waic > 0.4"""
+    elpd, p = table["elpd"], table["p_waic"]
+    n = len(elpd)
+    with np.errstate(all="ignore"):
+        se = 2.0 * math.sqrt(n * float(np.var(elpd, ddof=1))) if n > 1 else math.nan
+    return WaicResult(elpd_waic=float(np.sum(elpd)), p_waic=float(np.sum(p)), waic=-2.0 * float(np.sum(elpd)), se=se,
+                      n_high_variance=int(np.sum(p > 0.4)), pointwise=table)
+
+
+class DicResult(dict):
+    """what Chains.dic returns: dict(dic, p_d, d_bar, d_hat) that prints"""
+
+    def __str__(self):
+        return "DIC %.4f   p_D %.4f   mean deviance %.4f   deviance at the posterior mean %.4f" % (self["dic"], self["p_d"], self["d_bar"], self["d_hat"])
+
+    __repr__ = __str__
+
+
+def dic_from_table(table, fn, theta_bar, rows):
+    """D-bar = -2 sum_i mean_i; D(theta-bar) = -2 sum_i fn(theta-bar, row_i), on the host by the trace's evaluate; p_D = D-bar -
+    D(theta-bar); DIC = D-bar + p_D"""
+    d_bar = -2.0 * float(np.sum(table["mean"]))
+    d_hat = -2.0 * float(sum(fn.evaluate(theta_bar, r) for r in rows))
+    return DicResult(dic=2.0 * d_bar - d_hat, p_d=d_bar - d_hat, d_bar=d_bar, d_hat=d_hat)
+
+
 class DensityModel:
     """DensityModel(logdensity) -- src/AdvancedMH.jl:52-54.  `logdensity` is a catalogue log-density, HipLogDensity(source, dim),
     or a Python callable of the parameter vector together with `dim`: the callable is traced once (mhx/trace.py) and lowered
@@ -1353,6 +1497,38 @@ class Chains:
         value, _ = run.samples()
         return Chains(value, names + ["lp"], self.start, self.thin, accepted=self.accepted, stats=dict(self.stats), state=run)
 
+    def _pointwise_sums(self, who, fn, rows):
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "%s needs the live run (chain.state)" % who)
+        return self.state.pointwise(fn, rows, names=self.params())
+
+    def pointwise(self, fn, rows=None):
+        """The pointwise log-likelihood table of the chain: `chain.pointwise(lambda t, y: ..., data)` -- per data row lppd, mean, var,
+        p_waic, elpd and bad (pointwise_table has the formulas), from one pass over the run's sample buffer on the device
+        (Run.pointwise); the draws x rows matrix is never stored.  fn(theta, row) returns log p(row | theta): theta answers to the
+        parameter names, row is a number (1-D rows) or a vector (2-D).  Needs the live run."""
+        return pointwise_table(self._pointwise_sums("pointwise", fn, rows))
+
+    def waic(self, fn, rows=None):
+        """WAIC of the model whose per-row log-likelihood is fn (Turing's pointwise_loglikelihoods followed by WAIC; Watanabe's WAIC-2,
+        the variance form): dict(elpd_waic, p_waic, waic = -2 elpd_waic, se, n_high_variance, pointwise) -- waic_from_table.  Needs
+        the live run."""
+        return waic_from_table(self.pointwise(fn, rows))
+
+    def dic(self, fn, rows=None):
+        """DIC (MCMCChains' dic): D-bar = -2 sum_i mean_i from the same device pass as waic, D(theta-bar) on the host at the chain's
+        posterior means by the trace's evaluate, p_D = D-bar - D(theta-bar), DIC = D-bar + p_D.  fn must be a callable or a
+        TracedPointwise: a HipPointwise has no host evaluator.  Needs the live run."""
+        if isinstance(fn, HipPointwise):
+            raise L.ArgumentError(L.MHX_EINVAL, "dic: a HipPointwise has no host evaluator for D(theta-bar): pass a callable or a TracedPointwise")
+        sums = self._pointwise_sums("dic", fn, rows)
+        traced = sums.fn
+        theta_bar = np.array([self.mean(n) for n in self.params()], dtype=np.float64)
+        if traced.lp:
+            raise L.ArgumentError(L.MHX_EINVAL, "dic: a function that reads lp has no value at the posterior mean")
+        mat = traced.rows if rows is None else _pointwise_rows("dic", rows)
+        return dic_from_table(pointwise_table(sums), traced, theta_bar, mat)
+
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
         return "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
@@ -1927,6 +2103,32 @@ class Run:
         L.check(L.lib().mhx_run_predict(self.h, fn.source.encode(), fn.nout, L.rptr(data), 0 if data is None else data.size,
                                         seed & 0xffffffffffffffff, C.byref(h)))
         return DerivedRun(h, self, fn.nout)
+
+    def pointwise(self, fn, rows=None, shift=None, names=None):
+        """The pointwise log-likelihood l[i, s] = log p(rows[i] | saved draw s) reduced over all draws of all chains on the device
+        (mhx_run_pointwise): a PointwiseSums -- dict(max, sumexp, s1, s2, bad, shift [nrows] float64 each, T)
+        as include/mhx.h defines them; the T x nrows matrix is never stored.  fn: a Python callable fn(theta, row) that returns one
+        number -- traced once by mhx.trace.trace_pointwise, theta answering to the model's parameter names (or `names`), row a number
+        for 1-D rows and a vector for 2-D --, a TracedPointwise, or a HipPointwise(source, rows, data); `rows` may be left out where
+        fn carries its own.  shift: [nrows] to sum s1 and s2 about (None: the engine's, l of draw 0 of chain 0, returned).
+        pointwise_table(sums) turns the result into lppd, mean, var, p_waic and elpd per row."""
+        fn, mat = _pointwise_fn("pointwise", fn, rows, self.dim, names, getattr(getattr(self, "model", None), "param_names", None))
+        data = None if fn.data is None else self.ctx.arr(fn.data)
+        rr = self.ctx.arr(mat)
+        nrows, rowlen = rr.shape
+        if shift is None:
+            sh = np.zeros(nrows, dtype=np.float64)
+        else:
+            sh = np.array(shift, dtype=np.float64).reshape(-1)
+            if sh.size != nrows:
+                raise L.ArgumentError(L.MHX_EINVAL, "pointwise: %d shifts for %d rows" % (sh.size, nrows))
+        out, T = np.zeros((5, nrows), dtype=np.float64), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().mhx_run_pointwise(self.h, fn.source.encode(), L.rptr(rr), nrows, rowlen, L.rptr(data), 0 if data is None else data.size,
+                                          0 if shift is None else 1, sh.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(T)))
+        res = PointwiseSums(max=out[0], sumexp=out[1], s1=out[2], s2=out[3], bad=out[4], shift=sh, T=int(T.value))
+        res.fn = fn
+        return res
 
     def close(self):
         if self.h:

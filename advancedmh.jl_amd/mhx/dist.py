@@ -247,6 +247,18 @@ class Group:
         from .api import correlation_from_covariance
         return correlation_from_covariance(self.cov(params))
 
+    def pointwise(self, fn, rows=None, shift=None, names=None):
+        """Run.pointwise over the UNION of all members' draws: member 0 first (it fixes the shift where none is given), the other
+        members about member 0's shift, merged on the host in member order by merge_pointwise -- max and bad equal the unsharded
+        run's bit for bit, the sums to rounding."""
+        from .api import _pointwise_fn, merge_pointwise
+        fn, mat = _pointwise_fn("pointwise", fn, rows, self.dim, names, getattr(getattr(self.runs[0], "model", None), "param_names", None))
+        res = self.runs[0].pointwise(fn, mat, shift=shift)
+        for r in self.runs[1:]:
+            res = merge_pointwise(res, r.pointwise(fn, mat, shift=res["shift"]))
+        res.fn = fn
+        return res
+
     def close_runs(self):
         for r in self.runs:
             r.close()

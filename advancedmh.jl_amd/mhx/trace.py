@@ -31,7 +31,8 @@ import math
 import numpy as np
 
 __all__ = ["log", "exp", "sqrt", "abs", "fma", "where", "minimum", "maximum", "square", "sum_over", "trace", "Traced", "Sym", "Vec", "NamedVec", "TraceError",
-           "trace_proposal", "TracedProposal", "trace_map", "TracedMap", "draw", "trace_predictive", "TracedPredictive"]
+           "trace_proposal", "TracedProposal", "trace_map", "TracedMap", "draw", "trace_predictive", "TracedPredictive", "trace_pointwise",
+           "TracedPointwise"]
 
 
 class TraceError(TypeError):
@@ -1104,3 +1105,92 @@ def trace_predictive(fn, dim, names=None, lp=False):
     """trace_map for a function that may call `draw`: returns the recorded predictive map (a `TracedPredictive`).  An output that is
     itself a distribution is shorthand for draw(dist), so `lambda t: Normal(t.mu, t.sigma)` is a complete predictive map."""
     return _trace_map(fn, dim, names, lp, TracedPredictive)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pointwise log-likelihood (mhx_run_pointwise, DESIGN.md section 6.5.7): log p(row | draw) for every (saved draw, data row)
+
+
+class TracedPointwise(Traced):
+    """The recorded log-likelihood of one data row under one draw: `.source` (MHX_POINTWISE), `.dim`, `.rows` ([nrows][rowlen] float64,
+    what the call uploads), `.lp`, `.data` (None: a pointwise function is the body of a sum_over without the sum, and holds no loop
+    of its own), `.evaluate(x, row)` (the same program in numpy float64, for checks and for DIC's D(theta-bar))."""
+
+    def __init__(self, g, out, dim, rows, scalar_row, lp=False):
+        self.g, self.out, self.dim, self.lp = g, out, int(dim), bool(lp)
+        self.rows, self.scalar_row = rows, scalar_row
+        self._ld = {}
+        self.grad = None
+        self.data = None
+        lines, name = self._body([self.out])
+        self._nops -= sum(1 for i in self._reachable([self.out]) if g.nodes[i][0] == "lv")      # (a row entry is a load, as x[k] is)
+        src = ["// traced by mhx.trace (advancedmh.jl_amd/mhx/trace.py): the log-likelihood of a data row, %d operations in the source; "
+               "rows of %d reals" % (self._nops, rows.shape[1]),
+               "MHX_POINTWISE(x, r, m, d, data, ndata)", "{"] + lines + ["    return %s;" % name(self.out), "}"]
+        self.source = "\n".join(src) + "\n"
+
+    # the row entries are the `lv` leaves sum_over gives its body; here the frame, not an emitted loop, walks the rows: nothing is
+    # "inside a loop" for the emitter, and a row entry is read from r
+    def _loop_of(self, i):
+        return None
+
+    def _rhs(self, i, name):
+        key = self.g.nodes[i]
+        if key[0] == "lv":
+            return "r[%d]" % key[2]
+        return Traced._rhs(self, i, name)
+
+    def evaluate(self, x, row, lp=None):
+        x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+        if lp is not None:
+            x = np.concatenate([x[:self.dim], [float(lp)]])
+        if x.size < self.dim + (1 if self.lp else 0):
+            raise TraceError("evaluate: %d values for a function of %d parameters%s" % (x.size, self.dim, " and lp" if self.lp else ""))
+        row = np.atleast_1d(np.asarray(row, dtype=np.float64))
+        if row.size != self.rows.shape[1]:
+            raise TraceError("evaluate: a row of %d entries, the function was traced for rows of %d" % (row.size, self.rows.shape[1]))
+        val = {}
+        with np.errstate(all="ignore"):
+            for i in sorted(self._reachable([self.out])):
+                val[i] = np.float64(self._eval_node(i, val, x, row))
+        return float(val[self.out])
+
+
+def trace_pointwise(fn, dim, rows, names=None, lp=False):
+    """Run `fn(theta, row)` once -- theta the Vec (with `names`: the NamedVec) a log-density gets, row a traced number for 1-D `rows`
+    or a Vec of the row's entries for 2-D; with lp=True the call is fn(theta, row, lp) -- and return the recorded log-likelihood of a
+    row (a `TracedPointwise`).  fn returns ONE number.  `draw` and `sum_over` are refused inside it: the function is the body of a
+    sum_over without the sum, and the kernel's frame walks the rows."""
+    dim = int(dim)
+    if dim < 1:
+        raise TraceError("dim must be >= 1")
+    if names is not None and len(names) != dim:
+        raise TraceError("names: %d given for %d parameters" % (len(names), dim))
+    arr = np.asarray(rows, dtype=np.float64)
+    if arr.ndim not in (1, 2) or arr.size == 0:
+        raise TraceError("trace_pointwise: rows must be a non-empty 1-D or 2-D array")
+    mat = np.ascontiguousarray(arr.reshape(arr.shape[0], -1))
+    g = _Graph()
+    g.node("c", _const_key(0.0))        # node 0, as in trace
+    x = [Sym(g, g.node("x", k)) for k in range(dim)]
+    x = NamedVec(x, names) if names is not None else Vec(x)
+    lid = len(g.loops)
+    g.loops.append({"off": 0, "n": mat.shape[0], "m": mat.shape[1]})          # (the rows travel as the call's rows, not in the data block)
+    lv = [Sym(g, g.node("lv", lid, j)) for j in range(mat.shape[1])]
+    row = lv[0] if arr.ndim == 1 else Vec(lv)
+    _ACTIVE.append(g)
+    g.in_loop = lid                     # sum_over inside refuses, as inside a sum_over body
+    try:
+        out = fn(x, row, Sym(g, g.node("x", dim))) if lp else fn(x, row)
+    finally:
+        g.in_loop = None
+        _ACTIVE.pop()
+    if isinstance(out, Vec) and len(out) == 1:
+        out = out[0]
+    if isinstance(out, (int, float, np.integer, np.floating)) and not isinstance(out, (bool, np.bool_)):
+        out = Sym(g, g.node("c", _const_key(out)))
+    if not isinstance(out, Sym):
+        raise TraceError("a pointwise log-likelihood must return one number, got %r" % (type(out).__name__,))
+    if out.g is not g:
+        raise TraceError("the returned value belongs to another trace")
+    return TracedPointwise(g, out.i, dim, mat, arr.ndim == 1, lp)

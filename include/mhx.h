@@ -90,6 +90,7 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   default 1024; a positive number, fractions allowed; read at every call)
  *                   ACF_R (8 | 16 | 32 lags per tile of mhx_*_autocovariance; default: the fastest measured per width; read at every call)
  *                   DERIVE_DRAWS (1..16 draws a lane of mhx_*_derive / mhx_*_predict maps together; default 4 / 1; never more than the outputs leave registers for; read at every call)
+ *                   POINTWISE_ROWS (2 | 4 | 8 | 16 data rows per tile of mhx_*_pointwise, five fp64 accumulators each in registers; default: the fastest measured per width, 8 in fp64 and 4 in fp32; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
  * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
@@ -832,7 +833,7 @@ int mhx_ctx_autocovariance(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples
  * mhx_run_destroy, lives on the context of `src` (destroy it first), and may itself be a `src`.  On a derived run
  *   work      mhx_run_device_samples (accepted = NULL), mhx_run_get_samples (accepted must be NULL: MHX_EINVAL otherwise),
  *             mhx_run_stats (no transitions; kernel_ms = the map's launch, kernel_variant = -1), mhx_run_form_name ("derived"),
- *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_run_predict, mhx_group_attach, and every post-run statistic:
+ *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_run_predict, mhx_run_pointwise, mhx_group_attach, and every post-run statistic:
  *             mhx_run_diagnostics, _ess_bulk_tail, _rank_diagnostics, _rank_scores, _order_statistics, _select_histogram, _cross_moments,
  *             _hpd, _histogram, _histogram2d, _autocovariance
  *   refuse    with MHX_ESTATE and a message that says the run is derived, before anything else is looked at: mhx_run_init, _sample,
@@ -881,6 +882,44 @@ int mhx_run_predict(const mhx_run *src, const char *source, int32_t nout, const 
 int mhx_ctx_predict(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                     int64_t first_chain, const char *source, int32_t nout, const void *data, size_t ndata,
                     uint64_t seed, mhx_run **out);
+
+/* Pointwise log-likelihood: l[i, s] = log p(y_i | theta_s) of every data row i under every saved draw s of `src`, reduced over the draws
+ * on the device -- what Turing's pointwise_loglikelihoods gives WAIC / lppd and MCMCChains' dic; the matrix
+ * itself (T x nrows) is never stored.  `source` is HIP source of the form
+ *     MHX_POINTWISE(x, r, m, d, data, ndata) { const mhx_real z = (r[0] - x[0]) / x[1]; return MHX_R(-0.5) * z * z; }
+ * x is the draw exactly as MHX_DERIVED sees it (x[k] a lazy load of row k clamped to [0, d], x[d] the lp); r[j] is entry j < m = rowlen
+ * of the current data row (j clamped to [0, m)); data / ndata as for mhx_run_derive, and so are mhx_log, mhx_exp and the other
+ * operations of the engine; the function returns an mhx_real.
+ * Definitions.
+ *   T = n_saved x nchains     the pooled saved draws of the source (a run, a derived run, or a caller's tensor); written to *T
+ *   rows                      nrows >= 1 data rows of rowlen >= 1 reals of the context's dtype, on the host, copied by the call
+ *   l[i, s]                   the function of draw s and row i, evaluated in the run's width with the engine's operations, then
+ *                             widened to fp64.  Every accumulator below is fp64 in both widths; exp is the engine's fp64 exp.
+ * out5 receives five fp64 arrays of nrows, one after the other:
+ *   max[i]      max_s l[i, s]: one of the l values, bit for bit (no rounding); -inf if every l is -inf
+ *   sumexp[i]   sum_s exp(l[i, s] - max[i]), so that log sum_s exp l = max + log(sumexp)
+ *   s1[i]       sum_s (l[i, s] - shift[i])       over the draws whose l is finite
+ *   s2[i]       sum_s (l[i, s] - shift[i])^2     over the same draws
+ *   bad[i]      as a double: the number of draws whose l is NaN, +inf or -inf
+ * A -inf l adds 0 to sumexp, is counted in bad and left out of s1 and s2 (it never meets a -inf running maximum in a subtraction).  A
+ * NaN or +inf l is counted in bad, left out of s1 and s2, and makes max[i] and sumexp[i] NaN.  No other row is affected.
+ * shift is in/out, double[nrows]: with shift_given != 0 the caller supplies it; otherwise the engine sets shift[i] = l[i, draw 0 of
+ * chain 0] (0 where that is not finite) and returns it.  The sums are raw on purpose, so that members of a group add: s1, s2 and bad
+ * add under a common shift; (max, sumexp) merge as max = max(a, b), sumexp = sumexp_big + sumexp_small exp(max_small - max_big), and
+ * on equal maxima the sums add.
+ * The order of every operation is a function of the shape (n_saved, nchains, nrows) and option POINTWISE_ROWS alone -- no atomics;
+ * per-block partials go to scratch and are merged in index order -- so two calls on the same tensor give the same bits.
+ * Compiled at run time through the context's module table, keyed by source and defines: a second call with the same source compiles
+ * nothing.  MHX_ESTATE: `src` holds no device sample tensor; MHX_EINVAL: a NULL argument, nrows < 1, rowlen < 1, nrows x rowlen,
+ * n_saved or nchains >= 2^31, more than 65535 tiles of rows, and a source that does not compile (the compiler's diagnostic, which
+ * names the text pointwise.hip, is in mhx_last_error).  Rows and data are not checked for finiteness, as for mhx_run_derive.  A
+ * refusal writes nothing to shift, out5 or T.  Works on a derived run.  Blocking. */
+int mhx_run_pointwise(const mhx_run *src, const char *source, const void *rows, int64_t nrows, int32_t rowlen,
+                      const void *data, size_t ndata, int32_t shift_given, double *shift, double *out5, int64_t *T);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_derive): d = dim1 - 1 */
+int mhx_ctx_pointwise(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
+                      const char *source, const void *rows, int64_t nrows, int32_t rowlen, const void *data,
+                      size_t ndata, int32_t shift_given, double *shift, double *out5, int64_t *T);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
