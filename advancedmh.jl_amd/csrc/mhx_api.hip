@@ -41,6 +41,7 @@
 #include "mhx_acf_kernels.h"
 #include "mhx_derive_kernels.h"     // (its constants: the frame itself is compiled at run time only)
 #include "mhx_pointwise_kernels.h"  // (likewise)
+#include "mhx_psis_kernels.h"       // (likewise)
 #ifdef MHX_TOOLS_BUILD
 #include "mhx_jit_embed_tools.inc"   // generated: the device headers as string literals for hiprtc, probes included
 #else
@@ -256,8 +257,8 @@ struct mhx_ctx : mhx_handle_hdr {
     size_t select_landing_words = 0;
     void* cross_scratch = nullptr;                  // the cross moments alone: partial tiles, tables and results
     size_t cross_bytes = 0;
-    void* hpd_scratch = nullptr;                    // HPD alone, held across its select passes: tail keys, their sort, the partial minima
-    size_t hpd_bytes = 0;                           // (bounded by HPD_SCRATCH_MB)
+    void* hpd_scratch = nullptr;                    // the tails of HPD or of PSIS-LOO, held across the call's select passes: tail keys,
+    size_t hpd_bytes = 0;                           // their sort, what follows it (bounded by HPD_SCRATCH_MB / PSIS_SCRATCH_MB)
     ~mhx_ctx()
     {
         if (hpd_scratch) (void)hipFree(hpd_scratch);
@@ -316,10 +317,10 @@ static const opt_name k_opt_names[] = {
     {"EMCEE_MFMA", 0}, {"EMCEE_MFMA_WAVES", 0}, {"EMCEE_SCALAR", 0}, {"EMCEE_SCAL_MODE", 0}, {"EMCEE_SCAL_WPB", 0}, {"EMCEE_SCAL_REC", 0},
     {"EMCEE_FUSED", 0}, {"EMCEE_PERSIST", 0}, {"EMCEE_PRELOAD", 0}, {"EMCEE_DEFER", 0}, {"EMCEE_SWEEP_DEFER", 0}, {"EMCEE_WAVES", 0},
     {"EMCEE_REC_STORE", 0}, {"EMCEE_ROW_STORE", 0}, {"EMCEE_COOP_REC", 0},
-    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0}, {"HPD_SCRATCH_MB", 0}, {"ACF_R", 0}, {"DERIVE_DRAWS", 0}, {"POINTWISE_ROWS", 0},
+    {"HOST_COMPACT", 0}, {"HOST_THREADS", 0}, {"HOST_CHUNK", 0}, {"HOST_NUMA", 0}, {"TOTAL_CHAINS", 0}, {"JIT_COMPILER", 0}, {"SELECT_BITS", 0}, {"HPD_SCRATCH_MB", 0}, {"ACF_R", 0}, {"DERIVE_DRAWS", 0}, {"POINTWISE_ROWS", 0}, {"PSIS_SCRATCH_MB", 0}, {"PSIS_ROWS", 0},
 #ifdef MHX_TOOLS_BUILD
     {"ZIG_PROBE", 1}, {"ZIG_FORCE_FAIL", 1}, {"JIT_DEFS", 1}, {"JIT_FLAGS", 1}, {"EMCEE_PROBE", 1}, {"EMCEE_STAMPS", 1}, {"EMCEE_STAMPS_FILE", 1},
-    {"FAULT_SLAB", 1}, {"RAM_PROF", 1}, {"HPD_STOP_AFTER", 1},
+    {"FAULT_SLAB", 1}, {"RAM_PROF", 1}, {"HPD_STOP_AFTER", 1}, {"PSIS_STOP_AFTER", 1},
 #endif
 };
 static const opt_name* opt_find(const char* name)
@@ -507,12 +508,12 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
                              k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
                              k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h, k_src_mhx_derive_kernels_h,
-                             k_src_mhx_pointwise_kernels_h};
+                             k_src_mhx_pointwise_kernels_h, k_src_mhx_psis_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
                               "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h", "mhx_derive_kernels.h",
-                              "mhx_pointwise_kernels.h"};
+                              "mhx_pointwise_kernels.h", "mhx_psis_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -2224,5 +2225,6 @@ struct dev_array {
 #include "mhx_api_acf.inc"
 #include "mhx_api_derive.inc"
 #include "mhx_api_pointwise.inc"
+#include "mhx_api_psis.inc"
 
 }  // namespace MHX_NS

@@ -248,6 +248,64 @@ MHX_DEV double mhx_exp_f64(double x)
     return y;
 }
 
+// log in fp64, in BOTH widths, as mhx_exp_f64 above: the fp64 engine's mhx_log (below) and what the fp64 stages of an fp32 run take
+// logarithms with (the Pareto fit of mhx_psis_kernels.h).  Literals, not the width's MHX_LN2_* macros.
+// a / b for normal operands with |b| < 2^1022 (1 / b is normal) and |a| >= 2^-968 (the residual a - b q, a multiple of
+// ulp(b) ulp(q), is exact) whose quotient is normal, or a == +0: the correctly rounded sequence hipcc emits for an fp64 division
+// -- reciprocal estimate, two Newton steps, quotient, residual, final fma -- without its range scaling (v_div_scale x 2) and
+// special-case fix-up (v_div_fixup), which are the identity in that range: 8 instead of 11 instructions.  Outside it the result
+// can be one ulp off (|a| < 2^-969, |b| >= 2^1023) and a == -0 gives +0.  The one caller, mhx_log_core_f64, sends b in [1.7, 2.42]
+// and a == +0 or 2^-53 <= |a| < 0.42.  Verified bit for bit on near-midpoint quotients across that domain and on the caller's
+// ranges: tests/test_gpu_primitives.py (test_div_normal_is_correctly_rounded, test_log_core_division_is_correctly_rounded)
+MHX_DEV double mhx_div_normal_f64(const double a, const double b)
+{
+    double y = __builtin_amdgcn_rcp(b);
+    double e = __builtin_fma(-b, y, 1.0);
+    y = __builtin_fma(y, e, y);
+    e = __builtin_fma(-b, y, 1.0);
+    y = __builtin_fma(y, e, y);
+    const double q = a * y;
+    const double r = __builtin_fma(-b, q, a);
+    return __builtin_fma(r, y, q);
+}
+
+// m in [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), z = s^2:
+//   log(1 + f) = 2 s + s z P(z) = f - hfsq + s (hfsq + z P(z)),  hfsq = f^2 / 2       (one correctly rounded division)
+MHX_DEV double mhx_log_core_f64(mhx_u64 ix, const int eadj)
+{
+    const mhx_u64 t = ix - 0x3fe6a09e667f3bcdull;
+    const long long e = (long long)t >> 52;
+    const double m = __builtin_bit_cast(double, ix - ((mhx_u64)e << 52));
+    const double f = m - 1.0;
+    const double s = mhx_div_normal_f64(f, 2.0 + f);       // 2 + f in [1.7, 2.42]; f == 0 or |f| >= 2^-53
+    const double z = s * s;
+    double p = 0x1.2b59b70eb76c6p-3;
+    p = __builtin_fma(p, z, 0x1.39fe42e9d4a8ap-3);
+    p = __builtin_fma(p, z, 0x1.7462b58e4403ap-3);
+    p = __builtin_fma(p, z, 0x1.c71c62e26212ep-3);
+    p = __builtin_fma(p, z, 0x1.2492492df3ba9p-2);
+    p = __builtin_fma(p, z, 0x1.99999999952ccp-2);
+    p = __builtin_fma(p, z, 0x1.5555555555558p-1);
+    const double hfsq = (0.5 * f) * f;
+    const double ef = (double)((int)e + eadj);
+    const double t1 = s * __builtin_fma(z, p, hfsq);
+    const double t2 = __builtin_fma(ef, 0x1.a39ef35793c76p-33, t1);
+    const double t3 = hfsq - t2;
+    const double t4 = f - t3;
+    return __builtin_fma(ef, 0x1.62e42feep-1, t4);
+}
+// full-range log
+MHX_DEV double mhx_log_f64(double x)
+{
+    mhx_u64 ix = __builtin_bit_cast(mhx_u64, x);
+    if ((ix << 1) == 0ull) return -__builtin_inf();
+    if (ix >> 63) return __builtin_nan("");
+    if (ix >= 0x7ff0000000000000ull) return x;
+    int eadj = 0;
+    if (ix < 0x0010000000000000ull) { x = x * 0x1p54; ix = __builtin_bit_cast(mhx_u64, x); eadj = -54; }
+    return mhx_log_core_f64(ix, eadj);
+}
+
 #if MHX_REAL64
 // ---------------------------------------------------------------------------------------------
 // fp64 arithmetic spec (coefficients: tools/fit_coeffs64.py; the CPU checker restates the same literals)
@@ -261,63 +319,13 @@ MHX_DEV double  mhx_fma(double a, double b, double c) { return __builtin_fma(a, 
 #define MHX_INF    __builtin_inf()
 #define MHX_NAN    __builtin_nan("")
 
-// a / b for normal operands with |b| < 2^1022 (1 / b is normal) and |a| >= 2^-968 (the residual a - b q, a multiple of
-// ulp(b) ulp(q), is exact) whose quotient is normal, or a == +0: the correctly rounded sequence hipcc emits for an fp64 division
-// -- reciprocal estimate, two Newton steps, quotient, residual, final fma -- without its range scaling (v_div_scale x 2) and
-// special-case fix-up (v_div_fixup), which are the identity in that range: 8 instead of 11 instructions.  Outside it the result
-// can be one ulp off (|a| < 2^-969, |b| >= 2^1023) and a == -0 gives +0.  The one caller, mhx_log_core, sends b in [1.7, 2.42]
-// and a == +0 or 2^-53 <= |a| < 0.42.  Verified bit for bit on near-midpoint quotients across that domain and on the caller's
-// ranges: tests/test_gpu_primitives.py (test_div_normal_is_correctly_rounded, test_log_core_division_is_correctly_rounded)
-MHX_DEV double mhx_div_normal(const double a, const double b)
-{
-    double y = __builtin_amdgcn_rcp(b);
-    double e = mhx_fma(-b, y, 1.0);
-    y = mhx_fma(y, e, y);
-    e = mhx_fma(-b, y, 1.0);
-    y = mhx_fma(y, e, y);
-    const double q = a * y;
-    const double r = mhx_fma(-b, q, a);
-    return mhx_fma(r, y, q);
-}
-
-// m in [sqrt(1/2), sqrt(2)), f = m - 1, s = f / (2 + f), z = s^2:
-//   log(1 + f) = 2 s + s z P(z) = f - hfsq + s (hfsq + z P(z)),  hfsq = f^2 / 2       (one correctly rounded division)
-MHX_DEV double mhx_log_core(mhx_u64 ix, const int eadj)
-{
-    const mhx_u64 t = ix - 0x3fe6a09e667f3bcdull;
-    const long long e = (long long)t >> 52;
-    const double m = mhx_u2d(ix - ((mhx_u64)e << 52));
-    const double f = m - 1.0;
-    const double s = mhx_div_normal(f, 2.0 + f);       // 2 + f in [1.7, 2.42]; f == 0 or |f| >= 2^-53
-    const double z = s * s;
-    double p = 0x1.2b59b70eb76c6p-3;
-    p = mhx_fma(p, z, 0x1.39fe42e9d4a8ap-3);
-    p = mhx_fma(p, z, 0x1.7462b58e4403ap-3);
-    p = mhx_fma(p, z, 0x1.c71c62e26212ep-3);
-    p = mhx_fma(p, z, 0x1.2492492df3ba9p-2);
-    p = mhx_fma(p, z, 0x1.99999999952ccp-2);
-    p = mhx_fma(p, z, 0x1.5555555555558p-1);
-    const double hfsq = (0.5 * f) * f;
-    const double ef = (double)((int)e + eadj);
-    const double t1 = s * mhx_fma(z, p, hfsq);
-    const double t2 = mhx_fma(ef, MHX_LN2_LO, t1);
-    const double t3 = hfsq - t2;
-    const double t4 = f - t3;
-    return mhx_fma(ef, MHX_LN2_HI, t4);
-}
+// division, log core and log of the fp64 spec: the width-independent functions above (same literals, same operations)
+MHX_DEV double mhx_div_normal(const double a, const double b) { return mhx_div_normal_f64(a, b); }
+MHX_DEV double mhx_log_core(mhx_u64 ix, const int eadj) { return mhx_log_core_f64(ix, eadj); }
 // log for a positive, normal, finite argument (every uniform we draw): no special cases
 MHX_DEV double mhx_log_pos(double x) { return mhx_log_core(mhx_d2u(x), 0); }
 // full-range log (user log-densities, emcee's log z)
-MHX_DEV double mhx_log(double x)
-{
-    mhx_u64 ix = mhx_d2u(x);
-    if ((ix << 1) == 0ull) return -MHX_INF;
-    if (ix >> 63) return MHX_NAN;
-    if (ix >= 0x7ff0000000000000ull) return x;
-    int eadj = 0;
-    if (ix < 0x0010000000000000ull) { x = x * 0x1p54; ix = mhx_d2u(x); eadj = -54; }
-    return mhx_log_core(ix, eadj);
-}
+MHX_DEV double mhx_log(double x) { return mhx_log_f64(x); }
 // the same function without a branch -- special cases by selects AFTER the arithmetic ran on (possibly meaningless) bits -- for kernels
 // that evaluate several logarithms side by side (mhx_rwmh_wave_body): early returns would serialise them.  Same value for every input.
 MHX_DEV double mhx_log_sel(const double x)

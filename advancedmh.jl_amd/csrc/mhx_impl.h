@@ -130,6 +130,12 @@ void mhx_jit_unlock();
     int api_ctx_pointwise(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,        \
                           const char* source, const REAL* rows, int64_t nrows, int32_t rowlen, const REAL* data,       \
                           size_t ndata, int32_t shift_given, double* shift, double* out5, int64_t* T);                 \
+    int api_run_psis(const mhx_run* src, const char* source, const REAL* rows, int64_t nrows, int32_t rowlen,          \
+                     const REAL* data, size_t ndata, double reff, double* out8, double* tail_out, int64_t* T,          \
+                     int64_t* M);                                                                                      \
+    int api_ctx_psis(mhx_ctx* ctx, const REAL* d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,             \
+                     const char* source, const REAL* rows, int64_t nrows, int32_t rowlen, const REAL* data,            \
+                     size_t ndata, double reff, double* out8, double* tail_out, int64_t* T, int64_t* M);               \
     bool api_run_is_derived(const mhx_run* r);                                                                         \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \

@@ -8,6 +8,7 @@ from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposa
                   correlation_from_covariance, covariance_from_moments, hpd_ranks, Corner, density_binning_bound, density_from_counts, histogram_edges,
                   silverman_bandwidth, ACF_TILE, AutocorTable, autocorrelation, integrated_time, HipMap, HipPredictive, DerivedRun,
                   HipPointwise, PointwiseSums, PointwiseTable, merge_pointwise, pointwise_table, waic_from_table, dic_from_table,
+                  PsisResult, LooTable, LooResult, CompareTable, loo_table, loo_from_table, compare, psis_tail_length, khat_threshold,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
                   logdensity, pack_lower, sample, unpack_lower, zeros)
 from . import trace

@@ -134,6 +134,7 @@ EXPORTS = [
     "mhx_run_histogram", "mhx_ctx_histogram", "mhx_group_histogram", "mhx_run_histogram2d", "mhx_ctx_histogram2d", "mhx_group_histogram2d",
     "mhx_run_autocovariance", "mhx_ctx_autocovariance", "mhx_group_autocovariance",
     "mhx_run_derive", "mhx_ctx_derive", "mhx_run_predict", "mhx_ctx_predict", "mhx_run_pointwise", "mhx_ctx_pointwise",
+    "mhx_run_psis", "mhx_ctx_psis",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -295,6 +296,9 @@ def lib():
         L.mhx_run_pointwise.argtypes = [vp, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_int32, dp, dp, i64p]
         L.mhx_ctx_pointwise.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_int32,
                                         dp, dp, i64p]
+        L.mhx_run_psis.argtypes = [vp, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_double, dp, dp, i64p, i64p]
+        L.mhx_ctx_psis.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_double,
+                                   dp, dp, i64p, i64p]
         _lib = _loaded[_lib_path] = L
     return _lib
 

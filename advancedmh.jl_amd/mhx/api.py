@@ -617,6 +617,116 @@ def dic_from_table(table, fn, theta_bar, rows):
     return DicResult(dic=2.0 * d_bar - d_hat, p_d=d_bar - d_hat, d_bar=d_bar, d_hat=d_hat)
 
 
+class PsisResult(dict):
+    """what Run.psis returns: dict(elpd_loo, khat, sigma, tau, lmin, body, n_below, bad -- float64 [nrows] each --, T, M, reff and, with
+    tails=True, tails [nrows][M]) as include/mhx.h defines them (mhx_run_psis)"""
+
+
+def psis_tail_length(T, reff=1.0):
+    """M = min(floor(0.2 T), ceil(3 sqrt(T / reff))) in float64, as the engine computes it; M < 5 counts as 0 (no smoothing)"""
+    m = min(math.floor(0.2 * float(T)), math.ceil(3.0 * math.sqrt(float(T) / float(reff))))
+    return 0 if m < 5 else int(m)
+
+
+class LooTable(dict):
+    """what loo_table makes: dict(elpd_loo, p_loo, khat, lppd, bad -- float64 [nrows] each --, T, M) that prints as PointwiseTable does"""
+
+    COLUMNS = ("elpd_loo", "p_loo", "khat", "lppd", "bad")
+
+    def __str__(self):
+        n = len(self["elpd_loo"])
+        lines = ["PSIS-LOO (%d rows, %d draws, tails of %d)" % (n, self["T"], self["M"]), "  row     " + " ".join("%11s" % c for c in self.COLUMNS)]
+        show = range(n) if n <= 12 else list(range(6)) + [None] + list(range(n - 5, n))
+        for i in show:
+            lines.append("  ..." if i is None else "  %-7d " % i + " ".join("%11.4f" % self[c][i] for c in self.COLUMNS))
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
+def loo_table(psis, sums):
+    """Per row, in float64 on the host: elpd_loo and khat of a PsisResult, lppd of a PointwiseSums of the SAME draws and rows (as
+    pointwise_table forms it), p_loo = lppd - elpd_loo; bad as the PsisResult counts it"""
+    if int(psis["T"]) != int(sums["T"]) or len(psis["elpd_loo"]) != len(sums["max"]):
+        raise L.ArgumentError(L.MHX_EINVAL, "loo_table: the two results are not of the same draws and rows")
+    lppd = pointwise_table(sums)["lppd"]
+    elpd = np.array(psis["elpd_loo"], dtype=np.float64)
+    with np.errstate(all="ignore"):
+        p = lppd - elpd
+    return LooTable(elpd_loo=elpd, p_loo=p, khat=np.array(psis["khat"], dtype=np.float64), lppd=lppd,
+                    bad=np.array(psis["bad"], dtype=np.float64), T=int(psis["T"]), M=int(psis["M"]))
+
+
+KHAT_EDGES = (0.5, 0.7, 1.0)            # the classes of the printout: (-inf, 0.5], (0.5, 0.7], (0.7, 1], (1, inf)
+
+
+def khat_threshold(T):
+    """min(1 - 1 / log10(T), 0.7): the khat up to which T draws give a reliable estimate (Vehtari et al. 2024)"""
+    return min(1.0 - 1.0 / math.log10(T), 0.7) if T > 1 else -math.inf
+
+
+class LooResult(dict):
+    """what Chains.loo returns: dict(elpd_loo, p_loo, looic, se, khat_counts, khat_threshold, pointwise) that prints"""
+
+    def __str__(self):
+        c = self["khat_counts"]
+        return ("PSIS-LOO   elpd_loo %.4f (se %.4f)   p_loo %.4f   looic %.4f   rows %d\n"
+                "  khat (-inf, 0.5]: %d   (0.5, 0.7]: %d   (0.7, 1]: %d   (1, inf): %d   sample-size threshold %.3f" % (
+                    self["elpd_loo"], self["se"], self["p_loo"], self["looic"], len(self["pointwise"]["elpd_loo"]), c[0], c[1], c[2], c[3],
+                    self["khat_threshold"]))
+
+    __repr__ = __str__
+
+
+def loo_from_table(table):
+    """elpd_loo = sum_i elpd_loo_i, p_loo = sum_i p_loo_i, looic = -2 elpd_loo, se = 2 sqrt(nrows var_i(elpd_loo_i)) as waic_from_table
+    forms it, khat_counts = the rows per class of KHAT_EDGES (a NaN khat is in none), khat_threshold = khat_threshold(T)"""
+    elpd, k = table["elpd_loo"], table["khat"]
+    n = len(elpd)
+    with np.errstate(all="ignore"):
+        se = 2.0 * math.sqrt(n * float(np.var(elpd, ddof=1))) if n > 1 else math.nan
+        counts = [int(np.sum(k <= 0.5)), int(np.sum((k > 0.5) & (k <= 0.7))), int(np.sum((k > 0.7) & (k <= 1.0))), int(np.sum(k > 1.0))]
+    return LooResult(elpd_loo=float(np.sum(elpd)), p_loo=float(np.sum(table["p_loo"])), looic=-2.0 * float(np.sum(elpd)), se=se,
+                     khat_counts=counts, khat_threshold=khat_threshold(table["T"]), pointwise=table)
+
+
+class CompareTable(list):
+    """what compare returns: a list of dict(name, elpd, elpd_diff, se_diff), best first, that prints"""
+
+    def __str__(self):
+        lines = ["  %-16s %12s %12s %12s" % ("model", "elpd", "elpd_diff", "se_diff")]
+        lines += ["  %-16s %12.4f %12.4f %12.4f" % (r["name"], r["elpd"], r["elpd_diff"], r["se_diff"]) for r in self]
+        return "\n".join(lines)
+
+    __repr__ = __str__
+
+
+def compare(results):
+    """Model comparison on the host, as loo_compare: `results` maps a name to a LooResult or a WaicResult (or a LooTable / PointwiseTable)
+    over the SAME data rows.  Best (largest total elpd) first; elpd_diff = sum_i (elpd_i - elpd_i^best) and se_diff =
+    sqrt(n var_i(elpd_i - elpd_i^best)) (the sample variance over the rows), both 0 for the best model."""
+    rows = {}
+    for name, r in results.items():
+        t = r["pointwise"] if "pointwise" in r else r
+        e = np.asarray(t["elpd_loo"] if "elpd_loo" in t else t["elpd"], dtype=np.float64)
+        rows[str(name)] = e
+    if not rows:
+        raise L.ArgumentError(L.MHX_EINVAL, "compare: no models")
+    n = {len(e) for e in rows.values()}
+    if len(n) != 1:
+        raise L.ArgumentError(L.MHX_EINVAL, "compare: the models are not over the same number of data rows")
+    n = n.pop()
+    order = sorted(rows, key=lambda k: -float(np.sum(rows[k])))
+    best = rows[order[0]]
+    out = CompareTable()
+    for name in order:
+        diff = rows[name] - best
+        with np.errstate(all="ignore"):
+            se = math.sqrt(n * float(np.var(diff, ddof=1))) if n > 1 else math.nan
+        out.append(dict(name=name, elpd=float(np.sum(rows[name])), elpd_diff=float(np.sum(diff)), se_diff=0.0 if name == order[0] else se))
+    return out
+
+
 class DensityModel:
     """DensityModel(logdensity) -- src/AdvancedMH.jl:52-54.  `logdensity` is a catalogue log-density, HipLogDensity(source, dim),
     or a Python callable of the parameter vector together with `dim`: the callable is traced once (mhx/trace.py) and lowered
@@ -1529,6 +1639,16 @@ class Chains:
         mat = traced.rows if rows is None else _pointwise_rows("dic", rows)
         return dic_from_table(pointwise_table(sums), traced, theta_bar, mat)
 
+    def loo(self, fn, rows=None, reff=1.0):
+        """PSIS-LOO of the model whose per-row log-likelihood is fn (what ArviZ / R loo compute from Turing's
+        pointwise_loglikelihoods): `chain.loo(lambda t, y: ..., data)` -- dict(elpd_loo, p_loo, looic = -2 elpd_loo, se, khat_counts,
+        khat_threshold, pointwise) that prints, loo_from_table of loo_table of Run.psis and Run.pointwise.  reff: the relative
+        efficiency of the draws the tail length is computed with (1: as if independent).  Needs the live run."""
+        if self.state is None:
+            raise L.ArgumentError(L.MHX_EINVAL, "loo needs the live run (chain.state)")
+        sums = self.state.pointwise(fn, rows, names=self.params())
+        return loo_from_table(loo_table(self.state.psis(sums.fn, rows, reff=reff), sums))
+
     def _header(self):
         """the first line of the printout: shape, element type and iteration range, as MCMCChains words it"""
         return "Chains MCMC chain (%dx%dx%d Array{%s, 3}), iterations %d:%d:%d" % (
@@ -2127,6 +2247,33 @@ class Run:
         L.check(L.lib().mhx_run_pointwise(self.h, fn.source.encode(), L.rptr(rr), nrows, rowlen, L.rptr(data), 0 if data is None else data.size,
                                           0 if shift is None else 1, sh.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(T)))
         res = PointwiseSums(max=out[0], sumexp=out[1], s1=out[2], s2=out[3], bad=out[4], shift=sh, T=int(T.value))
+        res.fn = fn
+        return res
+
+    def psis(self, fn, rows=None, reff=1.0, names=None, tails=False):
+        """PSIS-LOO per data row on the device (mhx_run_psis): a PsisResult -- dict(elpd_loo, khat, sigma, tau,
+        lmin, body, n_below, bad [nrows] float64 each, T, M, reff; tails [nrows][M] with tails=True) as include/mhx.h defines them.  fn and
+        rows as Run.pointwise takes them.  loo_table(psis, sums) adds p_loo from a PointwiseSums."""
+        fn, mat = _pointwise_fn("psis", fn, rows, self.dim, names, getattr(getattr(self, "model", None), "param_names", None))
+        data = None if fn.data is None else self.ctx.arr(fn.data)
+        rr = self.ctx.arr(mat)
+        nrows, rowlen = rr.shape
+        reff = float(reff)
+        out, T, M = np.zeros((8, nrows), dtype=np.float64), C.c_int64(), C.c_int64()
+        tl = None
+        if tails:                               # [nrows][M]: M from the saved draws, as the engine computes it
+            n_saved = C.c_int64()
+            L.check(L.lib().mhx_run_device_samples(self.h, None, None, C.byref(n_saved)))
+            ok = reff > 0 and math.isfinite(reff)
+            tl = np.zeros((nrows, psis_tail_length(int(n_saved.value) * self.n, reff) if ok else 0), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().mhx_run_psis(self.h, fn.source.encode(), L.rptr(rr), nrows, rowlen, L.rptr(data), 0 if data is None else data.size,
+                                     reff, out.ctypes.data_as(dp), None if tl is None else tl.ctypes.data_as(dp), C.byref(T), C.byref(M)))
+        res = PsisResult(elpd_loo=out[0], khat=out[1], sigma=out[2], tau=out[3], lmin=out[4], body=out[5], n_below=out[6], bad=out[7],
+                         T=int(T.value), M=int(M.value), reff=reff)
+        if tails:
+            assert tl.shape[1] == res["M"]
+            res["tails"] = tl
         res.fn = fn
         return res
 

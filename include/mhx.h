@@ -91,8 +91,10 @@ int mhx_ctx_pci_bus_id(const mhx_ctx *ctx, char *buf, size_t len);
  *                   ACF_R (8 | 16 | 32 lags per tile of mhx_*_autocovariance; default: the fastest measured per width; read at every call)
  *                   DERIVE_DRAWS (1..16 draws a lane of mhx_*_derive / mhx_*_predict maps together; default 4 / 1; never more than the outputs leave registers for; read at every call)
  *                   POINTWISE_ROWS (2 | 4 | 8 | 16 data rows per tile of mhx_*_pointwise, five fp64 accumulators each in registers; default: the fastest measured per width, 8 in fp64 and 4 in fp32; read at every call)
+ *                   PSIS_SCRATCH_MB (as HPD_SCRATCH_MB, for mhx_*_psis; default 1024; read at every call)
+ *                   PSIS_ROWS (1 | 2 | 4 | 8 data rows per tile of the sweeps of mhx_*_psis, 2^11 LDS counters each; default 4; read at every call)
  * value == NULL unsets.  An unknown name is MHX_EINVAL.  The tools build (libmhx_tools.so, `make tools`) additionally knows
- * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER): setting one
+ * timing probes and fault injection (ZIG_PROBE, EMCEE_PROBE, EMCEE_STAMPS, ZIG_FORCE_FAIL, FAULT_SLAB, JIT_DEFS, JIT_FLAGS, RAM_PROF, HPD_STOP_AFTER, PSIS_STOP_AFTER): setting one
  * marks the context TAINTED -- mhx_stats.tainted = 1 for every run of it, and the host mirrors refuse to build a Chains from
  * such a run.  In libmhx.so those names do not exist. */
 int mhx_ctx_set_option(mhx_ctx *ctx, const char *name, const char *value);
@@ -833,7 +835,7 @@ int mhx_ctx_autocovariance(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples
  * mhx_run_destroy, lives on the context of `src` (destroy it first), and may itself be a `src`.  On a derived run
  *   work      mhx_run_device_samples (accepted = NULL), mhx_run_get_samples (accepted must be NULL: MHX_EINVAL otherwise),
  *             mhx_run_stats (no transitions; kernel_ms = the map's launch, kernel_variant = -1), mhx_run_form_name ("derived"),
- *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_run_predict, mhx_run_pointwise, mhx_group_attach, and every post-run statistic:
+ *             mhx_run_shape, mhx_run_host_stats (zeros), mhx_run_destroy, mhx_run_derive, mhx_run_predict, mhx_run_pointwise, mhx_run_psis, mhx_group_attach, and every post-run statistic:
  *             mhx_run_diagnostics, _ess_bulk_tail, _rank_diagnostics, _rank_scores, _order_statistics, _select_histogram, _cross_moments,
  *             _hpd, _histogram, _histogram2d, _autocovariance
  *   refuse    with MHX_ESTATE and a message that says the run is derived, before anything else is looked at: mhx_run_init, _sample,
@@ -920,6 +922,45 @@ int mhx_run_pointwise(const mhx_run *src, const char *source, const void *rows, 
 int mhx_ctx_pointwise(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains,
                       const char *source, const void *rows, int64_t nrows, int32_t rowlen, const void *data,
                       size_t ndata, int32_t shift_given, double *shift, double *out5, int64_t *T);
+
+/* PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out of every data row from the saved draws (Vehtari, Gelman, Gabry 2017;
+ * R loo's psis / gpdfit), on the device, with l[i, s] never stored.  `source`, rows, data and l[i, s] exactly as
+ * for mhx_run_pointwise: l is evaluated in the run's width and widened; everything after the widening is fp64 in both widths, with the
+ * engine's fp64 exp and log (log1p and expm1 are Kahan's forms on them).
+ * Definitions, per data row i, with T = n_saved x nchains (as a double where it enters arithmetic) and l_(0) <= ... <= l_(T-1) the draws
+ * ascending (ordered as the exact order statistics order them: -0 before +0):
+ *   M         the tail length min(floor(0.2 T), ceil(3 sqrt(T / reff))), computed in double on the host; M < 5 counts as M = 0
+ *   tau       the cutoff l_(M); it belongs to the body.  n_below = #{l < tau} <= M, n_eq = #{l == tau}
+ *   tail      a_0 <= ... <= a_(M-1): the n_below draws below tau, then M - n_below copies of tau.  lmin = a_0 (tau where M = 0)
+ *   c         exp(lmin - tau);  x_j = exp(lmin - a_(M-1-j)) - c, j < M: the tail's importance ratios relative to the largest, ascending
+ *   fit       (M >= 5, and a_(M-1) - a_0 >= 2^-52 / 100)  m = 30 + floor(sqrt(M)) grid points
+ *               theta_j = 1 / x_(M-1) + (1 - sqrt(m / (j - 1/2))) / (3 x*),  j = 1 .. m,  x* = x at index floor(M / 4 + 1/2) - 1
+ *               k_j = mean_i log1p(-theta_j x_i);  L_j = M (log(-theta_j / k_j) - k_j - 1);  w_j = 1 / sum_j' exp(L_j' - L_j)
+ *               theta^ = sum_j w_j theta_j;  k = mean_i log1p(-theta^ x_i);  sigma = -k / theta^;  khat = (k M + 5) / (M + 10)
+ *             where there is no fit, or theta^ or khat is not finite, or sigma is not a positive finite number (ties: x* = 0):
+ *             khat = +inf, sigma = NaN and the tail keeps its raw weights
+ *   lw~_j     fitted: min(0, log(sigma expm1(-khat log1p(-p_j)) / khat + c)), p_j = (j + 1/2) / M (the khat -> 0 limit
+ *             -sigma log1p(-p_j) + c where khat == 0);  raw: lmin - a_(M-1-j)
+ *   B         sum_{l_s > tau} exp(tau - l_s) + (n_eq - (M - n_below)): the body's ratios relative to the cutoff's, every term <= 1
+ *   elpd_loo  lmin + log((T - M) + sum_j exp(lw~_j + (a_(M-1-j) - lmin))) - log(c B + sum_j exp(lw~_j))
+ * out8 receives eight fp64 arrays of nrows, one after the other: elpd_loo, khat, sigma, tau, lmin, B, n_below, bad.  tail_out (may be
+ * NULL) receives [nrows][M] doubles, the tails a ascending.  *T and *M (each may be NULL) receive T and M.  tau, lmin, n_below, bad and
+ * the tails are exact (draws, bit for bit, and counts).
+ * A row with any NaN, +inf or -inf l among its draws has bad[i] = their number and NaN in its seven other entries and in its tail; no
+ * other row is affected.
+ * The order of every operation is a function of (n_saved, nchains) and reff alone: histograms are integer sums, the floating
+ * sums run lane-strided with a butterfly, over the waves in wave order and over the blocks' partials in index order; the tails are
+ * sorted before anything reads them.  Two calls give the same bits, whatever SELECT_BITS, PSIS_SCRATCH_MB and PSIS_ROWS are.
+ * Cost: (key passes of the select + 1) sweeps that each evaluate l for every (draw, row), a sort of nrows x M keys, nrows x m x M log1p.
+ * Rows go in batches whose scratch fits option PSIS_SCRATCH_MB (default 1024).  MHX_ESTATE and MHX_EINVAL as mhx_run_pointwise (out8
+ * in place of shift and out5); also MHX_EINVAL for reff not a positive finite number, M > 2^20, and one row whose scratch does not fit
+ * PSIS_SCRATCH_MB (refused before any sweep).  A refusal writes nothing to out8, tail_out, T or M.  Works on a derived run.  Blocking. */
+int mhx_run_psis(const mhx_run *src, const char *source, const void *rows, int64_t nrows, int32_t rowlen, const void *data,
+                 size_t ndata, double reff, double *out8, double *tail_out, int64_t *T, int64_t *M);
+/* the same on a caller's device tensor [n_samples][dim1][nchains] of the context's dtype (as mhx_ctx_pointwise) */
+int mhx_ctx_psis(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t dim1, int64_t nchains, const char *source,
+                 const void *rows, int64_t nrows, int32_t rowlen, const void *data, size_t ndata, double reff, double *out8,
+                 double *tail_out, int64_t *T, int64_t *M);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
