@@ -15,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include <errno.h>
@@ -784,9 +785,14 @@ int api_target_destroy(mhx_target* t)
     return MHX_OK;
 }
 
-static int launch_module(hipFunction_t fn, unsigned grid, unsigned block, hipStream_t s, void** params)
+// Launch a kernel of a run-time module.  The arguments are taken BY VALUE, in the kernel's order and each of the kernel's parameter type
+// up to const (a long where it says long, an int where it says int): the array of addresses hipModuleLaunchKernel wants is formed here.
+template <class... A>
+static int launch_module(hipFunction_t fn, dim3 grid, unsigned block, hipStream_t s, A... args)
 {
-    HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, s, params, nullptr));
+    static_assert(((!std::is_same<A, void**>::value) && ...), "launch_module takes the kernel's arguments, not an array of their addresses");
+    void* params[] = {(void*)&args...};
+    HIP_TRY(hipModuleLaunchKernel(fn, grid.x, grid.y, grid.z, block, 1, 1, 0, s, params, nullptr));
     return MHX_OK;
 }
 
@@ -810,8 +816,7 @@ int api_target_eval(mhx_ctx* ctx, const mhx_target* t, const mhx_real* x, int n,
             hipFunction_t fn;
             if ((rc = jit_generic_rwmh(t, &m))) break;
             if ((rc = jit_function(m, "mhx_jit_target_eval", &fn))) break;
-            void* params[] = {&dx, &dlp, &n, &d, &kind, &tp, &np, &cst, &lanes};
-            if ((rc = launch_module(fn, grid, 256, ctx->stream, params))) break;
+            if ((rc = launch_module(fn, grid, 256, ctx->stream, dx, dlp, n, d, kind, tp, np, cst, lanes))) break;
         } else {
             hipLaunchKernelGGL(k_target_eval, dim3(grid), dim3(256), 0, ctx->stream, dx, dlp, n, d, kind, tp, np, cst, lanes);
         }
@@ -1308,8 +1313,7 @@ int api_rwmh_create(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, 
                 for (int im = 0; im < 2 && rc == MHX_OK; ++im) {
                     if (!srcs[im]) continue;
                     mhx_real* dst = r->d_mfma_img + im * reals;
-                    void* params[] = {(void*)&srcs[im], &dst};
-                    rc = launch_module(fimg, 1, 256, ctx->stream, params);
+                    rc = launch_module(fimg, 1, 256, ctx->stream, srcs[im], dst);
                 }
                 if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(ctx->stream));
             }
@@ -1669,8 +1673,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
         draw = 0;
     }
     if (r->target->kind == MHX_TARGET_USER) {
-        void* params[] = {&a, &tp, &pv, &draw};
-        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, params);
+        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, a, tp, pv, draw);
         if (rc) return rc;
     } else {
         hipLaunchKernelGGL(k_rwmh_init, dim3(grid), dim3(256), 0, ctx->stream, a, tp, pv, draw);
@@ -1970,8 +1973,7 @@ int api_run_set_state(mhx_run* r, const mhx_real* x)
         int rc = jit_generic_rwmh(r->target, &m);
         if (rc) return rc;
         if ((rc = jit_function(m, "mhx_jit_target_eval", &fn))) return rc;
-        void* params[] = {&dx, &dlp, &nn, &dd, &kind, &tp, &np, &cst, &lanes};
-        if ((rc = launch_module(fn, grid, 256, ctx->stream, params))) return rc;
+        if ((rc = launch_module(fn, grid, 256, ctx->stream, dx, dlp, nn, dd, kind, tp, np, cst, lanes))) return rc;
     } else {
         hipLaunchKernelGGL(k_target_eval, dim3(grid), dim3(256), 0, ctx->stream, dx, dlp, nn, dd, kind, tp, np, cst, lanes);
     }
@@ -2141,7 +2143,7 @@ int api_run_destroy(mhx_run* r)
 #include "mhx_api_ram.inc"
 #include "mhx_api_mala.inc"
 
-// ---- what the post-run statistics share (the five .inc files below) ----
+// ---- what the post-run statistics share (the .inc files below) ----
 // The draws a statistic reads: a tensor [N][d1][C] on ctx's device, and the entry point's name for its messages.
 struct draws_view {
     mhx_ctx* ctx;
@@ -2217,6 +2219,93 @@ struct dev_array {
     ~dev_array() { if (p) (void)hipFree(p); }
     bool alloc(size_t count) { return hipMalloc(&p, count * sizeof(T)) == hipSuccess; }
 };
+
+// ---- what the statistics that compile a caller's text share (derive, predict, pointwise, psis) ----
+// One frame header of a user module and the define that switches its kernels on
+struct user_frame {
+    const char* have;
+    const char* header;
+};
+// The run-time module of a caller's text and its kernels.  The module's source -- with the defines the kernel key (jit_compile) -- is
+// the device math, the text under the name `file` (what the compiler's diagnostics call it), then every frame behind its define.  A
+// diagnostic on the caller's text makes the source the argument at fault: MHX_EINVAL, "the <noun> does not compile", the compiler's
+// log kept in the message.  Any other failure of the compile (no compiler, a module that does not load) stays MHX_EJIT.
+static int user_module(const draws_view& v, const char* file, const char* noun, const char* source, std::initializer_list<user_frame> frames,
+                       const std::vector<std::string>& defines, std::initializer_list<std::pair<const char*, hipFunction_t*>> kernels)
+{
+    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"";
+    s += file;
+    s += "\"\n";
+    s += source;
+    s += "\n";
+    for (const user_frame& f : frames) {
+        s += "#define ";
+        s += f.have;
+        s += " 1\n#include \"";
+        s += f.header;
+        s += "\"\n";
+    }
+    jit_module* m = nullptr;
+    int rc = jit_compile(v.ctx, s, defines, &m);
+    if (rc == MHX_EJIT) {
+        const std::string log = mhx_last_error();
+        if (log.find(file) != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the %s does not compile: %.1900s", v.who, noun, log.c_str());
+        return rc;
+    }
+    for (const auto& k : kernels)
+        if (rc == MHX_OK) rc = jit_function(m, k.first, k.second);
+    return rc;
+}
+
+// the data block of a user function: closed-over constants, at most 2^31 - 1 reals
+static int data_block_checked(const char* who, const mhx_real* data, size_t ndata)
+{
+    if (ndata && !data) return mhx_fail(MHX_EINVAL, "%s: data is NULL", who);
+    if (ndata > 0x7fffffffull) return mhx_fail(MHX_EINVAL, "%s: the data block is too large", who);
+    return MHX_OK;
+}
+// ... and the data rows of a pointwise function (`rows` itself is checked with the caller's other pointers), the data block, and the
+// tensor's extents, which the sweeps count in 31 bits
+static int row_blocks_checked(const draws_view& v, int64_t nrows, int32_t rowlen, const mhx_real* data, size_t ndata)
+{
+    const char* who = v.who;
+    if (nrows < 1 || rowlen < 1)
+        return mhx_fail(MHX_EINVAL, "%s: %lld data rows of %d reals: at least one row of at least one real", who, (long long)nrows, (int)rowlen);
+    if (nrows > 0x7fffffffll || (unsigned long long)nrows * (unsigned long long)rowlen > 0x7fffffffull)
+        return mhx_fail(MHX_EINVAL, "%s: %lld data rows of %d reals: rows are indexed in 31 bits", who, (long long)nrows, (int)rowlen);
+    if (int rc = data_block_checked(who, data, ndata)) return rc;
+    if (v.C > 0x7fffffffl || v.N > 0x7fffffffl)
+        return mhx_fail(MHX_EINVAL, "%s: %ld saved draws of %ld chains: each is counted in 31 bits", who, v.N, v.C);
+    return MHX_OK;
+}
+// The data block on the device: `count` reals of a scratch block or an allocation are `ndata ? ndata : 1` (one dummy element keeps the
+// pointer valid), and only a block that has reals is copied
+static size_t data_block_reals(size_t ndata) { return ndata ? ndata : 1; }
+static int data_block_upload(mhx_ctx* ctx, mhx_real* d_data, const mhx_real* data, size_t ndata)
+{
+    if (ndata) HIP_TRY(hipMemcpyAsync(d_data, data, ndata * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
+    return MHX_OK;
+}
+
+// The grid of a sweep of the pointwise frame (mhx_pointwise_sweep): chain blocks x strip slots x row tiles.  Slots only while the grid
+// is small -- MHX_POINTWISE_TARGET_BLOCKS, a few blocks per compute unit, is what it aims at before it stops splitting a chain block's
+// draws over strip slots -- and never more than MHX_POINTWISE_MAX_SLOTS: the partials are ncb * slots * nrows * K doubles whatever N
+// is.  `ntiles`: the row-tile term.  The pointwise sweep passes its tiles; PSIS passes 1, which makes the slots a function of the
+// tensor's shape alone -- not of the rows of a batch or of a tile -- so that the order of the sums over the draws, and with it every
+// bit of the result, is the same whatever PSIS_SCRATCH_MB and PSIS_ROWS are.
+#define MHX_POINTWISE_TARGET_BLOCKS 2048
+struct sweep_plan {
+    long ncb, nstrips, slots;
+};
+static sweep_plan pointwise_sweep_plan(const draws_view& v, long ntiles)
+{
+    sweep_plan g;
+    g.ncb = (v.C + MHX_POINTWISE_THREADS - 1) / MHX_POINTWISE_THREADS;
+    g.nstrips = (v.N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
+    const long want = (MHX_POINTWISE_TARGET_BLOCKS + g.ncb * ntiles - 1) / (g.ncb * ntiles);
+    g.slots = std::max(1l, std::min(std::min(want, g.nstrips), (long)MHX_POINTWISE_MAX_SLOTS));
+    return g;
+}
 
 #include "mhx_api_diag.inc"
 #include "mhx_api_moments.inc"

@@ -33,8 +33,7 @@ static int cond_check(mhx_run* r)
     int* nbad = r->d_cond_bad;
     HIP_TRY(hipMemsetAsync(nbad, 0, sizeof(int), ctx->stream));
     const int* ctab = r->d_cmp_tab;                         // (the last argument of a composite run's check kernel only)
-    void* params[] = {&a, &fam, &cdata, &ncdata, &pbuf, &nbad, &ctab};
-    int rc = launch_module(r->jit_cond_check, (unsigned)((r->n + 255) / 256), 256, ctx->stream, params);
+    int rc = launch_module(r->jit_cond_check, (unsigned)((r->n + 255) / 256), 256, ctx->stream, a, fam, cdata, ncdata, pbuf, nbad, ctab);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     int bad = 0;

@@ -1,5 +1,5 @@
 // derived quantities and predictive draws host side (included by mhx_api.hip after mhx_api_acf.inc): the checks, the run-time module
-// of the map, the derived run and its tensor, one launch (mhx_derive_kernels.h, DESIGN.md sections 6.5.5 and 6.5.6)
+// of the map (user_module), the derived run and its tensor, one launch (mhx_derive_kernels.h, DESIGN.md sections 6.5.5 and 6.5.6)
 
 // The outputs of the draws a lane maps together stay in registers until they are stored: (nout + 1) reals per draw.  More than this
 // many outputs are refused; up to it the draws per lane shrink so that the outputs stay within about a quarter of the register file.
@@ -33,19 +33,6 @@ static int derive_draws_per_lane(const mhx_ctx* ctx, const derive_kind& kind, in
     return std::min(asked >= 1 && asked <= 16 ? asked : kind.draws, fit);           // (the option never lifts the register cap)
 }
 
-// the module's source: the device math, the map, the frame; with the defines it is the kernel key (jit_compile)
-static std::string derive_source(const derive_kind& kind, const char* source)
-{
-    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"";
-    s += kind.file;
-    s += "\"\n";
-    s += source;
-    s += "\n#define ";
-    s += kind.have;
-    s += " 1\n#include \"mhx_derive_kernels.h\"\n";
-    return s;
-}
-
 // v is checked, nothing else is.  Nothing is left behind unless the call succeeds: the run and its tensor are owned here until then.
 // seed: the predictive streams' (a derived map has none); the run that is made inherits v's seed and first_id either way.
 static int derive_checked(const draws_view& v, const derive_kind& kind, const char* source, int32_t nout, const mhx_real* data, size_t ndata,
@@ -58,24 +45,15 @@ static int derive_checked(const draws_view& v, const derive_kind& kind, const ch
     if (nout > MHX_DERIVE_MAX_NOUT)
         return mhx_fail(MHX_EINVAL, "%s: nout = %d, at most %d outputs per map (they are held in registers): split the map", who, (int)nout,
                         MHX_DERIVE_MAX_NOUT);
-    if (ndata && !data) return mhx_fail(MHX_EINVAL, "%s: data is NULL", who);
-    if (ndata > 0x7fffffffull) return mhx_fail(MHX_EINVAL, "%s: the data block is too large", who);
+    if (int rc = data_block_checked(who, data, ndata)) return rc;
     if (v.C > 0x7fffffffl) return mhx_fail(MHX_EINVAL, "%s: %ld chains, a run holds fewer than 2^31", who, v.C);
     if (kind.rng && (unsigned long long)v.N > (1ull << 32))
         return mhx_fail(MHX_EINVAL, "%s: %ld saved draws, a predictive map numbers them in 32 bits (at most 2^32)", who, v.N);
     HIP_TRY(hipSetDevice(ctx->device));
     const int U = derive_draws_per_lane(ctx, kind, nout);
-    jit_module* m = nullptr;
     hipFunction_t fn = nullptr;
-    int rc = jit_compile(ctx, derive_source(kind, source), {"MHX_JIT_DERIVE_NOUT=" + std::to_string(nout), "MHX_JIT_DERIVE_DRAWS=" + std::to_string(U)}, &m);
-    if (rc == MHX_EJIT) {
-        // a diagnostic on the caller's text (derive_source names it derived.hip / predictive.hip): the source is the argument at fault, the compiler's
-        // log stays in the message.  Any other failure of the compile (no compiler, a module that does not load) stays MHX_EJIT.
-        const std::string log = mhx_last_error();
-        if (log.find(kind.file) != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the map does not compile: %.1900s", who, log.c_str());
-        return rc;
-    }
-    if (rc == MHX_OK) rc = jit_function(m, kind.entry, &fn);
+    int rc = user_module(v, kind.file, "map", source, {{kind.have, "mhx_derive_kernels.h"}},
+                         {"MHX_JIT_DERIVE_NOUT=" + std::to_string(nout), "MHX_JIT_DERIVE_DRAWS=" + std::to_string(U)}, {{kind.entry, &fn}});
     if (rc) return rc;
     std::unique_ptr<mhx_run> r(new mhx_run);
     r->dtype = ctx->dtype;
@@ -89,22 +67,18 @@ static int derive_checked(const draws_view& v, const derive_kind& kind, const ch
     rc = ensure_buffer((void**)&r->d_samples, &r->samples_cap, bytes, who, "derived sample tensor");
     if (rc) { (void)hipGetLastError(); return rc; }
     dev_array<mhx_real> d_data;
-    if (!d_data.alloc(ndata ? ndata : 1)) {                 // (one dummy element keeps the pointer valid)
+    if (!d_data.alloc(data_block_reals(ndata))) {
         (void)hipGetLastError();
         return mhx_fail(MHX_ENOMEM, "%s: %zu bytes of data block", who, ndata * sizeof(mhx_real));
     }
-    if (ndata) HIP_TRY(hipMemcpyAsync(d_data.p, data, ndata * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
-    const mhx_real* src = v.tensor;
-    mhx_real* dst = r->d_samples;
-    long N = v.N, C = v.C;
-    int d = v.d1 - 1, nd = (int)ndata;
-    const mhx_real* dd = d_data.p;
-    const long strip = (long)U * MHX_DERIVE_ROUNDS, nstrips = (N + strip - 1) / strip;
-    unsigned long long stream_seed = seed, first_id = v.first_id;
-    void* params[] = {&src, &dst, &N, &C, &d, &dd, &nd, &stream_seed, &first_id};        // (mhx_jit_derive takes the first seven)
+    if ((rc = data_block_upload(ctx, d_data.p, data, ndata))) return rc;
+    const long strip = (long)U * MHX_DERIVE_ROUNDS, nstrips = (v.N + strip - 1) / strip;
+    const dim3 grid((unsigned)((v.C + MHX_DERIVE_THREADS - 1) / MHX_DERIVE_THREADS), (unsigned)std::min(nstrips, 65535l));
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)((C + MHX_DERIVE_THREADS - 1) / MHX_DERIVE_THREADS), (unsigned)std::min(nstrips, 65535l), 1,
-                                  MHX_DERIVE_THREADS, 1, 1, 0, ctx->stream, params, nullptr));
+    // (mhx_jit_derive takes the first seven arguments, mhx_jit_predict the seed of its streams and the first chain's id as well)
+    rc = launch_module(fn, grid, MHX_DERIVE_THREADS, ctx->stream, v.tensor, r->d_samples, v.N, v.C, v.d1 - 1, d_data.p, (int)ndata,
+                       (unsigned long long)seed, (unsigned long long)v.first_id);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     float ms = 0.0f;

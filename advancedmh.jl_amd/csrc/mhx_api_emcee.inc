@@ -423,8 +423,8 @@ static int emcee_init(mhx_run* r, const mhx_real* init)
     const unsigned grid = (unsigned)((r->ens_w + 255) / 256), E = (unsigned)r->n_ens;
     int draw = init ? 0 : 1;
     if (r->jit_init) {
-        void* params[] = {&a, &tp, &draw};
-        HIP_TRY(hipModuleLaunchKernel(r->jit_init, grid, E, 1, 256, 1, 1, 0, ctx->stream, params, nullptr));
+        int rc = launch_module(r->jit_init, dim3(grid, E), 256, ctx->stream, a, tp, draw);
+        if (rc) return rc;
     } else {
         hipLaunchKernelGGL(k_emcee_init, dim3(grid, E), dim3(256), 0, ctx->stream, a, tp, draw);
     }

@@ -26,22 +26,6 @@ k_hpd_final(const mhx_hpd_row* __restrict__ rows, const mhx_key* __restrict__ ta
 
 #define MHX_HPD_SCRATCH_MB 1024.0                           // option HPD_SCRATCH_MB: bound on the scratch of a call, rows go in batches that fit
 
-// mhx_order_key on the host, of a value the select returned (a draw of this engine's width, widened)
-static unsigned long long hpd_key_of(const double v)
-{
-    if (v != v) return ~0ull;
-#if MHX_REAL64
-    uint64_t b;
-    memcpy(&b, &v, sizeof b);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-#else
-    const float f = (float)v;                               // exact: v is a widened float
-    uint32_t b;
-    memcpy(&b, &f, sizeof b);
-    return (unsigned long long)((b >> 31) ? ~b : (b | 0x80000000u));
-#endif
-}
-
 static size_t hpd_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }      // (a piece of scratch_carve)
 
 // the arguments are checked.  lower / upper are written last, after everything succeeded.
@@ -128,8 +112,8 @@ static int hpd_compute(const draws_view& v, const int32_t* params, int P, double
             bool any = false;
             for (int k = 0; k < R; ++k) {
                 const int i = r0 + k;
-                hL[k] = nan_row[i] ? 0ull : hpd_key_of(os[(size_t)i * 3]);
-                hU[k] = nan_row[i] ? ~0ull : hpd_key_of(os[(size_t)i * 3 + 1]);
+                hL[k] = nan_row[i] ? 0ull : mhx_select_key_of(os[(size_t)i * 3], MHX_KEY_BITS);
+                hU[k] = nan_row[i] ? ~0ull : mhx_select_key_of(os[(size_t)i * 3 + 1], MHX_KEY_BITS);
                 any = any || !nan_row[i];
             }
             if (!any) continue;

@@ -44,11 +44,9 @@ static int mala_mfma_images(mhx_run* r, jit_module* m)
     HIP_TRY(hipMalloc(&r->d_mfma_img, (ra + rt) * sizeof(mhx_real)));
     const mhx_real* src = r->target->dparams;
     mhx_real* dst = r->d_mfma_img;
-    void* pa[] = {(void*)&src, &dst};
-    rc = launch_module(fimg, 1, 256, r->ctx->stream, pa);
+    rc = launch_module(fimg, 1, 256, r->ctx->stream, src, dst);
     mhx_real* dstT = r->d_mfma_img2 = r->d_mfma_img + ra;
-    void* pt[] = {(void*)&src, &dstT};
-    if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, r->ctx->stream, pt);
+    if (rc == MHX_OK) rc = launch_module(fimgT, 1, 256, r->ctx->stream, src, dstT);
     if (rc == MHX_OK) HIP_TRY(hipStreamSynchronize(r->ctx->stream));
     return rc;
 }
@@ -222,8 +220,7 @@ static int mala_eval_state(mhx_run* r, int reset_counts)
     const mhx_real* tp = r->target->dparams;
     const unsigned grid = (unsigned)((r->n + 255) / 256);
     if (r->jit_init) {
-        void* params[] = {&a, &tp, &reset_counts};
-        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, params);
+        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, a, tp, reset_counts);
         if (rc) return rc;
     } else {
         hipLaunchKernelGGL(k_mala_init, dim3(grid), dim3(256), 0, ctx->stream, a, tp, reset_counts);

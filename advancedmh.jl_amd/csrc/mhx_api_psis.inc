@@ -1,4 +1,5 @@
-// PSIS-LOO host side (included by mhx_api.hip after mhx_api_pointwise.inc): the checks, the run-time module, and per batch of data rows
+// PSIS-LOO host side (included by mhx_api.hip after mhx_api_pointwise.inc): the checks (row_blocks_checked), the run-time module
+// (user_module) and the grid of the pointwise frame (pointwise_sweep_plan), and per batch of data rows
 // the cutoffs by the radix select (mhx_select_drive with a histogram pass that re-evaluates l; on the context's select block), then on
 // the context's tail block -- HPD's: it survives the select passes, and a call owns it until it returns -- one gather sweep, one
 // segmented sort of the tails, the fit (mhx_psis_kernels.h, DESIGN.md section 6.5.8)
@@ -7,14 +8,6 @@
 #define MHX_PSIS_ROWS_DEFAULT 4                             // data rows per tile of the two sweeps (LDS: rows x 2^11 counters)
 #define MHX_PSIS_MAX_TAIL (1ull << 20)                      // M at most: the fit's grid (30 + sqrt(M) points) lives in LDS
 #define MHX_PSIS_DRAWS_PER_SLOT (1l << 23)                  // 256 lanes x 2^23 draws: what a block may count in a 32-bit LDS counter
-
-static std::string psis_source(const char* source)
-{
-    std::string s = "#include \"mhx_device_math.h\"\n#line 1 \"pointwise.hip\"\n";
-    s += source;
-    s += "\n#define MHX_HAVE_POINTWISE 1\n#include \"mhx_pointwise_kernels.h\"\n#define MHX_HAVE_PSIS 1\n#include \"mhx_psis_kernels.h\"\n";
-    return s;
-}
 
 // M = min(floor(0.2 T), ceil(3 sqrt(T / reff))) in double; below 5: 0 (no smoothing)
 static unsigned long long psis_tail_length(unsigned long long T, double reff)
@@ -53,14 +46,11 @@ static int psis_hist_pass(void* user, const uint64_t* prefixes, const int32_t* n
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d_hist, 0, nh * sizeof(uint64_t), ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_pf, prefixes, (size_t)s->nrows * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    const mhx_real* src = v.tensor;
-    const mhx_real *rr = s->d_rows, *dd = s->d_data;
-    long N = v.N, C = v.C;
-    int d = v.d1 - 1, nrw = s->nrows, rl = s->rowlen, nd = s->ndata, sh = shift, db = digit_bits, top = shift + digit_bits == MHX_KEY_BITS;
-    const unsigned long long* cpf = d_pf;
-    void* p[] = {&src, &N, &C, &d, &rr, &nrw, &rl, &dd, &nd, &cpf, &sh, &db, &top, &d_hist};
-    const unsigned ntiles = (unsigned)((s->nrows + s->R - 1) / s->R);
-    HIP_TRY(hipModuleLaunchKernel(s->f_hist, (unsigned)s->ncb, (unsigned)s->slots, ntiles, MHX_POINTWISE_THREADS, 1, 1, 0, ctx->stream, p, nullptr));
+    const int top = shift + digit_bits == MHX_KEY_BITS;
+    const dim3 grid((unsigned)s->ncb, (unsigned)s->slots, (unsigned)((s->nrows + s->R - 1) / s->R));
+    rc = launch_module(s->f_hist, grid, MHX_POINTWISE_THREADS, ctx->stream, v.tensor, v.N, v.C, v.d1 - 1, s->d_rows, s->nrows, s->rowlen,
+                       s->d_data, s->ndata, d_pf, (int)shift, (int)digit_bits, top, d_hist);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(hist, d_hist, nh * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return MHX_OK;
@@ -73,14 +63,7 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     const char* who = v.who;
     mhx_ctx* ctx = v.ctx;
     if (!source || !rows || !out8) return mhx_fail(MHX_EINVAL, "%s: NULL argument", who);
-    if (nrows < 1 || rowlen < 1)
-        return mhx_fail(MHX_EINVAL, "%s: %lld data rows of %d reals: at least one row of at least one real", who, (long long)nrows, (int)rowlen);
-    if (nrows > 0x7fffffffll || (unsigned long long)nrows * (unsigned long long)rowlen > 0x7fffffffull)
-        return mhx_fail(MHX_EINVAL, "%s: %lld data rows of %d reals: rows are indexed in 31 bits", who, (long long)nrows, (int)rowlen);
-    if (ndata && !data) return mhx_fail(MHX_EINVAL, "%s: data is NULL", who);
-    if (ndata > 0x7fffffffull) return mhx_fail(MHX_EINVAL, "%s: the data block is too large", who);
-    if (v.C > 0x7fffffffl || v.N > 0x7fffffffl)
-        return mhx_fail(MHX_EINVAL, "%s: %ld saved draws of %ld chains: each is counted in 31 bits", who, v.N, v.C);
+    if (int rc = row_blocks_checked(v, nrows, rowlen, data, ndata)) return rc;
     if (!(reff > 0.0) || !std::isfinite(reff)) return mhx_fail(MHX_EINVAL, "%s: reff = %g is not a positive finite number", who, reff);
     const unsigned long long S = v.S();
     const unsigned long long M = psis_tail_length(S, reff);
@@ -96,15 +79,11 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     }
     const int digit = opt_int(ctx, "SELECT_BITS", MHX_SELECT_DIGIT_BITS);
     if (digit < 1 || digit > MHX_SELECT_MAX_DIGIT_BITS) return mhx_fail(MHX_EINVAL, "%s: option SELECT_BITS = %d outside [1, %d]", who, digit, MHX_SELECT_MAX_DIGIT_BITS);
-    // the grid of the two sweeps, as the pointwise sweep's; enough strip slots that no block counts 2^32 draws of a row
-    const long ncb = (v.C + MHX_POINTWISE_THREADS - 1) / MHX_POINTWISE_THREADS;
-    const long nstrips = (v.N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
-    const long min_slots = (v.N + MHX_PSIS_DRAWS_PER_SLOT - 1) / MHX_PSIS_DRAWS_PER_SLOT;
+    // the grid of the two sweeps, without the row-tile term (pointwise_sweep_plan says why); enough strip slots that no block counts
+    // 2^32 draws of a row
+    const sweep_plan g = pointwise_sweep_plan(v, 1);
+    const long ncb = g.ncb, slots = std::max((v.N + MHX_PSIS_DRAWS_PER_SLOT - 1) / MHX_PSIS_DRAWS_PER_SLOT, g.slots);
     const size_t nr = (size_t)nrows, cap = (size_t)M;
-    // (the slots are a function of the tensor's shape alone -- not of the rows of a batch or of a tile -- so that the order of the sums
-    // over the draws, and with it every bit of the result, is the same whatever PSIS_SCRATCH_MB and PSIS_ROWS are)
-    const long want_slots = (MHX_POINTWISE_TARGET_BLOCKS + ncb - 1) / ncb;
-    const long slots = std::max(min_slots, std::max(1l, std::min(std::min(want_slots, nstrips), (long)MHX_POINTWISE_MAX_SLOTS)));
     if (slots > 65535) return mhx_fail(MHX_EINVAL, "%s: %ld saved draws need more than 65535 strip slots", who, v.N);
     // the scratch plan, before any compile or sweep: the largest batch of rows whose pieces fit the budget
     auto sort_bytes_of = [&](size_t rb, size_t* bytes) {
@@ -121,7 +100,7 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     };
     auto plan_bytes = [&](size_t rb, size_t sort_bytes) {
         scratch_pieces c{nullptr};
-        c.take<mhx_real>(nr * (size_t)rowlen); c.take<mhx_real>(ndata ? ndata : 1);
+        c.take<mhx_real>(nr * (size_t)rowlen); c.take<mhx_real>(data_block_reals(ndata));
         c.take<mhx_key>(rb * cap); c.take<mhx_key>(rb * cap); c.take<double>(rb * cap); c.take<double>(rb * cap ? rb * cap : 1);
         c.take<char>(sort_bytes ? sort_bytes : 1);
         c.take<double>((size_t)ncb * (size_t)slots * rb * 3);
@@ -139,17 +118,11 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
                             "PSIS_SCRATCH_MB = %g", who, M, need / 1048576.0, budget_mb);
         Rb = std::max<size_t>(1, std::min<size_t>(Rb - 1, (size_t)((double)Rb * budget_mb * 1048576.0 / need)));
     }
-    jit_module* m = nullptr;
     hipFunction_t f_hist = nullptr, f_gather = nullptr, f_fit = nullptr;
-    int rc = jit_compile(ctx, psis_source(source), {"MHX_JIT_PSIS_ROWS=" + std::to_string(R)}, &m);
-    if (rc == MHX_EJIT) {                                   // as pointwise_checked: a diagnostic on the caller's text is the caller's error
-        const std::string log = mhx_last_error();
-        if (log.find("pointwise.hip") != std::string::npos) return mhx_fail(MHX_EINVAL, "%s: the function does not compile: %.1900s", who, log.c_str());
-        return rc;
-    }
-    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_psis_hist", &f_hist);
-    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_psis_gather", &f_gather);
-    if (rc == MHX_OK) rc = jit_function(m, "mhx_jit_psis_fit", &f_fit);
+    int rc = user_module(v, "pointwise.hip", "function", source,
+                         {{"MHX_HAVE_POINTWISE", "mhx_pointwise_kernels.h"}, {"MHX_HAVE_PSIS", "mhx_psis_kernels.h"}},
+                         {"MHX_JIT_PSIS_ROWS=" + std::to_string(R)},
+                         {{"mhx_jit_psis_hist", &f_hist}, {"mhx_jit_psis_gather", &f_gather}, {"mhx_jit_psis_fit", &f_fit}});
     if (rc) return rc;
     const size_t P = (size_t)ncb * (size_t)slots;
     mhx_real *d_rows = nullptr, *d_data = nullptr;
@@ -160,7 +133,7 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     unsigned* d_off = nullptr;
     rc = scratch_carve(&ctx->hpd_scratch, &ctx->hpd_bytes, who, "PSIS scratch", [&](scratch_pieces& c) {
         d_rows = c.take<mhx_real>(nr * (size_t)rowlen);     // every data row, once
-        d_data = c.take<mhx_real>(ndata ? ndata : 1);
+        d_data = c.take<mhx_real>(data_block_reals(ndata));
         d_tails = c.take<mhx_key>(Rb * cap);                // the keys strictly below the cutoffs, as they arrive
         d_sorted = c.take<mhx_key>(Rb * cap);               // ... ascending
         d_x = c.take<double>(Rb * cap);                     // the abscissae of the fit
@@ -175,7 +148,7 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     });
     if (rc) { (void)hipGetLastError(); return rc; }
     HIP_TRY(hipMemcpyAsync(d_rows, rows, nr * (size_t)rowlen * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
-    if (ndata) HIP_TRY(hipMemcpyAsync(d_data, data, ndata * sizeof(mhx_real), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = data_block_upload(ctx, d_data, data, ndata))) return rc;
     // phase timing (tools build): return after 1 the select, 2 the gather, 3 the sort, with nothing written to the caller
     const char* stop_opt = MHX_PROBE_OPT(ctx, "PSIS_STOP_AFTER");
     const int stop_after = stop_opt ? atoi(stop_opt) : 0;
@@ -184,30 +157,23 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
     std::vector<unsigned> hoff(Rb * 2);
     const int64_t rank = (int64_t)M;                        // tau = l_(M), 0-based; M <= 0.2 T < T
     select_landing(ctx, digit, (int32_t)Rb, 1);
-    const mhx_real* src = v.tensor;
-    long N = v.N, C = v.C, PP = (long)P;
-    int d = v.d1 - 1, nd = (int)ndata, rl = (int)rowlen;
-    unsigned long long capv = M;
-    double Td = (double)S;
+    const int d = v.d1 - 1;
     for (size_t r0 = 0; r0 < nr; r0 += Rb) {
         const size_t rb = std::min(Rb, nr - r0);
-        int nrw = (int)rb;
-        const mhx_real *rr = d_rows + r0 * (size_t)rowlen, *dd = d_data;
-        psis_pass_source ps{v, f_hist, rr, dd, nrw, rl, nd, R, ncb, slots};
+        const mhx_real* rr = d_rows + r0 * (size_t)rowlen;
+        psis_pass_source ps{v, f_hist, rr, d_data, (int)rb, (int)rowlen, (int)ndata, R, ncb, slots};
         rc = mhx_select_drive(who, MHX_KEY_BITS, digit, (int32_t)rb, &rank, 1, S, psis_hist_pass, &ps, taus.data(), ctx->select_landing,
                               ctx->select_landing_words);
         if (rc) return rc;
         if (stop_after == 1) continue;
-        for (size_t k = 0; k < rb; ++k) hkey[k] = hpd_key_of(taus[k]);
+        for (size_t k = 0; k < rb; ++k) hkey[k] = mhx_select_key_of(taus[k], MHX_KEY_BITS);
         HIP_TRY(hipMemsetAsync(d_cursor, 0, rb * sizeof(uint64_t), ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_tkey, hkey.data(), rb * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d_tau, taus.data(), rb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        const unsigned long long *ctkey = d_tkey, *ccur = d_cursor;
-        const double *ctau = d_tau, *cpart = d_part;
-        const mhx_key* csorted = d_sorted;
-        const unsigned ntiles = (unsigned)((rb + (size_t)R - 1) / (size_t)R);
-        void* p1[] = {&src, &N, &C, &d, &rr, &nrw, &rl, &dd, &nd, &ctkey, &ctau, &capv, &d_cursor, &d_tails, &d_part};
-        HIP_TRY(hipModuleLaunchKernel(f_gather, (unsigned)ncb, (unsigned)slots, ntiles, MHX_POINTWISE_THREADS, 1, 1, 0, ctx->stream, p1, nullptr));
+        const dim3 grid((unsigned)ncb, (unsigned)slots, (unsigned)((rb + (size_t)R - 1) / (size_t)R));
+        rc = launch_module(f_gather, grid, MHX_POINTWISE_THREADS, ctx->stream, v.tensor, v.N, v.C, d, rr, (int)rb, (int)rowlen, d_data, (int)ndata,
+                           d_tkey, d_tau, M, d_cursor, d_tails, d_part);
+        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(hcur.data(), d_cursor, rb * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         bool any = false;
@@ -228,8 +194,9 @@ static int psis_checked(const draws_view& v, const char* source, const mhx_real*
                 return mhx_fail(MHX_EHIP, "%s: segmented radix sort of the tails failed", who);
         }
         if (stop_after == 3) { HIP_TRY(hipStreamSynchronize(ctx->stream)); continue; }
-        void* p2[] = {&csorted, &ccur, &ctau, &cpart, &PP, &nrw, &capv, &Td, &d_x, &d_out, &d_tl};
-        HIP_TRY(hipModuleLaunchKernel(f_fit, (unsigned)rb, 1, 1, MHX_PSIS_FIT_THREADS, 1, 1, 0, ctx->stream, p2, nullptr));
+        rc = launch_module(f_fit, (unsigned)rb, MHX_PSIS_FIT_THREADS, ctx->stream, d_sorted, d_cursor, d_tau, d_part, (long)P, (int)rb, M, (double)S,
+                           d_x, d_out, d_tl);
+        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(hout.data(), d_out, rb * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (tail_out && cap) HIP_TRY(hipMemcpyAsync(tails.data() + r0 * cap, d_tl, rb * cap * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));

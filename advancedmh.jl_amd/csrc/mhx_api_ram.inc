@@ -460,8 +460,7 @@ static int ram_init(mhx_run* r, const mhx_real* init)
     int draw = init ? 0 : 1;
     const unsigned grid = grid1d(r->n, 256);
     if (r->jit_init) {
-        void* params[] = {&a, &tp, &draw};
-        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, params);
+        int rc = launch_module(r->jit_init, grid, 256, ctx->stream, a, tp, draw);
         if (rc) return rc;
     } else {
         hipLaunchKernelGGL(k_ram_init, dim3(grid), dim3(256), 0, ctx->stream, a, tp, draw);

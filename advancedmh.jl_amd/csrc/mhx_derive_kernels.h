@@ -50,18 +50,7 @@
 #if defined(MHX_HAVE_DERIVED) || defined(MHX_HAVE_PREDICTIVE)
 MHX_NS_BEGIN
 
-// one draw as the map reads it
-struct mhx_derive_in {
-    const mhx_real* base;       // row 0 of the draw at the block's first chain (wave-uniform)
-    long ld;                    // C
-    int d;
-    mhx_u32 lane;               // the lane's byte offset in the block's chains
-    MHX_DEV mhx_real operator[](const int k) const
-    {
-        const int kk = k < 0 ? 0 : (k > d ? d : k);
-        return mhx_ld_off(base + (long)kk * ld, lane);
-    }
-};
+// (one draw as the map reads it: mhx_derive_in, mhx_device_math.h)
 
 // the outputs of one draw
 template <int K>

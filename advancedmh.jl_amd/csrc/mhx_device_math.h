@@ -121,6 +121,52 @@ MHX_DEV mhx_real mhx_ld_off(const mhx_real* base, mhx_u32 byte_off)
 }
 MHX_DEV void mhx_st_off(mhx_real* base, mhx_u32 byte_off, mhx_real v) { *(mhx_real*)((char*)base + byte_off) = v; }
 
+// One saved draw of a sample tensor [N][d + 1][C] as a user function reads it (MHX_DERIVED, MHX_PREDICTIVE, MHX_POINTWISE): x[k] is a
+// load of row k of the draw, issued where the source names it; k is clamped to [0, d], x[d] is the draw's lp.
+struct mhx_derive_in {
+    const mhx_real* base;       // row 0 of the draw at the block's first chain (wave-uniform)
+    long ld;                    // C
+    int d;
+    mhx_u32 lane;               // the lane's byte offset in the block's chains
+    MHX_DEV mhx_real operator[](const int k) const
+    {
+        const int kk = k < 0 ? 0 : (k > d ? d : k);
+        return mhx_ld_off(base + (long)kk * ld, lane);
+    }
+};
+
+// The order key of a draw (the radix select, the HPD and PSIS tails): an unsigned key of the draw's own width whose unsigned order is
+// the numeric order (sign set: all bits inverted; sign clear: sign bit set); every NaN becomes the all-ones key, so NaNs come last as
+// in numpy.sort.  -0.0 < +0.0 as keys.  The host's pair is mhx_select_key_of / mhx_select_key_value (mhx_select.h).
+#if MHX_REAL64
+typedef unsigned long long mhx_key;
+#define MHX_KEY_BITS 64
+MHX_DEV mhx_key mhx_order_key(const double x)
+{
+    const mhx_key b = __builtin_bit_cast(mhx_key, x);
+    if (x != x) return ~0ull;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+#else
+typedef unsigned int mhx_key;
+#define MHX_KEY_BITS 32
+MHX_DEV mhx_key mhx_order_key(const float x)
+{
+    const mhx_key b = __builtin_bit_cast(mhx_key, x);
+    if (x != x) return ~0u;
+    return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+#endif
+// the inverse, widened (exactly) to double; the all-ones key (NaN) is not in its domain: the callers answer NaN rows themselves
+MHX_DEV double mhx_key_value(const mhx_key k)
+{
+#if MHX_REAL64
+    return __builtin_bit_cast(double, (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k);
+#else
+    return (double)__builtin_bit_cast(float, (k >> 31) ? (k ^ 0x80000000u) : ~k);
+#endif
+}
+
 // A [rows][ld] slab of reals addressed through a buffer descriptor: wave-uniform base in the SRD, the row
 // offset in an SGPR (soffset), the lane's column offset in one VGPR (voffset) -- no per-access 64-bit
 // vector address arithmetic.  `bytes` bounds the slab (hardware range check).

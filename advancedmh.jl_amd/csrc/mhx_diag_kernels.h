@@ -153,27 +153,7 @@ MHX_DEV double mhx_diag_fold_rank(const mhx_real* __restrict__ sorted, const lon
 }
 
 // ---- exact order statistics: one pass of a histogram radix SELECT over the strided tensor ----
-// A draw becomes an unsigned key of its own width whose unsigned order is the numeric order (sign set: all bits inverted;
-// sign clear: sign bit set); every NaN becomes the all-ones key, so NaNs come last as in numpy.sort.  -0.0 < +0.0 as keys.
-#if MHX_REAL64
-typedef unsigned long long mhx_key;
-#define MHX_KEY_BITS 64
-MHX_DEV mhx_key mhx_order_key(const double x)
-{
-    const mhx_key b = (mhx_key)__double_as_longlong(x);
-    if (x != x) return ~0ull;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-#else
-typedef unsigned int mhx_key;
-#define MHX_KEY_BITS 32
-MHX_DEV mhx_key mhx_order_key(const float x)
-{
-    const mhx_key b = __float_as_uint(x);
-    if (x != x) return ~0u;
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-#endif
+// The draws are compared as their order keys (mhx_order_key, mhx_device_math.h): NaNs come last, -0.0 < +0.0.
 
 #define MHX_SELECT_THREADS 512
 // loads in flight per thread: 32 bytes per thread either way (16 KiB per block, up to 64 KiB per CU)

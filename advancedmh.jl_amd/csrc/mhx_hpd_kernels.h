@@ -9,21 +9,12 @@
 //   (the host sorts the two buffers of every row: rocPRIM radix sort of the unsigned keys)
 //   mhx_hpd_argmin_body / mhx_hpd_final_body   the first minimum of b[i] - a[i] over i < m, a and b rebuilt from the sorted buffers,
 //                         the thresholds and the counts
-// Everything works on the select's own keys (mhx_order_key), so the order is the select's bit for bit.
+// Everything works on the select's own keys (mhx_order_key and its inverse mhx_key_value, mhx_device_math.h), so the order is the
+// select's bit for bit.
 #pragma once
 #include "mhx_diag_kernels.h"
 
 MHX_NS_BEGIN
-
-// the inverse of mhx_order_key, widened (exactly) to double; the all-ones key (NaN) never reaches it: NaN rows are answered on the host
-MHX_DEV double mhx_key_value(const mhx_key k)
-{
-#if MHX_REAL64
-    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-#else
-    return (double)__uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
-#endif
-}
 
 // lanes of this wave below the calling lane whose bit is set in `mask`
 MHX_DEV unsigned mhx_hpd_rank_in(const unsigned long long mask)

@@ -22,10 +22,12 @@
 //   l NaN or +inf       bad += 1, sumexp = NaN (which no later step removes); max[i] is made NaN when the row is written
 // A running max of -inf meets only finite l: exp(-inf) = 0 and sumexp (0 until then) becomes 0 * 0 + 1.
 //
-// The end of a lane's strips: the partials are merged over the wave by a butterfly of shuffles (xor 1, 2, .. 32: the pair merge
-// is symmetric in its arguments bit for bit, so every lane ends with the same value), then over the block's four waves through
-// LDS in wave order.  Lanes beyond C hold the neutral partial (-inf, 0, 0, 0, 0) and take part.  No atomics anywhere: the order
-// of every operation is a function of the shape alone, and two calls give the same bits.
+// The end of a lane's strips: mhx_block_partials (butterfly over the wave, the block's four waves through LDS in wave order).  Lanes
+// beyond C hold the neutral partial (-inf, 0, 0, 0, 0) and take part.  No atomics anywhere: the order of every operation is a
+// function of the shape alone, and two calls give the same bits.
+//
+// This header also holds what the PSIS sweeps (mhx_psis_kernels.h) share with this one: the sweep frame mhx_pointwise_sweep and the
+// block reduction mhx_block_partials.
 #pragma once
 #include "mhx_device_math.h"
 
@@ -44,18 +46,7 @@
 #ifdef MHX_HAVE_POINTWISE
 MHX_NS_BEGIN
 
-// one draw as the function reads it: mhx_derive_in's load, restated here so that this header stands without the derive frame
-struct mhx_pointwise_in {
-    const mhx_real* base;       // row 0 of the draw at the block's first chain (wave-uniform)
-    long ld;                    // C
-    int d;
-    mhx_u32 lane;               // the lane's byte offset in the block's chains
-    MHX_DEV mhx_real operator[](const int k) const
-    {
-        const int kk = k < 0 ? 0 : (k > d ? d : k);
-        return mhx_ld_off(base + (long)kk * ld, lane);
-    }
-};
+typedef mhx_derive_in mhx_pointwise_in;     // one draw as the function reads it (mhx_device_math.h)
 
 // one data row
 struct mhx_pointwise_row {
@@ -101,13 +92,107 @@ MHX_DEV void mhx_pw_merge_lse(double& mx, double& se, const double bmx, const do
     mx = a_big ? mx : bmx;
 }
 
+// ---- what the sweeps of this module and of mhx_psis_kernels.h share ---------------------------------------------------------------
+// The merge of two partials of K doubles, a <- a (+) b: every field a plain sum, or (max, sumexp) first and plain sums after.
+struct mhx_merge_sums {
+    template <int K>
+    MHX_DEV void operator()(double (&a)[K], const double (&b)[K]) const
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] = a[k] + b[k];
+    }
+};
+struct mhx_merge_pw {
+    MHX_DEV void operator()(double (&a)[5], const double (&b)[5]) const
+    {
+        mhx_pw_merge_lse(a[0], a[1], b[0], b[1]);
+        a[2] = a[2] + b[2];
+        a[3] = a[3] + b[3];
+        a[4] = a[4] + b[4];
+    }
+};
+
+// The sweep frame: every draw of this lane's strips x every row of the block's tile -> f(j, l), l = the user function of (draw, row
+// i0 + j).  grid (chain blocks, strip slots, row tiles); a lane beyond C calls nothing.  SKIP: the rows of a ragged last tile beyond
+// nrows are skipped (what a sweep that counts needs); otherwise they are evaluated on a repeat of the last row, for the caller not to
+// write.  C and the lane offset are made opaque as in mhx_derive_draws: a scalar base plus the lane's 32-bit offset per load.
+template <int R, bool SKIP, class F>
+MHX_DEV void mhx_pointwise_sweep(const mhx_real* __restrict__ src, const long N, const long C, const int d,
+                                 const mhx_real* __restrict__ rows, const int nrows, const int rowlen,
+                                 const mhx_real* __restrict__ data, const int ndata, const F& f)
+{
+    const long c0 = (long)blockIdx.x * MHX_POINTWISE_THREADS;
+    const int i0 = (int)blockIdx.z * R;
+    if (c0 + (long)threadIdx.x < C) {
+        long ld = C;
+        mhx_u32 l = (mhx_u32)threadIdx.x * MHX_RB;
+        asm volatile("" : "+s"(ld), "+v"(l));
+        const long nstrips = (N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
+        for (long s = blockIdx.y; s < nstrips; s += gridDim.y) {
+            const long t0 = s * MHX_POINTWISE_STRIP;
+            const long end = t0 + MHX_POINTWISE_STRIP < N ? t0 + MHX_POINTWISE_STRIP : N;
+            for (long t = t0; t < end; ++t) {
+                const mhx_pointwise_in x = {src + t * (long)(d + 1) * ld + c0, ld, d, l};
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const bool live = i0 + j < nrows;               // uniform over the block
+                    if (SKIP && !live) continue;
+                    const mhx_pointwise_row r = {rows + (long)(live ? i0 + j : nrows - 1) * rowlen, rowlen};
+                    f(j, mhx_user_pointwise(x, r, rowlen, d, data, ndata));
+                }
+            }
+        }
+    }
+}
+
+// The block's partial of R rows x K doubles: v[j] of every lane merged over the wave by a butterfly of shuffles (xor 1, 2, .. 32: a
+// merge that is symmetric in its arguments bit for bit leaves every lane with the same value), then over the block's waves through
+// LDS in wave order by thread j, which writes row i0 + j of part [P][nrows][K] at p = blockIdx.x * gridDim.y + blockIdx.y.  Every
+// lane of the block calls it, the lanes beyond C with the neutral partial.
+template <int R, int K, class M>
+MHX_DEV void mhx_block_partials(double (&v)[R][K], const M& merge, const int nrows, double* __restrict__ part)
+{
+    __shared__ double lds[MHX_POINTWISE_THREADS / 64][R][K];
+    const int i0 = (int)blockIdx.z * R;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+#pragma unroll
+        for (int mask = 1; mask < 64; mask <<= 1) {
+            double b[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) b[k] = __shfl_xor(v[j][k], mask, 64);
+            merge(v[j], b);
+        }
+    }
+    const int wave = (int)threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+#pragma unroll
+            for (int k = 0; k < K; ++k) lds[wave][j][k] = v[j][k];
+    }
+    __syncthreads();
+    const int j = (int)threadIdx.x;
+    if (j < R && i0 + j < nrows) {
+        double a[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) a[k] = lds[0][j][k];
+        for (int w = 1; w < MHX_POINTWISE_THREADS / 64; ++w) merge(a, lds[w][j]);
+        const long p = (long)blockIdx.x * gridDim.y + blockIdx.y;
+        double* o = part + (p * (long)nrows + (i0 + j)) * K;
+#pragma unroll
+        for (int k = 0; k < K; ++k) o[k] = a[k];
+    }
+}
+
+// The pointwise sweep.  Its loop is mhx_pointwise_sweep<R, false> written out: on the frame the fp64 kernel at R = 8 goes from 159 to
+// 169 - 191 VGPRs and from three waves per SIMD to two (DESIGN.md section 6.7 has the forms tried).
 template <int R>
 MHX_DEV void mhx_pointwise_body(const mhx_real* __restrict__ src, const long N, const long C, const int d,
                                 const mhx_real* __restrict__ rows, const int nrows, const int rowlen,
                                 const mhx_real* __restrict__ data, const int ndata, const double* __restrict__ shift,
                                 double* __restrict__ part)
 {
-    __shared__ double lds[MHX_POINTWISE_THREADS / 64][R][5];
     const long c0 = (long)blockIdx.x * MHX_POINTWISE_THREADS;
     const bool active = c0 + (long)threadIdx.x < C;
     const int i0 = (int)blockIdx.z * R;
@@ -120,7 +205,7 @@ MHX_DEV void mhx_pointwise_body(const mhx_real* __restrict__ src, const long N, 
         sh[j] = shift[i];
     }
     if (active) {
-        long ld = C;                                                // as mhx_derive_draws: scalar base + 32-bit lane offset per load
+        long ld = C;
         mhx_u32 l = (mhx_u32)threadIdx.x * MHX_RB;
         asm volatile("" : "+s"(ld), "+v"(l));
         const long nstrips = (N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
@@ -139,46 +224,13 @@ MHX_DEV void mhx_pointwise_body(const mhx_real* __restrict__ src, const long N, 
             }
         }
     }
-    // over the wave
-    double bad[R];
+    double v[R][5];
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-        bad[j] = (double)acc[j].bad;                                // (a lane counts at most N < 2^32 draws; their sums are doubles)
-#pragma unroll
-        for (int mask = 1; mask < 64; mask <<= 1) {
-            const double bmx = __shfl_xor(acc[j].mx, mask, 64), bse = __shfl_xor(acc[j].se, mask, 64);
-            mhx_pw_merge_lse(acc[j].mx, acc[j].se, bmx, bse);
-            acc[j].s1 = acc[j].s1 + __shfl_xor(acc[j].s1, mask, 64);
-            acc[j].s2 = acc[j].s2 + __shfl_xor(acc[j].s2, mask, 64);
-            bad[j] = bad[j] + __shfl_xor(bad[j], mask, 64);
-        }
+        v[j][0] = acc[j].mx; v[j][1] = acc[j].se; v[j][2] = acc[j].s1; v[j][3] = acc[j].s2;
+        v[j][4] = (double)acc[j].bad;                               // (a lane counts at most N < 2^32 draws; their sums are doubles)
     }
-    const int wave = (int)threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            lds[wave][j][0] = acc[j].mx;
-            lds[wave][j][1] = acc[j].se;
-            lds[wave][j][2] = acc[j].s1;
-            lds[wave][j][3] = acc[j].s2;
-            lds[wave][j][4] = bad[j];
-        }
-    }
-    __syncthreads();
-    // over the block's waves, in wave order: thread j merges row j of the tile and writes the block's partial
-    const int j = (int)threadIdx.x;
-    if (j < R && i0 + j < nrows) {
-        double mx = lds[0][j][0], se = lds[0][j][1], s1 = lds[0][j][2], s2 = lds[0][j][3], bad = lds[0][j][4];
-        for (int w = 1; w < MHX_POINTWISE_THREADS / 64; ++w) {
-            mhx_pw_merge_lse(mx, se, lds[w][j][0], lds[w][j][1]);
-            s1 = s1 + lds[w][j][2];
-            s2 = s2 + lds[w][j][3];
-            bad = bad + lds[w][j][4];
-        }
-        const long p = (long)blockIdx.x * gridDim.y + blockIdx.y;
-        double* o = part + (p * (long)nrows + (i0 + j)) * 5;
-        o[0] = mx; o[1] = se; o[2] = s1; o[3] = s2; o[4] = bad;
-    }
+    mhx_block_partials(v, mhx_merge_pw{}, nrows, part);
 }
 
 extern "C" __global__ void __launch_bounds__(MHX_POINTWISE_THREADS, MHX_DERIVE_MIN_WAVES)

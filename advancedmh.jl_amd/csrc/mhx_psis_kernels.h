@@ -12,9 +12,9 @@
 //   mhx_jit_psis_fit      one block per row: the partials merged in index order, the generalised-Pareto fit of Zhang and Stephens, the
 //                         smoothed tail and the two sums of elpd_loo
 // Compiled at run time behind the user's MHX_POINTWISE text, after mhx_pointwise_kernels.h, whose draw and row views and whose frame
-// (lane = chain, strips of draws dealt to strip slots, tiles of R data rows) the two sweeps share.  l is evaluated in the run's width
-// and keyed in that width (the map of mhx_order_key, restated: this module does not carry the diagnostics header); everything after
-// the widening is fp64 in both widths, with mhx_exp_f64 / mhx_log_f64.
+// (lane = chain, strips of draws dealt to strip slots, tiles of R data rows: mhx_pointwise_sweep) and block reduction
+// (mhx_block_partials) the two sweeps share.  l is evaluated in the run's width and keyed in that width (mhx_order_key); everything
+// after the widening is fp64 in both widths, with mhx_exp_f64 / mhx_log_f64.
 //
 // Order of operations.  The histograms are integer sums (LDS and global atomics: independent of arrival).  B', n_eq and bad are reduced
 // as the pointwise partials are: butterfly over the wave, LDS in wave order, per-block partials merged in index order.  Every sum of the
@@ -31,34 +31,6 @@
 
 #if defined(MHX_HAVE_POINTWISE) && defined(MHX_HAVE_PSIS)
 MHX_NS_BEGIN
-
-#if MHX_REAL64
-typedef unsigned long long mhx_psis_key_t;
-#define MHX_PSIS_KEY_BITS 64
-MHX_DEV mhx_psis_key_t mhx_psis_key(const double x)
-{
-    const mhx_psis_key_t b = (mhx_psis_key_t)__builtin_bit_cast(long long, x);
-    if (x != x) return ~0ull;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-MHX_DEV double mhx_psis_key_value(const mhx_psis_key_t k)
-{
-    return __builtin_bit_cast(double, (k >> 63) ? (k ^ 0x8000000000000000ull) : ~k);
-}
-#else
-typedef unsigned int mhx_psis_key_t;
-#define MHX_PSIS_KEY_BITS 32
-MHX_DEV mhx_psis_key_t mhx_psis_key(const float x)
-{
-    const mhx_psis_key_t b = __builtin_bit_cast(unsigned int, x);
-    if (x != x) return ~0u;
-    return (b >> 31) ? ~b : (b | 0x80000000u);
-}
-MHX_DEV double mhx_psis_key_value(const mhx_psis_key_t k)
-{
-    return (double)__builtin_bit_cast(float, (k >> 31) ? (k ^ 0x80000000u) : ~k);
-}
-#endif
 
 // log(1 + y) and exp(y) - 1 in fp64 from the engine's log and exp (Kahan's forms: the rounding of 1 + y, or of exp(y), is divided out)
 MHX_DEV double mhx_log1p_f64(const double y)
@@ -98,37 +70,18 @@ mhx_jit_psis_hist(const mhx_real* __restrict__ src, const long N, const long C, 
     __shared__ unsigned lds[R << MHX_PSIS_MAX_DIGIT_BITS];
     const int nb = 1 << digit_bits;
     for (int k = threadIdx.x; k < R * nb; k += MHX_POINTWISE_THREADS) lds[k] = 0u;
-    const long c0 = (long)blockIdx.x * MHX_POINTWISE_THREADS;
-    const bool active = c0 + (long)threadIdx.x < C;
     const int i0 = (int)blockIdx.z * R;
-    mhx_psis_key_t pf[R];
+    mhx_key pf[R];
 #pragma unroll
-    for (int j = 0; j < R; ++j) pf[j] = (mhx_psis_key_t)prefixes[i0 + j < nrows ? i0 + j : nrows - 1];
-    const mhx_psis_key_t dmask = (mhx_psis_key_t)(nb - 1);
+    for (int j = 0; j < R; ++j) pf[j] = (mhx_key)prefixes[i0 + j < nrows ? i0 + j : nrows - 1];
+    const mhx_key dmask = (mhx_key)(nb - 1);
     const int hshift = top ? 0 : shift + digit_bits;            // top: shift + digit_bits is the key width, not a legal shift count
     __syncthreads();
-    if (active) {
-        long ld = C;
-        mhx_u32 l = (mhx_u32)threadIdx.x * MHX_RB;
-        asm volatile("" : "+s"(ld), "+v"(l));
-        const long nstrips = (N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
-        for (long s = blockIdx.y; s < nstrips; s += gridDim.y) {
-            const long t0 = s * MHX_POINTWISE_STRIP;
-            const long end = t0 + MHX_POINTWISE_STRIP < N ? t0 + MHX_POINTWISE_STRIP : N;
-            for (long t = t0; t < end; ++t) {
-                const mhx_pointwise_in x = {src + t * (long)(d + 1) * ld + c0, ld, d, l};
-#pragma unroll
-                for (int j = 0; j < R; ++j) {
-                    if (i0 + j < nrows) {                       // uniform over the block
-                        const mhx_pointwise_row r = {rows + (long)(i0 + j) * rowlen, rowlen};
-                        const mhx_psis_key_t key = mhx_psis_key(mhx_user_pointwise(x, r, rowlen, d, data, ndata));
-                        const unsigned digit = (unsigned)((key >> shift) & dmask);
-                        if (top || (mhx_psis_key_t)(key >> hshift) == pf[j]) atomicAdd(&lds[j * nb + (int)digit], 1u);
-                    }
-                }
-            }
-        }
-    }
+    mhx_pointwise_sweep<R, true>(src, N, C, d, rows, nrows, rowlen, data, ndata, [&](const int j, const mhx_real v) {
+        const mhx_key key = mhx_order_key(v);
+        const unsigned digit = (unsigned)((key >> shift) & dmask);
+        if (top || (mhx_key)(key >> hshift) == pf[j]) atomicAdd(&lds[j * nb + (int)digit], 1u);
+    });
     __syncthreads();
     for (int k = threadIdx.x; k < R * nb; k += MHX_POINTWISE_THREADS) {
         const unsigned v = lds[k];
@@ -145,73 +98,41 @@ extern "C" __global__ void __launch_bounds__(MHX_POINTWISE_THREADS)
 mhx_jit_psis_gather(const mhx_real* __restrict__ src, const long N, const long C, const int d, const mhx_real* __restrict__ rows,
                     const int nrows, const int rowlen, const mhx_real* __restrict__ data, const int ndata,
                     const unsigned long long* __restrict__ tau_key, const double* __restrict__ tau, const unsigned long long cap,
-                    unsigned long long* __restrict__ cursor, mhx_psis_key_t* __restrict__ tails, double* __restrict__ part)
+                    unsigned long long* __restrict__ cursor, mhx_key* __restrict__ tails, double* __restrict__ part)
 {
     constexpr int R = MHX_JIT_PSIS_ROWS;
-    __shared__ double lds[MHX_POINTWISE_THREADS / 64][R][3];
-    const long c0 = (long)blockIdx.x * MHX_POINTWISE_THREADS;
-    const bool active = c0 + (long)threadIdx.x < C;
     const int i0 = (int)blockIdx.z * R;
-    mhx_psis_key_t tk[R];
+    mhx_key tk[R];
     double tv[R], body[R];
     mhx_u32 neq[R], bad[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) {
         const int i = i0 + j < nrows ? i0 + j : nrows - 1;
-        tk[j] = (mhx_psis_key_t)tau_key[i];
+        tk[j] = (mhx_key)tau_key[i];
         tv[j] = tau[i];
         body[j] = 0.0;
         neq[j] = bad[j] = 0u;
     }
-    if (active) {
-        long ld = C;
-        mhx_u32 l = (mhx_u32)threadIdx.x * MHX_RB;
-        asm volatile("" : "+s"(ld), "+v"(l));
-        const long nstrips = (N + MHX_POINTWISE_STRIP - 1) / MHX_POINTWISE_STRIP;
-        for (long s = blockIdx.y; s < nstrips; s += gridDim.y) {
-            const long t0 = s * MHX_POINTWISE_STRIP;
-            const long end = t0 + MHX_POINTWISE_STRIP < N ? t0 + MHX_POINTWISE_STRIP : N;
-            for (long t = t0; t < end; ++t) {
-                const mhx_pointwise_in x = {src + t * (long)(d + 1) * ld + c0, ld, d, l};
-#pragma unroll
-                for (int j = 0; j < R; ++j) {
-                    if (i0 + j < nrows) {
-                        const mhx_pointwise_row r = {rows + (long)(i0 + j) * rowlen, rowlen};
-                        const mhx_real v = mhx_user_pointwise(x, r, rowlen, d, data, ndata);
-                        const double lv = (double)v;
-                        if (!(__builtin_fabs(lv) < __builtin_inf())) {
-                            bad[j] += 1u;
-                        } else {
-                            const mhx_psis_key_t key = mhx_psis_key(v);
-                            if (key < tk[j]) {
-                                const unsigned long long pos = atomicAdd(&cursor[i0 + j], 1ull);
-                                if (pos < cap) tails[(unsigned long long)(i0 + j) * cap + pos] = key;
-                            } else if (key == tk[j]) {
-                                neq[j] += 1u;
-                            } else {
-                                body[j] = body[j] + mhx_exp_f64(tv[j] - lv);
-                            }
-                        }
-                    }
-                }
+    mhx_pointwise_sweep<R, true>(src, N, C, d, rows, nrows, rowlen, data, ndata, [&](const int j, const mhx_real v) {
+        const double lv = (double)v;
+        if (!(__builtin_fabs(lv) < __builtin_inf())) {
+            bad[j] += 1u;
+        } else {
+            const mhx_key key = mhx_order_key(v);
+            if (key < tk[j]) {
+                const unsigned long long pos = atomicAdd(&cursor[i0 + j], 1ull);
+                if (pos < cap) tails[(unsigned long long)(i0 + j) * cap + pos] = key;
+            } else if (key == tk[j]) {
+                neq[j] += 1u;
+            } else {
+                body[j] = body[j] + mhx_exp_f64(tv[j] - lv);
             }
         }
-    }
-    const int wave = (int)threadIdx.x >> 6;
+    });
+    double v[R][3];
 #pragma unroll
-    for (int j = 0; j < R; ++j) {
-        const double b = mhx_psis_wave_sum(body[j]), e = mhx_psis_wave_sum((double)neq[j]), n = mhx_psis_wave_sum((double)bad[j]);
-        if ((threadIdx.x & 63u) == 0u) { lds[wave][j][0] = b; lds[wave][j][1] = e; lds[wave][j][2] = n; }
-    }
-    __syncthreads();
-    const int j = (int)threadIdx.x;
-    if (j < R && i0 + j < nrows) {
-        double b = lds[0][j][0], e = lds[0][j][1], n = lds[0][j][2];
-        for (int w = 1; w < MHX_POINTWISE_THREADS / 64; ++w) { b = b + lds[w][j][0]; e = e + lds[w][j][1]; n = n + lds[w][j][2]; }
-        const long p = (long)blockIdx.x * gridDim.y + blockIdx.y;
-        double* o = part + (p * (long)nrows + (i0 + j)) * 3;
-        o[0] = b; o[1] = e; o[2] = n;
-    }
+    for (int j = 0; j < R; ++j) { v[j][0] = body[j]; v[j][1] = (double)neq[j]; v[j][2] = (double)bad[j]; }
+    mhx_block_partials(v, mhx_merge_sums{}, nrows, part);
 }
 
 // ---- 4. fit and sums --------------------------------------------------------------------------------------------------------------
@@ -228,7 +149,7 @@ MHX_DEV double mhx_psis_wave_strided(const unsigned long long n, const F& f)
 // wrote it; xbuf [nrows][cap] doubles of scratch; out [8][nrows]: elpd_loo, khat, sigma, tau, lmin, body, n_below, bad;
 // tail_out [nrows][M] the tail ascending, copies of tau included.  M = cap.
 extern "C" __global__ void __launch_bounds__(MHX_PSIS_FIT_THREADS)
-mhx_jit_psis_fit(const mhx_psis_key_t* __restrict__ sorted, const unsigned long long* __restrict__ count, const double* __restrict__ tau,
+mhx_jit_psis_fit(const mhx_key* __restrict__ sorted, const unsigned long long* __restrict__ count, const double* __restrict__ tau,
                  const double* __restrict__ part, const long P, const int nrows, const unsigned long long M, const double T,
                  double* xbuf, double* __restrict__ out, double* tail_out)
 {
@@ -258,14 +179,14 @@ mhx_jit_psis_fit(const mhx_psis_key_t* __restrict__ sorted, const unsigned long 
     const double tv = tau[i];
     unsigned long long nbelow = count[i];
     if (nbelow > M) nbelow = M;
-    const mhx_psis_key_t* keys = sorted + (unsigned long long)i * M;
-    const double lmin = nbelow ? mhx_psis_key_value(keys[0]) : tv;
+    const mhx_key* keys = sorted + (unsigned long long)i * M;
+    const double lmin = nbelow ? mhx_key_value(keys[0]) : tv;
     const double ecut = mhx_exp_f64(lmin - tv);
     const double B = bsum + (neq - (double)(M - nbelow));
     double* x = xbuf + (unsigned long long)i * M;
     // the tail ascending (a[j], j < M) and the abscissae ascending: x[j] belongs to a[M - 1 - j]
     for (unsigned long long j = tid; j < M; j += MHX_PSIS_FIT_THREADS) {
-        const double a = j < nbelow ? mhx_psis_key_value(keys[j]) : tv;
+        const double a = j < nbelow ? mhx_key_value(keys[j]) : tv;
         tl[j] = a;
         x[M - 1 - j] = mhx_exp_f64(lmin - a) - ecut;
     }

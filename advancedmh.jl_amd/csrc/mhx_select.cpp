@@ -8,10 +8,21 @@
 #include <cstring>
 #include <vector>
 
-namespace {
+uint64_t mhx_select_key_of(double v, int keybits)
+{
+    if (v != v) return ~0ull;
+    if (keybits == 64) {
+        uint64_t b;
+        memcpy(&b, &v, sizeof b);
+        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    }
+    const float f = (float)v;
+    uint32_t b;
+    memcpy(&b, &f, sizeof b);
+    return (uint64_t)((b >> 31) ? ~b : (b | 0x80000000u));
+}
 
-// the inverse of the key map of mhx_order_key (mhx_diag_kernels.h); the all-ones key stands for every NaN
-double key_to_double(uint64_t k, int keybits)
+double mhx_select_key_value(uint64_t k, int keybits)
 {
     if (keybits == 64) {
         if (k == ~0ull) return std::nan("");
@@ -27,8 +38,6 @@ double key_to_double(uint64_t k, int keybits)
     memcpy(&x, &b, sizeof x);
     return (double)x;                                      // exact
 }
-
-}  // namespace
 
 size_t mhx_select_hist_words(int digit, int32_t nparams, int32_t nranks)
 {
@@ -97,7 +106,7 @@ int mhx_select_drive(const char* who, int keybits, int digit, int32_t nparams, c
         // after the last digit the prefix is the key
         for (int32_t p = 0; p < nparams; ++p)
             for (int k = 0; k < nt; ++k)
-                res[(size_t)p * T + b0 + k] = key_to_double(prefix[(size_t)p * gstride + grp[(size_t)p * gstride + k]], keybits);
+                res[(size_t)p * T + b0 + k] = mhx_select_key_value(prefix[(size_t)p * gstride + grp[(size_t)p * gstride + k]], keybits);
     }
     for (int32_t p = 0; p < nparams; ++p)
         for (int32_t j = 0; j < nranks; ++j) {

@@ -27,5 +27,10 @@ typedef int (*mhx_select_hist_fn)(void* user, const uint64_t* prefixes, const in
 // a context keeps a page-locked one from call to call; NULL or too small: pageable memory of the call.
 int mhx_select_drive(const char* who, int keybits, int digit, int32_t nparams, const int64_t* ranks, int32_t nranks, uint64_t S,
                      mhx_select_hist_fn fn, void* user, double* out, uint64_t* landing, size_t landing_words);
+// The key map of the device (mhx_order_key / mhx_key_value, mhx_device_math.h) on the host, for keys of `keybits` = 32 or 64 bits:
+// the key of a value the select returned (a draw of that width, widened: the narrowing is exact), and the value of a key, where the
+// all-ones key stands for every NaN.
+uint64_t mhx_select_key_of(double v, int keybits);
+double mhx_select_key_value(uint64_t k, int keybits);
 // an upper bound of the words of `hist` a call with these arguments needs (0: the arguments are refused)
 size_t mhx_select_hist_words(int digit, int32_t nparams, int32_t nranks);

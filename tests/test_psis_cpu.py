@@ -183,8 +183,13 @@ def test_the_module_compiles_for_gfx950_behind_a_traced_function(tmp_path, real)
     assert os.path.exists(hipcc), "hipcc not found: the build needs it too"
     tp = T.trace_pointwise(normal_ll, 2, [0.5, 1.5, -2.0], names=["mu", "sigma"])
     inc = open(os.path.join(CSRC, "mhx_api_psis.inc")).read()
+    api = open(os.path.join(CSRC, "mhx_api.hip")).read()
     tail = '#define MHX_HAVE_POINTWISE 1\n#include "mhx_pointwise_kernels.h"\n#define MHX_HAVE_PSIS 1\n#include "mhx_psis_kernels.h"\n'
-    assert tail.replace("\n", "\\n").replace('"', '\\"') in inc                  # what psis_source appends
+    # what user_module appends for psis_checked: its frames in this order, each as "#define <have> 1\n#include \"<header>\"\n"
+    assert '{{"MHX_HAVE_POINTWISE", "mhx_pointwise_kernels.h"}, {"MHX_HAVE_PSIS", "mhx_psis_kernels.h"}}' in inc
+    frame = api[api.index("for (const user_frame& f : frames) {"):]
+    frame = "".join(re.findall(r's \+= (.*);', frame[:frame.index("}")]))
+    assert frame == '"#define "f.have" 1\\n#include \\""f.header"\\"\\n"', frame
     src = tmp_path / "psis.hip"
     src.write_text('#include "mhx_device_math.h"\n#line 1 "pointwise.hip"\n' + tp.source + "\n" + tail)
     out = tmp_path / "k.s"
@@ -224,6 +229,8 @@ def test_entry_points_are_declared_exported_and_guarded(mhx):
     spec.loader.exec_module(eh)
     assert "mhx_psis_kernels.h" in eh.HEADERS
     inc = open(os.path.join(CSRC, "mhx_api_psis.inc")).read()
+    assert "row_blocks_checked(v, nrows, rowlen, data, ndata)" in inc            # the refusals of the rows and the data block: mhx_api.hip
+    inc += open(os.path.join(CSRC, "mhx_api.hip")).read()
     for guard in ("NULL argument", "at least one row of at least one real", "rows are indexed in 31 bits", "reff = %g is not a positive finite number",
                   "PSIS_SCRATCH_MB"):
         assert guard in inc, guard
