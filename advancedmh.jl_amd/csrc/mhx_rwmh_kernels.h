@@ -423,6 +423,19 @@ MHX_DEV void mhx_rwmh_whiten_body(const mhx_rwmh_args& a, const mhx_real* __rest
 #ifndef MHX_ZIG_FIX2
 #define MHX_ZIG_FIX2 1
 #endif
+// MHX_GEN_SHARE_LAST = 1: where lane-half 1's last block is padding altogether (two lanes per chain, d <= 4 (2 (NBL - 1) + 1): C2's
+// d = 100) the generator wave's lane-halves share the two Philox calls of lane-half 0's last block, one call per lane; 0: two calls
+// per lane, one block thrown away.  Same chains bit for bit either way; measured at C2 in profiles/gen_wide/README.md (DESIGN.md
+// section 6.7 #38).
+#ifndef MHX_GEN_SHARE_LAST
+#define MHX_GEN_SHARE_LAST 1
+#endif
+template <bool V> struct mhx_gen_share { static constexpr bool value = V; };     // (which of the generator's two step loops)
+// the value that lane + 32 holds, in lanes 0-31 (lanes 32-63 keep their own): one v_permlane32_swap
+MHX_DEV mhx_u32 mhx_upper_half(const mhx_u32 v)
+{
+    return __builtin_amdgcn_permlane32_swap(v, v, false, false)[1];
+}
 #endif
 // where slot sl (= 4 i + j: block i of the lane, normal j of the block) of lane `ln` lives in a step's slab of normals
 #if MHX_REAL64
@@ -1480,12 +1493,20 @@ MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __
         const mhx_u64 id = a.first_chain + (mhx_u64)(gc_raw < a.nchains ? gc_raw : (long)a.nchains - 1);
         const mhx_u32 id_lo = (mhx_u32)id, id_hi = (mhx_u32)(id >> 32);
         const int k_last = 4 * (l + L * (NBL - 1));
+        constexpr bool ZADDC = (MHX_ZADDC == 2 || (MHX_ZADDC == 1 && NBL > 4)) && NBL <= 16;
+        // MHX_GEN_SHARE_LAST: with two lanes per chain and d <= 4 (L (NBL - 1) + 1) lane-half 1's last block is padding altogether, and
+        // the two Philox calls of lane-half 0's last block are shared between the halves, one call per lane.  Wave-uniform and decided
+        // ahead of the step loop, which exists ONCE PER ANSWER: with the test inside one loop, at the two places that differ, the
+        // branches cut the last two blocks out of the loop's one scheduling region and the kernel was 2.7 % slower than without the
+        // sharing (profiles/gen_wide/README.md).  Either loop executes the two barriers per step.
+        constexpr bool SHARE_OK = MHX_GEN_SHARE_LAST != 0 && L == 2 && NBL > 1 && ZADDC;
+        auto gen_steps = [&](auto share_is) __attribute__((always_inline)) {
+        constexpr bool share = decltype(share_is)::value;
 #pragma unroll 1
         for (int it = 0; it < a.nsteps; ++it) {
             const mhx_u32 step = a.step0 + (mhx_u32)it;
             // phase A of the body above, one step: every slot's candidate by the fast path into the pair's slab, the failures noted
             mhx_u64 fm = 0ull;
-            constexpr bool ZADDC = (MHX_ZADDC == 2 || (MHX_ZADDC == 1 && NBL > 4)) && NBL <= 16;
             mhx_u32 m4[4] = {0u, 0u, 0u, 0u};
             mhx_u32 khi[4], klo[4];                                 // the candidates' raw words (hi:lo) of the block in flight
             auto draw = [&](const int i, mhx_u32 (&hi)[4], mhx_u32 (&lo)[4]) {
@@ -1495,11 +1516,46 @@ MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __
                 hi[0] = w0.x; lo[0] = w0.y; hi[1] = w0.z; lo[1] = w0.w;
                 hi[2] = w1.x; lo[2] = w1.y; hi[3] = w1.z; lo[3] = w1.w;
             };
+            // the shared last block: lane-half l draws call l of block L (NBL - 1), the owner's (lane-half 0's) candidates 2 l, 2 l + 1
+            auto draw_shared = [&](mhx_u32 (&hi)[4], mhx_u32 (&lo)[4]) {
+                const mhx_u32x4 w = mhx_philox(ks, id_lo, id_hi, step, (MHX_STREAM_PROPOSAL << 28) | (mhx_u32)(2 * L * (NBL - 1) + l));
+                hi[0] = w.x; lo[0] = w.y; hi[1] = w.z; lo[1] = w.w;
+                hi[2] = 0u; lo[2] = 0u; hi[3] = 0u; lo[3] = 0u;
+            };
             draw(0, khi, klo);
             mhx_u32 zsign = 0x80000000u;                            // (opaque: see mhx_zig_signed)
             asm volatile("" : "+s"(zsign));
 #pragma unroll
             for (int i = 0; i < NBL; ++i) {
+                if (share && i == NBL - 1) {
+                    // ---- the shared last block (MHX_GEN_SHARE_LAST): two look-ups and two fast paths per lane, the pair of lane-half
+                    // l into row 2 i + l of the slab at the OWNER's column.  Lane-half 1's own slots (all padding) stay unwritten: the
+                    // consumer assigns 0 to them before use, and their failure bits are cleared with the padding below.
+                    const int own = lane & (CPW - 1);
+                    mhx_d2 xs[2];
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const mhx_u32 ly = klo[e] & (mhx_u32)(MHX_ZIG_N - 1);
+                        xs[e].x = zt[ly]; xs[e].y = zt[ly + 1];
+                    }
+                    mhx_d2 v2;
+                    {
+                        const int lane = own;                       // (what MHX_ZIG_FORCE_FAIL reads: the candidate's owner and its slot there)
+                        const double ax0 = mhx_zig_ax(khi[0], klo[0], xs[0].x);
+                        v2.x = mhx_zig_signed(ax0, klo[0], zsign);
+                        MHX_ZIG_NOTE64(m4[0], ax0, xs[0].y, 4 * i + 2 * l + 0);
+                        const double ax1 = mhx_zig_ax(khi[1], klo[1], xs[1].x);
+                        v2.y = mhx_zig_signed(ax1, klo[1], zsign);
+                        MHX_ZIG_NOTE64(m4[1], ax1, xs[1].y, 4 * i + 2 * l + 1);
+                        (void)lane;
+                    }
+                    // lane-half 1's two notes belong to the owner's slots 4 i + 2 and 4 i + 3: across the halves by one swap each
+                    const mhx_u32 f2 = mhx_upper_half(m4[0]) & 1u, f3 = mhx_upper_half(m4[1]) & 1u;
+                    m4[2] = (m4[2] << 1) | f2;
+                    m4[3] = (m4[3] << 1) | f3;
+                    *(mhx_d2*)(zn0 + (((i * 2 + l) * 64 + own) << 1)) = v2;
+                    continue;
+                }
                 mhx_d2 xe[4];                                       // x[layer], x[layer + 1] of the block's candidates
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -1508,14 +1564,22 @@ MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 mhx_u32 nhi[4], nlo[4];
-                if (i + 1 < NBL) draw(i + 1, nhi, nlo);
+                if (i + 1 < NBL) {
+                    if (share && i + 1 == NBL - 1) draw_shared(nhi, nlo);
+                    else draw(i + 1, nhi, nlo);
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 double nn[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const double ax = mhx_zig_ax(khi[j], klo[j], xe[j].x);
+                    // (sign, then note: in this order hipcc keeps ax for the note and moves the signed word into the store's registers,
+                    // two v_mov_b32 per store; with the note first it does not.  Measured, profiles/gen_wide/README.md: the shared loop
+                    // is faster WITH the moves, the other loop without them)
+                    if (ZADDC && !share) MHX_ZIG_NOTE64(m4[j], ax, xe[j].y, 4 * i + j);
                     nn[j] = mhx_zig_signed(ax, klo[j], zsign);
-                    if (ZADDC) { MHX_ZIG_NOTE64(m4[j], ax, xe[j].y, 4 * i + j); continue; }
+                    if (ZADDC && share) MHX_ZIG_NOTE64(m4[j], ax, xe[j].y, 4 * i + j);
+                    if (ZADDC) continue;
                     bool fail = !(ax < xe[j].y);
 #ifdef MHX_TOOLS_BUILD
 #ifdef MHX_ZIG_FORCE_FAIL
@@ -1556,6 +1620,9 @@ MHX_DEV void mhx_rwmh_coop_pairs_body(const mhx_rwmh_args& a, const mhx_real* __
                                                     MHX_STREAM_PROPOSAL, true, fm, ZADDC ? NBL - 1 : -1);
             __syncthreads();                     // the slab holds the step's normals, final
         }
+        };
+        if (SHARE_OK && a.dim <= 4 * (L * (NBL - 1) + 1)) gen_steps(mhx_gen_share<SHARE_OK>{});
+        else gen_steps(mhx_gen_share<false>{});
         if (a.nsteps > 0) __syncthreads();       // the second barrier of the last step
         return;                                  // (after the loop: every barrier of the block has been executed)
     }

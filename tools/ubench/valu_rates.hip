@@ -88,6 +88,34 @@ __global__ void __launch_bounds__(64) k_mad_u64(unsigned long long* out, unsigne
     if (threadIdx.x == 0) out[blockIdx.x] = t1 - t0;
 }
 
+// The Philox round's dependent pair: v_mad_u64_u32 -> v_bitop3_b32 (reads both halves of the product) -> the next v_mad_u64_u32
+// (reads the bitop3's result), as NCH independent chains issued side by side: 1 = the bare latency of the pair, 8 = what the rows
+// above time.  32 pairs per turn of the inner loop whatever NCH: 64 instructions, as many as the KERNEL rows' 2 x 32.
+template <int NCH>
+__global__ void __launch_bounds__(64) k_mad_bitop_dep(unsigned long long* out, unsigned seed)
+{
+    unsigned a[NCH];
+    for (int j = 0; j < NCH; ++j) a[j] = seed + j + threadIdx.x;
+    unsigned long long t0 = __builtin_readcyclecounter();
+    for (int i = 0; i < ITERS; ++i) {
+#pragma unroll
+        for (int r = 0; r < 32 / NCH; ++r) {
+            unsigned long long p[NCH];
+#pragma unroll
+            for (int j = 0; j < NCH; ++j)
+                asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(p[j]) : "v"(a[j]), "s"(0xD2511F53u) : "vcc");
+#pragma unroll
+            for (int j = 0; j < NCH; ++j)
+                asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(a[j]) : "v"((unsigned)(p[j] >> 32)), "v"((unsigned)p[j]), "s"(seed));
+        }
+    }
+    unsigned long long t1 = __builtin_readcyclecounter();
+    unsigned x = 0;
+    for (int j = 0; j < NCH; ++j) x ^= a[j];
+    if (x == 12345u) out[1000000] = 1;
+    if (threadIdx.x == 0) out[blockIdx.x] = t1 - t0;
+}
+
 // packed fp32
 typedef float float2v __attribute__((ext_vector_type(2)));
 __global__ void __launch_bounds__(64) k_pk_fma(unsigned long long* out, unsigned seed)
@@ -142,6 +170,10 @@ int main()
         run("v_mul_hi_u32", k_mul_hi, nb, d_out);
         run("v_mul_u32_u24", k_mul_u24, nb, d_out);
         run("mad_u64+xor", k_mad_u64, nb, d_out);
+        run("mad>bitop3 x1", k_mad_bitop_dep<1>, nb, d_out, 2.0);       // per instruction of the dependent pair, 1 / 2 / 4 / 8 chains
+        run("mad>bitop3 x2", k_mad_bitop_dep<2>, nb, d_out, 2.0);
+        run("mad>bitop3 x4", k_mad_bitop_dep<4>, nb, d_out, 2.0);
+        run("mad>bitop3 x8", k_mad_bitop_dep<8>, nb, d_out, 2.0);
         run("v_fma_f64", k_fma64, nb, d_out);
         run("v_mul_f64", k_mul64, nb, d_out);
         run("v_add_f64", k_add64, nb, d_out);
