@@ -1,0 +1,15 @@
+// the parallel-tempering entries of the C ABI (included at the end of mhx_abi.cpp; engine side: mhx_api_tempered.inc).  Like the
+// pointwise entries they were never part of the hand-written dispatcher whose all-zero answers tests/golden/abi_null_contract.json
+// records, so they stand apart from the 73 entries of that record; tests/test_tempered_cpu.py pins their guards.
+extern "C" {
+
+int mhx_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tcfg, mhx_run** out)
+{
+    NEED_SAME(rwmh_create_tempered, ctx, t, cfg, tcfg, out);
+}
+
+int mhx_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps) { NEED_SAMPLER(run_swap_stats, r, attempts, swaps); }
+
+int mhx_run_rung(mhx_run* r, int32_t rung, mhx_run** out) { NEED(run_rung, r, rung, out); }
+
+}

@@ -29,6 +29,7 @@
 #include "mhx_rwmh_family_kernels.h"
 #include "mhx_rwmh_cond_kernels.h"
 #include "mhx_rwmh_composite_kernels.h"
+#include "mhx_rwmh_tempered_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
 #include "mhx_mala_kernels.h"
@@ -509,12 +510,12 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
                              k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
                              k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h, k_src_mhx_derive_kernels_h,
-                             k_src_mhx_pointwise_kernels_h, k_src_mhx_psis_kernels_h};
+                             k_src_mhx_pointwise_kernels_h, k_src_mhx_psis_kernels_h, k_src_mhx_rwmh_tempered_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
                               "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h", "mhx_derive_kernels.h",
-                              "mhx_pointwise_kernels.h", "mhx_psis_kernels.h"};
+                              "mhx_pointwise_kernels.h", "mhx_psis_kernels.h", "mhx_rwmh_tempered_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -852,6 +853,7 @@ enum kernel_form {
     KF_FAMILY = 13,         // a proposal of univariate family components: specialised register form or state in HBM
     KF_COND = 14,           // ... whose parameters are a function of the state (a conditional proposal): the same two forms
     KF_COMPOSITE = 15,      // ... and whose kind, symmetric flag and parameter map vary per block of components (a composite proposal)
+    KF_TEMPERED = 16,       // parallel tempering of the plain random walk: specialised register form or state in HBM (mhx_api_tempered.inc)
 };
 
 // One kernel of a run, ready to launch: everything the host needs for it, filled ONCE, in the branch of a create function that
@@ -938,6 +940,11 @@ struct mhx_run : mhx_handle_hdr {
     int* d_cmp_tab = nullptr;               // {kind bit, mapped mask} per component, then {first, count, flags} per block
     int cmp_nblocks = 0;
     bool cmp_mapped = false;                // some parameter is mapped: the first state must be given
+    // KF_TEMPERED (mhx_api_tempered.inc): fam_reg as above, and
+    int tmp_R = 0;                          // rungs per ladder (0: not a tempered run)
+    int tmp_swap_every = 0;                 // a swap round after every so many transitions (0: none)
+    mhx_real* d_ttab = nullptr;             // beta[R] | dbeta[R] | sig[R] or sig[R][dim]
+    uint32_t* d_swapc = nullptr;            // [2][n] swap attempts, swaps of pair (r, r + 1), kept by the lower slot
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -1014,7 +1021,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (acc_total_pin) (void)hipHostFree(acc_total_pin);
     }
@@ -1662,6 +1669,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
         int rcz = rwmh_canonical_zero(r);
         if (rcz) return rcz;
     }
+    if (r->d_swapc) HIP_TRY(hipMemsetAsync(r->d_swapc, 0, 2 * (size_t)r->n * sizeof(uint32_t), ctx->stream));      // a tempered run: its swap counts begin here
     mhx_rwmh_args a = rwmh_args(r);
     const mhx_real* tp = r->target->dparams;
     const mhx_real* pv = r->d_pvec;
@@ -1817,6 +1825,8 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
     r->rec_loga_view = nullptr;
     if (save_samples == MHX_SAVE_MOMENTS) {
         // running moments instead of a sample tensor
+        if (r->tmp_R)
+            return mhx_fail(MHX_ESTATE, "mhx_run_sample: running moments (MHX_SAVE_MOMENTS) are not kept by a tempered run: record samples");
         if (r->kind == RUN_RWMH && r->variant == KF_COMPOSITE)
             return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run with a composite proposal "
                                     "(kernel variant 15): record samples");
@@ -2019,6 +2029,7 @@ static std::vector<ckpt_part> ckpt_parts(mhx_run* r)
 int api_run_state_size(mhx_run* r, size_t* bytes)
 {
     if (!r || !bytes) return mhx_fail(MHX_EINVAL, "mhx_run_state_size: NULL argument");
+    if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_state_size: a tempered run has no checkpoint / resume");
     size_t total = sizeof(ckpt_header);
     for (const auto& p : ckpt_parts(r)) total += p.bytes;
     *bytes = total;
@@ -2027,6 +2038,7 @@ int api_run_state_size(mhx_run* r, size_t* bytes)
 int api_run_save_state(mhx_run* r, void* blob, size_t bytes)
 {
     if (!r || !blob) return mhx_fail(MHX_EINVAL, "mhx_run_save_state: NULL argument");
+    if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_save_state: a tempered run has no checkpoint / resume");
     if (!r->initialised) return mhx_fail(MHX_ESTATE, "mhx_run_save_state: run is not initialised");
     size_t need = 0;
     api_run_state_size(r, &need);
@@ -2048,6 +2060,7 @@ int api_run_save_state(mhx_run* r, void* blob, size_t bytes)
 int api_run_load_state(mhx_run* r, const void* blob, size_t bytes)
 {
     if (!r || !blob) return mhx_fail(MHX_EINVAL, "mhx_run_load_state: NULL argument");
+    if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_load_state: a tempered run has no checkpoint / resume");
     size_t need = 0;
     api_run_state_size(r, &need);
     ckpt_header h;
@@ -2108,6 +2121,7 @@ const char* api_run_form_name(const mhx_run* r)
     case KF_EMCEE_MFMA: return "emcee_mfma";
     case KF_WAVE: return "wave";
     case KF_RAM_DEFER: return "ram_defer";
+    case KF_TEMPERED: return r->fam_reg ? "tempered_reg" : "tempered_generic";
     case KF_FAMILY: return "family";
     case KF_COND: return "cond";
     case KF_COMPOSITE: return "composite";
@@ -2313,6 +2327,7 @@ static sweep_plan pointwise_sweep_plan(const draws_view& v, long ntiles)
 #include "mhx_api_hist.inc"
 #include "mhx_api_acf.inc"
 #include "mhx_api_derive.inc"
+#include "mhx_api_tempered.inc"
 #include "mhx_api_pointwise.inc"
 #include "mhx_api_psis.inc"
 

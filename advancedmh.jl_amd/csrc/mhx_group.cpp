@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -210,6 +211,8 @@ extern "C" int mhx_group_attach(mhx_group* g, mhx_run* const* runs)
     std::vector<int> dims(n), cnt(n);
     for (int i = 0; i < n; ++i) {
         if (!runs[i]) return mhx_fail(MHX_EINVAL, "mhx_group_attach: run %d is NULL", i);
+        if (!strncmp(mhx_run_form_name(runs[i]), "tempered", 8))
+            return mhx_fail(MHX_ESTATE, "mhx_group_attach: run %d is a tempered run, which a group does not drive (no Group twin of the swap statistics and the rung snapshot)", i);
         int32_t d = 0, c = 0;
         const int rc = mhx_run_shape(runs[i], &d, &c);
         if (rc) return rc;

@@ -137,6 +137,10 @@ void mhx_jit_unlock();
                      const char* source, const REAL* rows, int64_t nrows, int32_t rowlen, const REAL* data,            \
                      size_t ndata, double reff, double* out8, double* tail_out, int64_t* T, int64_t* M);               \
     bool api_run_is_derived(const mhx_run* r);                                                                         \
+    int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                          \
+                                 const mhx_tempered_cfg* tcfg, mhx_run** out);                                        \
+    int api_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps);                                          \
+    int api_run_rung(mhx_run* src, int32_t rung, mhx_run** out);                                                      \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \
     int api_emcee_device_state(mhx_run* r, REAL** xw, int32_t* pitch, REAL** lp, uint32_t** acc_count,                 \

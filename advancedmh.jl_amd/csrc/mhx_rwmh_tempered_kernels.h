@@ -1,0 +1,361 @@
+// mhx_rwmh_tempered_kernels.h -- parallel tempering (replica exchange) of random-walk Metropolis-Hastings, one lane per chain.
+//
+// A run is `nladders` ladders of R rungs: chain c is rung r = c mod R of ladder c div R and samples pi^beta[r]
+// with its own proposal scale; beta[0] = 1 is the chain that is read.  R is a power of two <= 64 and the first chain's id a multiple
+// of R, so a ladder is R consecutive lanes of ONE wave and neighbouring temperatures exchange their states across lanes, inside the
+// step kernel: no second kernel, no trip through memory, nothing to wait for but the wave itself.
+//
+//   transition    y = fma(sig[r], n, x) as the plain lane-per-chain kernels form it, accept iff logu < beta[r] * (lpy - lp)
+//   swap round    after the accept / reject of every transition `step` with step % swap_every == 0; round s = step / swap_every (the
+//                 GLOBAL step: a run advanced in two calls is the run advanced in one); pairs (r, r + 1) with r = s (mod 2); one
+//                 Philox block per pair, keyed by the LOWER slot's chain id, step word s, stream MHX_STREAM_SWAP; swap iff
+//                 logu_s < dbeta[r] * (lp[r + 1] - lp[r]); a swap exchanges x[0..d) and lp, nothing else.
+// A slot keeps its temperature, its RNG streams and its accept counters; states move.  Both lanes of a pair evaluate the SAME
+// expression on the SAME operands (lower slot's lp, upper slot's lp, the pair's dbeta and uniform), so they cannot disagree.
+//
+// Two kernels share the arithmetic, as mhx_rwmh_reg_body / mhx_rwmh_generic_body do:
+//   mhx_tmp_reg_body<D, TK, PK, R>   run-time specialised, one wave per block; x[D] and y[D] in VGPRs for a whole launch, records
+//                                    through SRD stores.  The exchange is in registers: even rounds pair lane ^ 1 (a DPP quad
+//                                    permutation, one v_mov_b32_dpp per 32-bit word, in place), odd rounds lane +- 1 across the 16- and
+//                                    32-lane rows (ds_bpermute_b32, one per word, in place), both under the execute mask of the lanes
+//                                    that swap and skipped whole when none does.
+//   mhx_tmp_generic_body             run-time dimension, state in HBM as [dim][nchains] plus ybuf, 256-thread blocks (whole ladders):
+//                                    a lane exchange of lp, then each lane of a swapping pair hands its column over through registers.
+// The tempering table `tt` (reals, built on the host): beta[R], dbeta[R] (dbeta[R - 1] unused, 0), then the proposal scales,
+// sig[R] (ISO) or sig[R][dim] (DIAG).  `swapc`: [2][nchains] u32, attempts then swaps of pair (r, r + 1), kept by the lower slot.
+#pragma once
+#include "mhx_rwmh_kernels.h"
+
+MHX_NS_BEGIN
+
+// stream tag of the swap uniforms: 0 .. 3 are the older streams, 4 .. 7 their retry twins, 8 .. 10 and 12 .. 14 the family streams
+#define MHX_STREAM_SWAP 11u
+
+// Largest dimension the register form is built for: x[D], y[D] and the temporaries of the unrolled candidate loop (DIAG: the lane's
+// own scales too, which the compiler hoists out of the step loop) must fit 512 VGPRs without scratch memory.  Measured by
+// cross-compiling for gfx950 with the options of the run-time build, isotropic Gaussian target, R = 64, ISO and DIAG: fp64 clean at
+// 48 (DIAG: all 512 registers), scratch at 52 and 56 (DIAG; ISO is clean at 56 and spills at 64); fp32 clean at 72 and 80, scratch
+// at 88 (DIAG; ISO is clean at 96 and spills at 128).  tests/test_tempered_cpu.py compiles the kernel at the limit and at the next
+// size tried.  Above it the state-in-HBM form runs.
+#define MHX_TEMPERED_REG_MAX_DIM (MHX_REAL64 ? 48 : 80)
+
+// the value of `v` in lane (lane ^ 1): a quad permutation [1, 0, 3, 2]
+MHX_DEV mhx_u32 mhx_tmp_xor1_u32(const mhx_u32 v)
+{
+    return (mhx_u32)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false);
+}
+// the value of `v` in the lane whose byte address (4 * lane) is `paddr`
+MHX_DEV mhx_u32 mhx_tmp_perm_u32(const int paddr, const mhx_u32 v) { return (mhx_u32)__builtin_amdgcn_ds_bpermute(paddr, (int)v); }
+
+template <bool EVEN>
+MHX_DEV mhx_real mhx_tmp_partner(const mhx_real v, const int paddr)
+{
+#if MHX_REAL64
+    const mhx_u64 b = (mhx_u64)__double_as_longlong(v);
+    mhx_u32 lo = (mhx_u32)b, hi = (mhx_u32)(b >> 32);
+    if constexpr (EVEN) { lo = mhx_tmp_xor1_u32(lo); hi = mhx_tmp_xor1_u32(hi); }
+    else { lo = mhx_tmp_perm_u32(paddr, lo); hi = mhx_tmp_perm_u32(paddr, hi); }
+    return __longlong_as_double((long long)(((mhx_u64)hi << 32) | (mhx_u64)lo));
+#else
+    const mhx_u32 b = __float_as_uint(v);
+    return __uint_as_float(EVEN ? mhx_tmp_xor1_u32(b) : mhx_tmp_perm_u32(paddr, b));
+#endif
+}
+
+// What a lane knows of its place in the ladder, fixed for a launch
+struct mhx_tmp_lane {
+    int r;              // rung
+    int paddr_odd;      // byte address of the odd rounds' partner lane (the lane itself where it has none)
+    bool low_odd;       // odd rounds: the lower slot of a pair
+    bool pair_odd;      // odd rounds: in a pair at all (rungs 0 and R - 1 are not)
+    mhx_real beta;
+    mhx_real db_even;   // dbeta of the even rounds' pair, of the odd rounds' pair
+    mhx_real db_odd;
+};
+
+MHX_DEV mhx_tmp_lane mhx_tmp_lane_of(const int c, const int R, const mhx_real* __restrict__ tt)
+{
+    mhx_tmp_lane t;
+    const int lane = (int)(threadIdx.x & 63u);
+    t.r = c & (R - 1);
+    t.low_odd = (t.r & 1) != 0 && t.r + 1 < R;
+    const bool up_odd = (t.r & 1) == 0 && t.r >= 2;
+    t.pair_odd = t.low_odd || up_odd;
+    t.paddr_odd = 4 * (t.low_odd ? lane + 1 : (up_odd ? lane - 1 : lane));
+    t.beta = tt[t.r];
+    t.db_even = tt[R + (t.r & ~1)];
+    t.db_odd = tt[R + (t.low_odd ? t.r : (up_odd ? t.r - 1 : 0))];
+    return t;
+}
+
+// The decision of swap round `s` for this lane's pair: true in BOTH lanes of a pair that swaps, false elsewhere.  `plp` receives the
+// partner's lp.  attempts / swaps: the lower slot's counters.
+template <bool EVEN>
+MHX_DEV bool mhx_tmp_decide(const mhx_tmp_lane& t, const mhx_philox_key& ks, const mhx_u64 id, const mhx_u32 s, const mhx_real lp,
+                            mhx_real& plp, mhx_u32& attempts, mhx_u32& swaps)
+{
+    const bool low = EVEN ? (t.r & 1) == 0 : t.low_odd;
+    const bool paired = EVEN ? true : t.pair_odd;
+    plp = mhx_tmp_partner<EVEN>(lp, t.paddr_odd);
+    const mhx_u64 idl = low ? id : id - 1ull;                       // the pair's uniform is keyed by its lower slot
+    const mhx_u32x4 w = mhx_philox(ks, (mhx_u32)idl, (mhx_u32)(idl >> 32), s, MHX_STREAM_SWAP << 28);
+    const mhx_real logu = mhx_log_pos(mhx_fam_u_open(w));           // words (x, y) in fp64, word x in fp32: as mhx_accept_logu's even steps
+    const mhx_real lp_lo = low ? lp : plp, lp_hi = low ? plp : lp;
+    const mhx_real logs = (EVEN ? t.db_even : t.db_odd) * (lp_hi - lp_lo);
+    const bool sw = paired && (logu < logs);                        // strict; NaN compares false => no swap
+    attempts += (paired && low) ? 1u : 0u;
+    swaps += (sw && low) ? 1u : 0u;
+    return sw;
+}
+
+// ---------------------------------------------------------------------------------------------
+// state in HBM, run-time dimension
+template <int TK>
+MHX_DEV void mhx_tmp_generic_body(const mhx_rwmh_args& a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                                  mhx_u32* __restrict__ swapc, const int swap_every, const int R)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.nchains) return;                                     // (whole ladders leave together: nchains is a multiple of R)
+    const mhx_u64 id = a.first_chain + (mhx_u64)c;
+    const mhx_u32 id_lo = (mhx_u32)id, id_hi = (mhx_u32)(id >> 32);
+    const mhx_philox_key ks = mhx_philox_schedule(a.seed);
+    const long ld = a.ld;
+    const int d = a.dim;
+    mhx_real* xs = a.x + c;
+    mhx_real* ys = a.ybuf + c;
+    const mhx_tmp_lane t = mhx_tmp_lane_of(c, R, tt);
+    const bool iso = a.prop_kind == MHX_PROP_ISO;
+    const mhx_real* sig = tt + 2 * R + (iso ? (long)t.r : (long)t.r * d);
+
+    mhx_real lp = a.lp[c];
+    mhx_u32 nacc = a.acc_count[c];
+    mhx_u32 wave_acc = 0;
+    bool last = a.last_acc[c] != 0;
+    mhx_u32 attempts = swapc[c], swaps = swapc[ld + c];
+    mhx_accept_cache ac;
+    ac.group = 0xffffffffu;
+    ac.w.x = ac.w.y = ac.w.z = ac.w.w = 0u;
+    mhx_u32 save_next = a.save_next;
+    long slot = a.save_slot;
+    const int nblk = (d + 3) >> 2;
+    mhx_u32 swap_next = 0xffffffffu;                                 // the next step with a swap round
+    mhx_u32 sround = 0u;                                             // ... and its round number, step / swap_every of the GLOBAL step
+    if (swap_every > 0) {
+        sround = (a.step0 + (mhx_u32)swap_every - 1u) / (mhx_u32)swap_every;
+        swap_next = sround * (mhx_u32)swap_every;
+    }
+
+    for (int i = 0; i < a.nsteps; ++i) {
+        const mhx_u32 step = a.step0 + (mhx_u32)i;
+        for (int b = 0; b < nblk; ++b) {
+            mhx_real n[4];
+            mhx_normal4(ks, id_lo, id_hi, step, MHX_STREAM_PROPOSAL, (mhx_u32)b, n);
+            for (int j = 0; j < 4; ++j) {
+                const int k = 4 * b + j;
+                if (k < d) ys[(long)k * ld] = mhx_fma(iso ? sig[0] : sig[k], n[j], xs[(long)k * ld]);
+            }
+        }
+        mhx_strided_x yv;
+        yv.base = ys;
+        yv.ld = ld;
+        const mhx_real lpy = mhx_target_eval<TK>(a.target_kind, yv, d, tparams, a.ntparams, a.tconst);
+        const mhx_real logu = mhx_accept_logu(ks, id_lo, id_hi, step, ac);
+        const mhx_real loga = t.beta * (lpy - lp);
+        const bool acc = logu < loga;                    // strict; NaN compares false => reject
+        lp = acc ? lpy : lp;
+        nacc += acc ? 1u : 0u;
+        last = acc;
+        wave_acc += (mhx_u32)__popcll(__ballot(acc));
+        if (acc) {
+            for (int k = 0; k < d; ++k) xs[(long)k * ld] = ys[(long)k * ld];
+        }
+        if (step == swap_next) {                         // wave-uniform
+            const mhx_u32 s = sround++;
+            mhx_real plp;
+            if ((s & 1u) == 0u) {
+                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, lp, plp, attempts, swaps);
+                if (__ballot(sw) != 0ull) {
+                    for (int k = 0; k < d; ++k) {
+                        const mhx_real mine = xs[(long)k * ld];
+                        const mhx_real theirs = mhx_tmp_partner<true>(mine, t.paddr_odd);
+                        if (sw) xs[(long)k * ld] = theirs;
+                    }
+                    lp = sw ? plp : lp;
+                }
+            } else {
+                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, lp, plp, attempts, swaps);
+                if (__ballot(sw) != 0ull) {
+                    for (int k = 0; k < d; ++k) {
+                        const mhx_real mine = xs[(long)k * ld];
+                        const mhx_real theirs = mhx_tmp_partner<false>(mine, t.paddr_odd);
+                        if (sw) xs[(long)k * ld] = theirs;
+                    }
+                    lp = sw ? plp : lp;
+                }
+            }
+            swap_next += (mhx_u32)swap_every;
+        }
+        if (step == save_next) {                         // the state after the step's swap round
+            mhx_real* row = a.samples + slot * (long)(d + 1) * ld + c;
+            for (int k = 0; k < d; ++k) row[(long)k * ld] = xs[(long)k * ld];
+            row[(long)d * ld] = lp;
+            a.accepted[slot * ld + c] = acc ? 1 : 0;
+            save_next += (mhx_u32)a.thinning;
+            ++slot;
+        }
+    }
+    a.lp[c] = lp;
+    a.acc_count[c] = nacc;
+    a.last_acc[c] = last ? 1 : 0;
+    swapc[c] = attempts;
+    swapc[ld + c] = swaps;
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        atomicAdd(a.acc_total, (mhx_u64)wave_acc);
+}
+
+// column r, r + R, r + 2R, ... of a [N][d1][C] sample tensor as a [N][d1][C / R] tensor (mhx_run_rung)
+MHX_DEV void mhx_tmp_rung_body(const mhx_real* __restrict__ src, mhx_real* __restrict__ dst, const long rows, const long C, const int R, const int r)
+{
+    const long L = C / R;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * L) return;
+    const long row = i / L, l = i - row * L;
+    dst[i] = src[row * C + l * R + r];
+}
+
+// ---------------------------------------------------------------------------------------------
+// state in registers; dimension, target, proposal kind and ladder size compile-time constants
+#ifdef MHX_JIT_TEMPERED_REG
+template <int D, int TK, int PK, int R>
+MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                              mhx_u32* __restrict__ swapc, const int swap_every)
+{
+    static_assert(R >= 2 && R <= 64 && (R & (R - 1)) == 0, "a ladder is a power of two of lanes of one wave");
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.nchains) return;                                     // (whole ladders leave together: nchains is a multiple of R)
+    const mhx_u64 id = a.first_chain + (mhx_u64)c;
+    const mhx_u32 id_lo = (mhx_u32)id, id_hi = (mhx_u32)(id >> 32);
+    const mhx_philox_key ks = mhx_philox_schedule(a.seed);
+    const long ld = a.ld;
+    const mhx_tmp_lane t = mhx_tmp_lane_of(c, R, tt);
+    const mhx_real* sig = tt + 2 * R + (PK == MHX_PROP_ISO ? t.r : t.r * D);
+    const mhx_real sig0 = sig[0];
+
+    mhx_real x[D], y[D];
+    const mhx_u32 cu = (mhx_u32)c * MHX_RB;  // row pointers are wave-uniform (scalar), the lane adds its byte offset
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = mhx_ld_off(a.x + (long)k * ld, cu);
+    mhx_real lp = a.lp[c];
+    mhx_u32 nacc = a.acc_count[c];
+    mhx_u32 wave_acc = 0;
+    bool last = a.last_acc[c] != 0;
+    mhx_u32 attempts = swapc[c], swaps = swapc[ld + c];
+    mhx_accept_cache ac;
+    ac.group = 0xffffffffu;
+    ac.w.x = ac.w.y = ac.w.z = ac.w.w = 0u;
+    mhx_u32 save_next = a.save_next;
+    long slot = a.save_slot;
+    mhx_u32 swap_next = 0xffffffffu;                                 // the next step with a swap round
+    mhx_u32 sround = 0u;                                             // ... and its round number, step / swap_every of the GLOBAL step
+    if (swap_every > 0) {
+        sround = (a.step0 + (mhx_u32)swap_every - 1u) / (mhx_u32)swap_every;
+        swap_next = sround * (mhx_u32)swap_every;
+    }
+
+    for (int i = 0; i < a.nsteps; ++i) {
+        const mhx_u32 step = a.step0 + (mhx_u32)i;
+#pragma unroll
+        for (int b = 0; b < (D + 3) / 4; ++b) {
+            mhx_real n[4];
+            mhx_normal4(ks, id_lo, id_hi, step, MHX_STREAM_PROPOSAL, (mhx_u32)b, n);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 4 * b + j;
+                if (k < D) y[k] = mhx_fma(PK == MHX_PROP_ISO ? sig0 : sig[k], n[j], x[k]);
+            }
+        }
+        const mhx_real lpy = mhx_target_eval<TK>(TK, y, D, tparams, a.ntparams, a.tconst);
+        const mhx_real logu = mhx_accept_logu(ks, id_lo, id_hi, step, ac);
+        const mhx_real loga = t.beta * (lpy - lp);
+        const bool acc = logu < loga;                    // strict; NaN compares false => reject
+        // (fp64: a move under the execute mask, fp32: a select -- see mhx_rwmh_reg_body)
+        if (MHX_REAL64) {
+            if (acc) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) x[k] = y[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < D; ++k) x[k] = acc ? y[k] : x[k];
+        }
+        lp = acc ? lpy : lp;
+        nacc += acc ? 1u : 0u;
+        last = acc;
+        wave_acc += (mhx_u32)__popcll(__ballot(acc));
+        if (step == swap_next) {                         // wave-uniform
+            const mhx_u32 s = sround++;
+            mhx_real plp;
+            // the exchange runs under the execute mask of the lanes that swap -- both lanes of a pair, by construction -- and in place:
+            // y is dead here, but not even it is needed
+            if ((s & 1u) == 0u) {
+                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, lp, plp, attempts, swaps);
+                if (__ballot(sw) != 0ull) {
+                    if (sw) {
+#pragma unroll
+                        for (int k = 0; k < D; ++k) x[k] = mhx_tmp_partner<true>(x[k], t.paddr_odd);
+                        lp = plp;
+                    }
+                }
+            } else if (R > 2) {                          // (R = 2: the odd rounds have no pair)
+                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, lp, plp, attempts, swaps);
+                if (__ballot(sw) != 0ull) {
+                    if (sw) {
+#pragma unroll
+                        for (int k = 0; k < D; ++k) x[k] = mhx_tmp_partner<false>(x[k], t.paddr_odd);
+                        lp = plp;
+                    }
+                }
+            }
+            swap_next += (mhx_u32)swap_every;
+        }
+        if (step == save_next) {                         // the state after the step's swap round
+            mhx_real* slotp = a.samples + slot * (long)(D + 1) * ld;
+            const mhx_srd srd = mhx_make_srd(slotp, (mhx_u32)(D + 1) * (mhx_u32)ld * MHX_RB);
+            const mhx_u32 ldb = (mhx_u32)ld * MHX_RB;
+            mhx_u32 roff = 0u;
+            asm volatile("" : "+s"(roff));
+#pragma unroll
+            for (int k = 0; k < D; ++k) { mhx_srd_store<MHX_REC_STORE_AUX>(srd, cu, roff, x[k]); roff += ldb; }
+            mhx_srd_store<MHX_REC_STORE_AUX>(srd, cu, roff, lp);
+            a.accepted[slot * ld + c] = acc ? 1 : 0;
+            save_next += (mhx_u32)a.thinning;
+            ++slot;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) mhx_st_off(a.x + (long)k * ld, cu, x[k]);
+    a.lp[c] = lp;
+    a.acc_count[c] = nacc;
+    a.last_acc[c] = last ? 1 : 0;
+    swapc[c] = attempts;
+    swapc[ld + c] = swaps;
+    if (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0u)
+        atomicAdd(a.acc_total, (mhx_u64)wave_acc);
+}
+
+extern "C" __global__ void __launch_bounds__(64)
+mhx_jit_tempered_reg(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                     mhx_u32* __restrict__ swapc, const int swap_every)
+{
+    mhx_tmp_reg_body<MHX_JIT_DIM, MHX_JIT_TK, MHX_JIT_PK, MHX_JIT_R>(a, tparams, tt, swapc, swap_every);
+}
+#endif
+#ifdef MHX_JIT_TEMPERED_GENERIC
+extern "C" __global__ void __launch_bounds__(256)
+mhx_jit_tempered_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                         mhx_u32* __restrict__ swapc, const int swap_every, const int R)
+{
+    mhx_tmp_generic_body<MHX_JIT_TK>(a, tparams, tt, swapc, swap_every, R);
+}
+#endif
+MHX_NS_END

@@ -54,6 +54,11 @@ class RwmhCfg(C.Structure):
                 ("proposal_mean", C.c_void_p), ("reduce_lanes", C.c_int32)]
 
 
+class TemperedCfg(C.Structure):
+    """mhx_tempered_cfg: the ladder of a tempered run; beta and scale point at R doubles (scale may be NULL)"""
+    _fields_ = [("R", C.c_int32), ("swap_every", C.c_int32), ("beta", C.c_void_p), ("scale", C.c_void_p)]
+
+
 class ProposalComponent(C.Structure):
     """mhx_proposal_component: one univariate component of a proposal, parameters as in Distributions.jl"""
     _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
@@ -134,7 +139,7 @@ EXPORTS = [
     "mhx_run_histogram", "mhx_ctx_histogram", "mhx_group_histogram", "mhx_run_histogram2d", "mhx_ctx_histogram2d", "mhx_group_histogram2d",
     "mhx_run_autocovariance", "mhx_ctx_autocovariance", "mhx_group_autocovariance",
     "mhx_run_derive", "mhx_ctx_derive", "mhx_run_predict", "mhx_ctx_predict", "mhx_run_pointwise", "mhx_ctx_pointwise",
-    "mhx_run_psis", "mhx_ctx_psis",
+    "mhx_run_psis", "mhx_ctx_psis", "mhx_rwmh_create_tempered", "mhx_run_swap_stats", "mhx_run_rung",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -299,6 +304,9 @@ def lib():
         L.mhx_run_psis.argtypes = [vp, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_double, dp, dp, i64p, i64p]
         L.mhx_ctx_psis.argtypes = [vp, vp, C.c_int64, C.c_int32, C.c_int64, C.c_char_p, rp, C.c_int64, C.c_int32, rp, C.c_size_t, C.c_double,
                                    dp, dp, i64p, i64p]
+        L.mhx_rwmh_create_tempered.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), pvp]
+        L.mhx_run_swap_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.mhx_run_rung.argtypes = [vp, C.c_int32, pvp]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -933,6 +933,52 @@ def RWMH(d):
     return MetropolisHastings(RandomWalkProposal(d))
 
 
+def geometric_betas(R, beta_min):
+    """The usual ladder of parallel tempering: R inverse temperatures 1 = beta_0 > ... > beta_{R-1} = beta_min in geometric
+    progression, beta_r = beta_min^(r / (R - 1)) (doubles; beta_0 is exactly 1)."""
+    R = int(R)
+    if R < 2 or not (0.0 < float(beta_min) < 1.0):
+        raise L.ArgumentError(L.MHX_EINVAL, "geometric_betas: R >= 2 rungs and 0 < beta_min < 1")
+    b = np.array([float(beta_min) ** (r / (R - 1.0)) for r in range(R)], dtype=np.float64)
+    b[0], b[-1] = 1.0, float(beta_min)
+    return b
+
+
+class Tempered:
+    """Tempered(sampler, betas, swap_every=1, scales=None) -- parallel tempering (replica exchange) around a random-walk sampler, what
+    MCMCTempering.jl wraps around AdvancedMH's samplers and emcee shipped as PTSampler.  `sampler`: an RWMH over an isotropic or
+    diagonal zero-mean MvNormal.  `betas`: the ladder, betas[0] == 1, strictly decreasing, a power of two of rungs (2..64).  Rung r
+    samples target^betas[r] with the proposal scaled by scales[r] (default betas[r]^(-1/2)); after every swap_every-th transition
+    neighbouring rungs may exchange their states.  `sample(model, Tempered(...), N, nladders)` returns the nladders cold chains."""
+
+    def __init__(self, sampler, betas, swap_every=1, scales=None):
+        if not isinstance(sampler, MetropolisHastings) or not isinstance(sampler.proposal, RandomWalkProposal) or \
+                not isinstance(sampler.proposal.proposal, MvNormal):
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered wraps an RWMH sampler over an isotropic or diagonal MvNormal")
+        self.sampler = sampler
+        self.proposal = sampler.proposal                     # (what Run.init looks at)
+        self.param_names = sampler.param_names
+        self.betas = np.ascontiguousarray(betas, dtype=np.float64).ravel()
+        self.R = int(self.betas.size)
+        self.swap_every = int(swap_every)
+        self.scales = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64).ravel()
+        if self.scales is not None and self.scales.size != self.R:
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered: %d scales for %d betas" % (self.scales.size, self.R))
+
+
+class SwapTable(list):
+    """swap_rates() of a tempered run: one row {pair, beta_lo, beta_hi, attempts, swaps, rate} per pair of neighbouring rungs"""
+
+    def __str__(self):
+        out = ["pair     beta_r    beta_r+1    attempts       swaps    rate"]
+        for w in self:
+            out.append("%2d-%-2d %9.4g %11.4g %11d %11d %7.3f" % (w["pair"][0], w["pair"][1], w["beta_lo"], w["beta_hi"], w["attempts"],
+                                                               w["swaps"], w["rate"]))
+        return "\n".join(out)
+
+    __repr__ = __str__
+
+
 class StretchProposal:
     """StretchProposal(prior, a = 2.0) -- src/emcee.jl:63-68."""
 
@@ -1712,7 +1758,22 @@ class Run:
         lib = L.lib()
         d = model.dim
         self._keep = []
-        if isinstance(sampler, MetropolisHastings):
+        self.tempered = isinstance(sampler, Tempered)
+        if self.tempered:
+            # a ladder of R rungs per "chain" asked for: nchains device chains in all, whole ladders (mhx_rwmh_create_tempered)
+            mv = sampler.proposal.proposal
+            if mv.dim != d:
+                raise L.ArgumentError(L.MHX_EINVAL, "proposal dimension %d != model dimension %d" % (mv.dim, d))
+            vec = None if mv.vec is None else f32(mv.vec)
+            mean = f32(mv.mean) if np.any(mv.mean != 0) else None
+            self._keep += [vec, mean, sampler.betas, sampler.scales]
+            cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
+            tcfg = L.TemperedCfg(sampler.R, sampler.swap_every, sampler.betas.ctypes.data,
+                                 None if sampler.scales is None else sampler.scales.ctypes.data)
+            L.check(lib.mhx_rwmh_create_tempered(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(self.h)))
+            self.n = nchains
+            self.kind = "rwmh"
+        elif isinstance(sampler, MetropolisHastings):
             mv = sampler.proposal.proposal
             if mv.dim != d:
                 raise L.ArgumentError(L.MHX_EINVAL, "proposal dimension %d != model dimension %d" % (mv.dim, d))
@@ -1829,6 +1890,7 @@ class Run:
             rng = np.random.default_rng([self.seed, 0xE3CEE])
             ip = self.ctx.arr(np.stack([self.sampler.proposal.rand_initial(rng) for _ in range(self.n)], axis=1))
         L.check(L.lib().mhx_run_init(self.h, L.fptr(ip)))
+        self._transitions = 0
 
     def sample(self, n_samples, discard_initial=0, thinning=1, num_warmup=0, save=True):
         """save: True/1 sample tensor, False/0 nothing, "moments"/2 running moments only (mhx.h)."""
@@ -1836,6 +1898,7 @@ class Run:
         mode = 2 if (isinstance(save, str) and save == "moments") or (save is not True and save == 2) else (1 if save else 0)
         L.check(L.lib().mhx_run_sample(self.h, C.byref(s), mode))
         self._last_n = n_samples if mode == 1 else 0
+        self._transitions = getattr(self, "_transitions", 0) + discard_initial + (n_samples - 1) * thinning
 
     def sample_to_host(self, n_samples, discard_initial=0, thinning=1, num_warmup=0, want_accepted=True, out=None,
                        out_accepted=None, slab_samples=0, pinned=None):
@@ -2277,6 +2340,37 @@ class Run:
         res.fn = fn
         return res
 
+    # -- a tempered run (mhx.Tempered): the ladder's own statistics
+    def swap_stats(self):
+        """(attempts [R - 1], swaps [R - 1]) of the pairs (r, r + 1), summed over the ladders, since init (mhx_run_swap_stats)"""
+        R = self.sampler.R if getattr(self, "tempered", False) else 2
+        att, sw = (C.c_uint64 * (R - 1))(), (C.c_uint64 * (R - 1))()
+        L.check(L.lib().mhx_run_swap_stats(self.h, att, sw))
+        return np.array(att[:], dtype=np.uint64), np.array(sw[:], dtype=np.uint64)
+
+    def swap_rates(self):
+        att, sw = self.swap_stats()
+        b = self.sampler.betas
+        return SwapTable(dict(pair=(r, r + 1), beta_lo=float(b[r]), beta_hi=float(b[r + 1]), attempts=int(att[r]), swaps=int(sw[r]),
+                              rate=(float(sw[r]) / float(att[r]) if att[r] else float("nan"))) for r in range(len(att)))
+
+    def rung(self, r):
+        """rung r of every ladder as a snapshot run (mhx_run_rung): [n_saved][dim + 1][nladders] on the device, read by every post-run
+        statistic like any run"""
+        h = C.c_void_p()
+        L.check(L.lib().mhx_run_rung(self.h, int(r), C.byref(h)))
+        out = DerivedRun(h, self, self.dim)
+        out.n = self.n // self.sampler.R
+        return out
+
+    def accept_rates(self):
+        """Metropolis-Hastings acceptance rate of every temperature since init: accepted proposals of the rung's slots over their
+        transitions, [R]"""
+        R = self.sampler.R
+        cnt = self.state()[2].astype(np.float64).reshape(-1, R)
+        total = getattr(self, "_transitions", 0)
+        return cnt.mean(axis=0) / float(total) if total else np.full(R, np.nan)
+
     def close(self):
         if self.h:
             L.lib().mhx_run_destroy(self.h)
@@ -2374,10 +2468,22 @@ def sample(model, sampler, N, nchains=1, *more, initial_params=None, discard_ini
         discard_initial = num_warmup
     if not isinstance(model, DensityModel) and (_is_logdensity_problem(model) or isinstance(model, _TargetSpec)):
         model = LogDensityModel(model)              # sample(problem, sampler, N): AbstractMCMC wraps what implements the interface
+    if isinstance(sampler, Tempered):              # sample(model, Tempered(...), N, nladders): R device chains per ladder
+        nchains = int(nchains) * sampler.R
     run = Run(model, sampler, nchains=nchains, seed=seed, first_chain=first_chain, ctx=ctx, flags=flags,
               reduce_lanes=reduce_lanes, dtype=dtype, normal_gen=normal_gen)
     run.init(initial_params)
-    if callback is None:
+    cold = None
+    if run.tempered:
+        # the draws stay on the device (the accept-compacted return path does not know swaps): the cold rung is gathered there and
+        # only it comes back
+        if callback is not None:
+            raise L.ArgumentError(L.MHX_EINVAL, "sample: a tempered run takes no callback")
+        run.sample(N, discard_initial, thinning, num_warmup)
+        cold = run.rung(0)
+        value = cold.samples()[0]
+        acc = np.ascontiguousarray(run.samples()[1][:, 0::sampler.R])
+    elif callback is None:
         # one call: the samples stream to the host while the chains advance (mhx_run_sample_to_host)
         value, acc = run.sample_to_host(N, discard_initial, thinning, num_warmup)
     else:
@@ -2412,7 +2518,10 @@ def sample(model, sampler, N, nchains=1, *more, initial_params=None, discard_ini
             raise L.ArgumentError(L.MHX_EINVAL, "param_names has the wrong length")
     names = names + ["lp"]
     if chain_type is Chains:
-        return Chains(value, names, discard_initial + 1, thinning, accepted=acc, stats=run.stats(), state=run)
+        chain = Chains(value, names, discard_initial + 1, thinning, accepted=acc, stats=run.stats(), state=cold if cold is not None else run)
+        if cold is not None:
+            chain.tempered = run                                    # the full run: swap_rates(), rung(r), accept_rates()
+        return chain
     if chain_type is np.ndarray:
         return value
     if chain_type is StructArray:

@@ -522,7 +522,10 @@ typedef struct {
                                   14 a conditional proposal (mhx_rwmh_create_conditional), lane per chain, compiled at run time:
                                   the register form or the state-in-HBM form, the same chain,
                                   15 a composite proposal (mhx_rwmh_create_composite): blocks of components with their own kind,
-                                  symmetric flag and parameter map; lane per chain, compiled at run time, the same two forms */
+                                  symmetric flag and parameter map; lane per chain, compiled at run time, the same two forms,
+                                  16 a tempered run (mhx_rwmh_create_tempered): ladders of temperatures in consecutive lanes, swaps
+                                  across lanes inside the step kernel; the run-time specialised register form or the state-in-HBM
+                                  form (pre-built for the catalogue targets), the same chain */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
@@ -531,7 +534,7 @@ typedef struct {
                                   (0 = diagonal, 1 = bidiagonal: an AR(1) / Markov model, ...), -1 = none (dense form, other samplers) */
     int32_t tainted;           /* 1: a probe / fault-injection option of the tools build was set on the run's context -- the chains of
                                   such a run may be INVALID (timing probes skip work).  Always 0 from libmhx.so. */
-    int32_t register_form;     /* kernel variants 13, 14 and 15: 1 = the run is stepped by the run-time specialised register form, 0 = by
+    int32_t register_form;     /* kernel variants 13, 14, 15 and 16: 1 = the run is stepped by the run-time specialised register form, 0 = by
                                   the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
@@ -963,7 +966,39 @@ int mhx_ctx_psis(mhx_ctx *ctx, const void *d_tensor, int64_t n_samples, int32_t 
                  double *tail_out, int64_t *T, int64_t *M);
 
 /* ---------------------------------------------------------------------------------------------
- * Many chains over many GPUs as ONE call from ONE process.  Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
+ * Parallel tempering (replica exchange) of random-walk Metropolis-Hastings.  A run of `nchains` device chains is
+ * nchains / R ladders of R rungs: chain c is rung r = c mod R of ladder c div R and samples target^beta[r] with the proposal scaled by
+ * scale[r]; after every swap_every-th transition neighbouring rungs of a ladder may exchange their states (deterministic even-odd
+ * pairs, one uniform per pair).  The chain to read is rung 0 (beta = 1): mhx_run_rung.  A slot keeps its temperature; the accept
+ * counters of a slot are those of its temperature.  The run records EVERY rung (R times the cold rung's memory and store traffic).
+ *     R           a power of two in 2..64; cfg.nchains and cfg.first_chain are multiples of it
+ *     swap_every  >= 0; 0 = no swap rounds
+ *     beta        [R] doubles, beta[0] == 1, strictly decreasing, all > 0 (swap_every == 0: non-increasing is enough, so that a
+ *                 ladder of equal temperatures can be timed against the plain run); rounded once to the run's width
+ *     scale       [R] doubles or NULL = beta^(-1/2) (computed in double); scale[0] == 1, all > 0; the proposal of rung r is
+ *                 ISO scale[r] * sigma, DIAG scale[r] * sigma_k: one product in double, rounded once
+ * cfg: proposal kinds ISO and DIAG with zero mean; any target.  MHX_EINVAL with a message that names the rule for: a bad R, nchains
+ * or first_chain not a multiple of R, a bad ladder or scale, swap_every < 0, MHX_FLAG_ZIGGURAT, MHX_FLAG_STATIC_PROPOSAL, a proposal
+ * mean, MHX_PROP_DENSE, reduce_lanes > 1, MHX_FLAG_NO_JIT with a user target.  Initial states as mhx_rwmh_create's.
+ * A tempered run refuses, with MHX_ESTATE: MHX_SAVE_MOMENTS, mhx_run_sample_to_host (the accept-compacted return path assumes that a
+ * rejected transition repeats the row above; a swap breaks that), mhx_run_state_size / _save_state / _load_state, mhx_group_attach. */
+typedef struct {
+    int32_t R;
+    int32_t swap_every;
+    const void *beta;  /* [R] doubles (whatever the run's width) */
+    const void *scale; /* [R] doubles or NULL */
+} mhx_tempered_cfg;
+int mhx_rwmh_create_tempered(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_tempered_cfg *tcfg, mhx_run **out);
+/* attempts[R - 1], swaps[R - 1]: swap rounds pair (r, r + 1) took part in since mhx_run_init and how many of them swapped, summed
+ * over the ladders (the per-slot counters are kept without atomics: the counts are deterministic).  MHX_ESTATE: not a tempered run. */
+int mhx_run_swap_stats(mhx_run *run, uint64_t *attempts, uint64_t *swaps);
+/* Rung r of every ladder as a snapshot run in the sense of mhx_run_derive: a device tensor [n_samples][dim + 1][nchains / R] gathered
+ * from columns r, r + R, r + 2R, ... of the sample tensor; it inherits seed and first_chain as a derived run does and every post-run
+ * statistic reads it like any run.  MHX_EINVAL: r out of range; MHX_ESTATE: not a tempered run, or no sample tensor.  Blocking. */
+int mhx_run_rung(mhx_run *run, int32_t r, mhx_run **out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Many chains over many GPUs as ONE call from ONE process. Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
  * (README.md:135-148: one task per chain) -- here one host thread per GPU behind the ABI.  A group is N member contexts (one
  * per entry of `devices`; entries may repeat -- several members on one device are legal, which is how the form is verified on a
  * one-GPU box), N persistent worker threads and the host-side sum of the statistics that ranks of a multi-process run all-reduce
