@@ -854,6 +854,7 @@ enum kernel_form {
     KF_COND = 14,           // ... whose parameters are a function of the state (a conditional proposal): the same two forms
     KF_COMPOSITE = 15,      // ... and whose kind, symmetric flag and parameter map vary per block of components (a composite proposal)
     KF_TEMPERED = 16,       // parallel tempering of the plain random walk: specialised register form or state in HBM (mhx_api_tempered.inc)
+    KF_TEMPERED_ADAPT = 17, // ... whose ladders tune their temperatures from their swaps while the run warms up: the same two forms
 };
 
 // One kernel of a run, ready to launch: everything the host needs for it, filled ONCE, in the branch of a create function that
@@ -945,6 +946,10 @@ struct mhx_run : mhx_handle_hdr {
     int tmp_swap_every = 0;                 // a swap round after every so many transitions (0: none)
     mhx_real* d_ttab = nullptr;             // beta[R] | dbeta[R] | sig[R] or sig[R][dim]
     uint32_t* d_swapc = nullptr;            // [2][n] swap attempts, swaps of pair (r, r + 1), kept by the lower slot
+    // KF_TEMPERED_ADAPT: everything of KF_TEMPERED but d_ttab, and
+    bool tmp_adapt = false;
+    mhx_real* d_tadapt = nullptr;           // rho[n] | beta[n] | rho0[n] | gamma[adapt_steps / swap_every]
+    mhx_tmp_adapt tmp_ad{};                 // the step kernel's adaptation block: pointers into d_tadapt and d_pvec, the constants
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -1021,7 +1026,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc, d_tadapt};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (acc_total_pin) (void)hipHostFree(acc_total_pin);
     }
@@ -1657,6 +1662,8 @@ static int rwmh_canonical_zero(mhx_run* r)
     return MHX_OK;
 }
 
+static int tempered_reset_ladder(mhx_run* r);                       // (mhx_api_tempered.inc)
+
 static int rwmh_init(mhx_run* r, const mhx_real* init)
 {
     mhx_ctx* ctx = r->ctx;
@@ -1670,6 +1677,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
         if (rcz) return rcz;
     }
     if (r->d_swapc) HIP_TRY(hipMemsetAsync(r->d_swapc, 0, 2 * (size_t)r->n * sizeof(uint32_t), ctx->stream));      // a tempered run: its swap counts begin here
+    if (int rct = tempered_reset_ladder(r)) return rct;                                                             // ... and an adaptive ladder at rho0
     mhx_rwmh_args a = rwmh_args(r);
     const mhx_real* tp = r->target->dparams;
     const mhx_real* pv = r->d_pvec;
@@ -2122,6 +2130,7 @@ const char* api_run_form_name(const mhx_run* r)
     case KF_WAVE: return "wave";
     case KF_RAM_DEFER: return "ram_defer";
     case KF_TEMPERED: return r->fam_reg ? "tempered_reg" : "tempered_generic";
+    case KF_TEMPERED_ADAPT: return r->fam_reg ? "tempered_adapt_reg" : "tempered_adapt_generic";
     case KF_FAMILY: return "family";
     case KF_COND: return "cond";
     case KF_COMPOSITE: return "composite";

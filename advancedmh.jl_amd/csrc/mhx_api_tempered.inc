@@ -10,15 +10,36 @@ k_tempered_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, 
 {
     mhx_tmp_generic_body<MHX_TARGET_DYNAMIC>(a, tparams, tt, swapc, swap_every, R);
 }
+// ... of an adaptive ladder (mhx_rwmh_create_tempered_adaptive), and the ladder of every slot from its rho outside a step launch
+__global__ void __launch_bounds__(256)
+k_tempered_adapt_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_tmp_adapt ad, mhx_u32* __restrict__ swapc,
+                         const int swap_every, const int R)
+{
+    mhx_tmp_generic_body<MHX_TARGET_DYNAMIC, true>(a, tparams, nullptr, swapc, swap_every, R, &ad);
+}
+__global__ void __launch_bounds__(256)
+k_tempered_derive(const mhx_tmp_adapt ad, const int nchains, const int R) { mhx_tmp_derive_body(ad, nchains, R); }
 __global__ void __launch_bounds__(256)
 k_tempered_rung(const mhx_real* __restrict__ src, mhx_real* __restrict__ dst, const long rows, const long C, const int R, const int r)
 {
     mhx_tmp_rung_body(src, dst, rows, C, R, r);
 }
 
-int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc, mhx_run** out)
+// an adaptive run: rho and beta of every slot back to the initial ladder (create, mhx_run_init)
+static int tempered_reset_ladder(mhx_run* r)
 {
-    const char* me = "mhx_rwmh_create_tempered";
+    if (!r->tmp_adapt) return MHX_OK;
+    const size_t n = (size_t)r->n;
+    HIP_TRY(hipMemcpyAsync(r->tmp_ad.rho, r->d_tadapt + 2 * n, n * sizeof(mhx_real), hipMemcpyDeviceToDevice, r->ctx->stream));
+    hipLaunchKernelGGL(k_tempered_derive, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r->ctx->stream, r->tmp_ad, r->n, r->tmp_R);
+    HIP_TRY(hipGetLastError());
+    return MHX_OK;
+}
+
+// `ac` NULL: a fixed ladder (mhx_rwmh_create_tempered); else the ladder adapts (mhx_rwmh_create_tempered_adaptive, DESIGN.md section 3.17.1)
+static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc,
+                           const mhx_ladder_adapt_cfg* ac, mhx_run** out)
+{
     if (!ctx || !t || !cfg || !tc || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
     if (cfg->dim != t->dim) return mhx_fail(MHX_EINVAL, "%s: proposal dim %d != model dim %d", me, cfg->dim, t->dim);
     if (cfg->nchains <= 0) return mhx_fail(MHX_EINVAL, "%s: nchains must be positive", me);
@@ -49,6 +70,26 @@ int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_c
     const double* beta = (const double*)tc->beta;
     const double* scale = (const double*)tc->scale;
     if (!beta) return mhx_fail(MHX_EINVAL, "%s: beta is NULL", me);
+    // ---- an adaptive ladder: NaN in a field of the cfg = its default
+    double a_target = 0.234, a_c = 1.0, a_kappa = 0.6, a_rmin = -10.0, a_rmax = std::log(16.0 / (double)(R - 1));
+    if (ac) {
+        if (!std::isnan(ac->target_rate)) a_target = ac->target_rate;
+        if (!std::isnan(ac->c)) a_c = ac->c;
+        if (!std::isnan(ac->kappa)) a_kappa = ac->kappa;
+        if (!std::isnan(ac->rho_min)) a_rmin = ac->rho_min;
+        if (!std::isnan(ac->rho_max)) a_rmax = ac->rho_max;
+        if (tc->swap_every == 0) return mhx_fail(MHX_EINVAL, "%s: swap_every = 0 -- an adaptive ladder tunes itself from its swap rounds", me);
+        if (scale) return mhx_fail(MHX_EINVAL, "%s: scale[] given -- the proposal scales of an adaptive ladder follow its temperatures (beta^(-1/2))", me);
+        if (ac->adapt_steps < 0) return mhx_fail(MHX_EINVAL, "%s: adapt_steps = %d must not be negative", me, (int)ac->adapt_steps);
+        if (!(a_kappa > 0.5 && a_kappa <= 1.0)) return mhx_fail(MHX_EINVAL, "%s: kappa = %g outside (0.5, 1] (the step sizes c s^(-kappa) must sum to infinity and their squares must not)", me, a_kappa);
+        if (!(a_c >= 0.0) || !std::isfinite(a_c)) return mhx_fail(MHX_EINVAL, "%s: c = %g must be finite and not negative", me, a_c);
+        if (!(a_target > 0.0 && a_target < 1.0)) return mhx_fail(MHX_EINVAL, "%s: target_rate = %g outside (0, 1)", me, a_target);
+        if (!std::isfinite(a_rmin) || !std::isfinite(a_rmax) || !(a_rmin <= a_rmax))
+            return mhx_fail(MHX_EINVAL, "%s: rho_min = %g, rho_max = %g -- finite, rho_min <= rho_max", me, a_rmin, a_rmax);
+        if ((double)(R - 1) * std::exp(a_rmax) > 80.0)
+            return mhx_fail(MHX_EINVAL, "%s: (R - 1) exp(rho_max) = %g > 80 -- the coldest beta, exp(-(R - 1) exp(rho_max)), would leave fp32's normal range",
+                            me, (double)(R - 1) * std::exp(a_rmax));
+    }
     // ---- the table, in the run's width: beta[R] | dbeta[R] | sig[R] or sig[R][d]
     const bool iso = cfg->proposal_kind == MHX_PROP_ISO;
     std::vector<mhx_real> tt((size_t)2 * R + (size_t)R * (iso ? 1 : (size_t)d), MHX_R(0.0));
@@ -77,7 +118,7 @@ int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_c
     r->dim = d; r->n = cfg->nchains; r->seed = cfg->seed; r->first_id = cfg->first_chain;
     r->flags = cfg->flags;
     r->prop_kind = cfg->proposal_kind; r->prop_scale = (mhx_real)cfg->proposal_scale;          // (the initial draw is the plain run's)
-    r->variant = KF_TEMPERED;
+    r->variant = ac ? KF_TEMPERED_ADAPT : KF_TEMPERED;
     r->tmp_R = R; r->tmp_swap_every = tc->swap_every;
     HIP_TRY(hipMalloc(&r->d_pvec, (iso ? 1 : (size_t)d) * sizeof(mhx_real)));
     if (!iso) COPY_SYNC(ctx->stream, r->d_pvec, cfg_vec, (size_t)d * sizeof(mhx_real), hipMemcpyHostToDevice);
@@ -87,6 +128,35 @@ int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_c
     HIP_TRY(hipMemsetAsync(r->d_swapc, 0, 2 * (size_t)r->n * sizeof(uint32_t), ctx->stream));
     int rc = run_alloc_state(r.get());
     if (rc) return rc;
+    if (ac) {
+        // rho0[r] = log(log(beta[r] / beta[r + 1])) in double, rounded once, clamped in the width; gamma[s] = c s^(-kappa), s = 1 ..
+        // adapt_steps / swap_every, one pow and one product in double, rounded once.  d_tadapt: rho[n] | beta[n] | rho0[n] | gamma[nrounds]
+        const size_t n = (size_t)r->n, nrounds = (size_t)(ac->adapt_steps / tc->swap_every);
+        const mhx_real rmin = (mhx_real)a_rmin, rmax = (mhx_real)a_rmax;
+        std::vector<mhx_real> h(n + nrounds, MHX_R(0.0));
+        for (int q = 0; q + 1 < R; ++q) {
+            mhx_real v = (mhx_real)std::log(std::log(beta[q] / beta[q + 1]));
+            v = v < rmin ? rmin : (v > rmax ? rmax : v);
+            if (!(v == v)) return mhx_fail(MHX_EINVAL, "%s: beta[%d] / beta[%d] = %g has no log log", me, q, q + 1, beta[q] / beta[q + 1]);
+            for (size_t c = (size_t)q; c < n; c += (size_t)R) h[c] = v;
+        }
+        for (size_t s = 1; s <= nrounds; ++s) h[n + s - 1] = (mhx_real)(a_c * std::pow((double)s, -a_kappa));
+        HIP_TRY(hipMalloc(&r->d_tadapt, (3 * n + nrounds) * sizeof(mhx_real)));
+        COPY_SYNC(ctx->stream, r->d_tadapt + 2 * n, h.data(), (n + nrounds) * sizeof(mhx_real), hipMemcpyHostToDevice);
+        r->tmp_adapt = true;
+        r->tmp_ad.rho = r->d_tadapt;
+        r->tmp_ad.beta = r->d_tadapt + n;
+        r->tmp_ad.gamma = r->d_tadapt + 3 * n;
+        r->tmp_ad.sigk = r->d_pvec;
+        r->tmp_ad.sigma = r->prop_scale;
+        r->tmp_ad.target_rate = (mhx_real)a_target;
+        r->tmp_ad.rho_min = rmin;
+        r->tmp_ad.rho_max = rmax;
+        r->tmp_ad.nrounds = (mhx_u32)nrounds;
+        if ((rc = tempered_reset_ladder(r.get()))) return rc;
+    }
+    // the adaptive kernels take the adaptation block where the fixed ones take the table
+    const void* tab = ac ? (const void*)&r->tmp_ad : (const void*)&r->d_ttab;
     const int tk = t->kind;
     // the register form addresses a [dim+1][nchains] slab with 32-bit byte offsets and holds x and y in VGPRs
     const bool small = ((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) < (1ull << 32);
@@ -96,28 +166,59 @@ int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_c
         const char* ut = opt(ctx, "REG_UNROLL");
         std::vector<std::string> xo = {"-mllvm", "-pragma-unroll-threshold=4000000"};
         if (!ut || atoi(ut) > 0) { xo.push_back("-mllvm"); xo.push_back(std::string("-amdgpu-unroll-threshold-private=") + (ut ? ut : "100000")); }
+        std::vector<std::string> rdefs = {"MHX_JIT_TEMPERED_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
+                                          "MHX_JIT_PK=" + std::to_string(r->prop_kind), "MHX_JIT_R=" + std::to_string(R)};
+        if (ac) rdefs.push_back("MHX_JIT_ADAPT=1");                // (a fixed ladder's defines, and so its kernel key, are what they were)
         rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_tempered_kernels.h"),
-                         {"MHX_JIT_TEMPERED_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
-                          "MHX_JIT_PK=" + std::to_string(r->prop_kind), "MHX_JIT_R=" + std::to_string(R)}, &m, xo);
+                         rdefs, &m, xo);
         // kernel(args, tparams, table, swap counters, swap_every): a lane per chain, one wave per block
-        r->step = rec_shape("tempered register kernel", 64, 64, 0, {&r->k_tp, &r->d_ttab, &r->d_swapc, &r->tmp_swap_every});
-        if (rc == MHX_OK) rc = rec_bind(&r->step, m, "mhx_jit_tempered_reg");
+        r->step = rec_shape("tempered register kernel", 64, 64, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every});
+        if (rc == MHX_OK) rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_reg" : "mhx_jit_tempered_reg");
         if (rc) return rc;
         r->fam_reg = true;                                  // (mhx_stats.register_form)
     }
     // ... else kernel(args, tparams, table, swap counters, swap_every, R): the state in HBM, whole ladders per 256-thread block
-    if (!r->fam_reg) r->step = rec_shape("tempered state-in-HBM kernel", 256, 256, 0, {&r->k_tp, &r->d_ttab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_R});
+    if (!r->fam_reg) r->step = rec_shape("tempered state-in-HBM kernel", 256, 256, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_R});
     if (tk == MHX_TARGET_USER) {
         jit_module* m = nullptr;
         if ((rc = jit_generic_rwmh(t, &m))) return rc;
         if ((rc = jit_function(m, "mhx_jit_rwmh_init", &r->jit_init))) return rc;
         if (!r->fam_reg) {
-            if ((rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_tempered_kernels.h"), {"MHX_JIT_TEMPERED_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)}, &m))) return rc;
-            if ((rc = rec_bind(&r->step, m, "mhx_jit_tempered_generic"))) return rc;
+            std::vector<std::string> gdefs = {"MHX_JIT_TEMPERED_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)};
+            if (ac) gdefs.push_back("MHX_JIT_ADAPT=1");
+            if ((rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_tempered_kernels.h"), gdefs, &m))) return rc;
+            if ((rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_generic" : "mhx_jit_tempered_generic"))) return rc;
         }
-    } else if (!r->fam_reg && (rc = rec_bind(&r->step, (const void*)k_tempered_generic))) return rc;
+    } else if (!r->fam_reg && (rc = rec_bind(&r->step, ac ? (const void*)k_tempered_adapt_generic : (const void*)k_tempered_generic))) return rc;
     if (!r->fam_reg) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
     *out = r.release();
+    return MHX_OK;
+}
+
+int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc, mhx_run** out)
+{
+    return tempered_create("mhx_rwmh_create_tempered", ctx, t, cfg, tc, nullptr, out);
+}
+
+int api_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc,
+                                      const mhx_ladder_adapt_cfg* ac, mhx_run** out)
+{
+    const char* me = "mhx_rwmh_create_tempered_adaptive";
+    if (!ac) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
+    return tempered_create(me, ctx, t, cfg, tc, ac, out);
+}
+
+// beta[n]: slot c's current temperature, widened exactly.  A fixed ladder: its table.
+int api_run_ladder_betas(mhx_run* r, double* beta)
+{
+    if (!r || !beta) return mhx_fail(MHX_EINVAL, "mhx_run_ladder_betas: NULL argument");
+    if (!r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_ladder_betas: not a tempered run (mhx_rwmh_create_tempered)");
+    HIP_TRY(hipSetDevice(r->ctx->device));
+    const size_t n = (size_t)r->n, R = (size_t)r->tmp_R;
+    std::vector<mhx_real> h(r->tmp_adapt ? n : R);
+    COPY_SYNC(r->ctx->stream, h.data(), r->tmp_adapt ? (const mhx_real*)r->tmp_ad.beta : (const mhx_real*)r->d_ttab, h.size() * sizeof(mhx_real),
+              hipMemcpyDeviceToHost);
+    for (size_t c = 0; c < n; ++c) beta[c] = (double)h[r->tmp_adapt ? c : c % R];
     return MHX_OK;
 }
 

@@ -139,6 +139,10 @@ void mhx_jit_unlock();
     bool api_run_is_derived(const mhx_run* r);                                                                         \
     int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                          \
                                  const mhx_tempered_cfg* tcfg, mhx_run** out);                                        \
+    int api_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                 \
+                                          const mhx_tempered_cfg* tcfg, const mhx_ladder_adapt_cfg* acfg,             \
+                                          mhx_run** out);                                                             \
+    int api_run_ladder_betas(mhx_run* r, double* beta);                                                               \
     int api_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps);                                          \
     int api_run_rung(mhx_run* src, int32_t rung, mhx_run** out);                                                      \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \

@@ -59,6 +59,12 @@ class TemperedCfg(C.Structure):
     _fields_ = [("R", C.c_int32), ("swap_every", C.c_int32), ("beta", C.c_void_p), ("scale", C.c_void_p)]
 
 
+class LadderAdaptCfg(C.Structure):
+    """mhx_ladder_adapt_cfg: how the ladders of a tempered run adapt; a NaN double takes its default"""
+    _fields_ = [("adapt_steps", C.c_int32), ("target_rate", C.c_double), ("c", C.c_double), ("kappa", C.c_double),
+                ("rho_min", C.c_double), ("rho_max", C.c_double)]
+
+
 class ProposalComponent(C.Structure):
     """mhx_proposal_component: one univariate component of a proposal, parameters as in Distributions.jl"""
     _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
@@ -140,6 +146,7 @@ EXPORTS = [
     "mhx_run_autocovariance", "mhx_ctx_autocovariance", "mhx_group_autocovariance",
     "mhx_run_derive", "mhx_ctx_derive", "mhx_run_predict", "mhx_ctx_predict", "mhx_run_pointwise", "mhx_ctx_pointwise",
     "mhx_run_psis", "mhx_ctx_psis", "mhx_rwmh_create_tempered", "mhx_run_swap_stats", "mhx_run_rung",
+    "mhx_rwmh_create_tempered_adaptive", "mhx_run_ladder_betas",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -307,6 +314,9 @@ def lib():
         L.mhx_rwmh_create_tempered.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), pvp]
         L.mhx_run_swap_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.mhx_run_rung.argtypes = [vp, C.c_int32, pvp]
+        if hasattr(L, "mhx_run_ladder_betas"):            # (an older build bound by use_library for an A/B run has neither)
+            L.mhx_rwmh_create_tempered_adaptive.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), C.POINTER(LadderAdaptCfg), pvp]
+            L.mhx_run_ladder_betas.argtypes = [vp, dp]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -944,14 +944,44 @@ def geometric_betas(R, beta_min):
     return b
 
 
-class Tempered:
-    """Tempered(sampler, betas, swap_every=1, scales=None) -- parallel tempering (replica exchange) around a random-walk sampler, what
-    MCMCTempering.jl wraps around AdvancedMH's samplers and emcee shipped as PTSampler.  `sampler`: an RWMH over an isotropic or
-    diagonal zero-mean MvNormal.  `betas`: the ladder, betas[0] == 1, strictly decreasing, a power of two of rungs (2..64).  Rung r
-    samples target^betas[r] with the proposal scaled by scales[r] (default betas[r]^(-1/2)); after every swap_every-th transition
-    neighbouring rungs may exchange their states.  `sample(model, Tempered(...), N, nladders)` returns the nladders cold chains."""
+class LadderAdaptation:
+    """LadderAdaptation(steps, target_rate=0.234, c=1.0, kappa=0.6, rho_min=None, rho_max=None) -- how the ladders of a Tempered
+    sampler tune their temperatures during the first `steps` transitions (mhx_ladder_adapt_cfg): after swap
+    round s every attempted pair moves rho, the log of its gap in log beta, by c * s^(-kappa) * (min(1, swap ratio) - target_rate),
+    clamped to [rho_min, rho_max] (None: the library's defaults, -10 and log(16 / (R - 1))).  What the library would refuse on every
+    ladder is refused here; the limit on rho_max depends on R and is the library's."""
 
-    def __init__(self, sampler, betas, swap_every=1, scales=None):
+    def __init__(self, steps, target_rate=0.234, c=1.0, kappa=0.6, rho_min=None, rho_max=None):
+        self.steps, self.target_rate, self.c, self.kappa = int(steps), float(target_rate), float(c), float(kappa)
+        self.rho_min = None if rho_min is None else float(rho_min)
+        self.rho_max = None if rho_max is None else float(rho_max)
+        if self.steps < 0:
+            raise L.ArgumentError(L.MHX_EINVAL, "LadderAdaptation: steps = %d must not be negative" % self.steps)
+        if not (0.5 < self.kappa <= 1.0):
+            raise L.ArgumentError(L.MHX_EINVAL, "LadderAdaptation: kappa = %g outside (0.5, 1]" % self.kappa)
+        if not (self.c >= 0.0 and np.isfinite(self.c)):
+            raise L.ArgumentError(L.MHX_EINVAL, "LadderAdaptation: c = %g must be finite and not negative" % self.c)
+        if not (0.0 < self.target_rate < 1.0):
+            raise L.ArgumentError(L.MHX_EINVAL, "LadderAdaptation: target_rate = %g outside (0, 1)" % self.target_rate)
+        if self.rho_min is not None and self.rho_max is not None and not (self.rho_min <= self.rho_max):
+            raise L.ArgumentError(L.MHX_EINVAL, "LadderAdaptation: rho_min = %g > rho_max = %g" % (self.rho_min, self.rho_max))
+
+    def cfg(self):
+        nan = float("nan")
+        return L.LadderAdaptCfg(self.steps, self.target_rate, self.c, self.kappa, nan if self.rho_min is None else self.rho_min,
+                                nan if self.rho_max is None else self.rho_max)
+
+
+class Tempered:
+    """Tempered(sampler, betas, swap_every=1, scales=None, adapt=None) -- parallel tempering (replica exchange) around a random-walk
+    sampler, what MCMCTempering.jl wraps around AdvancedMH's samplers and emcee shipped as PTSampler.  `sampler`: an RWMH over an
+    isotropic or diagonal zero-mean MvNormal.  `betas`: the ladder, betas[0] == 1, strictly decreasing, a power of two of rungs (2..64).
+    Rung r samples target^betas[r] with the proposal scaled by scales[r] (default betas[r]^(-1/2)); after every swap_every-th transition
+    neighbouring rungs may exchange their states.  `adapt`: a LadderAdaptation -- `betas` is then where every ladder starts and each
+    tunes its own temperatures from its own swaps (no `scales`: they follow the ladder).
+    `sample(model, Tempered(...), N, nladders)` returns the nladders cold chains."""
+
+    def __init__(self, sampler, betas, swap_every=1, scales=None, adapt=None):
         if not isinstance(sampler, MetropolisHastings) or not isinstance(sampler.proposal, RandomWalkProposal) or \
                 not isinstance(sampler.proposal.proposal, MvNormal):
             raise L.ArgumentError(L.MHX_EINVAL, "Tempered wraps an RWMH sampler over an isotropic or diagonal MvNormal")
@@ -964,10 +994,31 @@ class Tempered:
         self.scales = None if scales is None else np.ascontiguousarray(scales, dtype=np.float64).ravel()
         if self.scales is not None and self.scales.size != self.R:
             raise L.ArgumentError(L.MHX_EINVAL, "Tempered: %d scales for %d betas" % (self.scales.size, self.R))
+        if adapt is not None and not isinstance(adapt, LadderAdaptation):
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered: adapt must be a LadderAdaptation or None")
+        if adapt is not None and self.scales is not None:
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered: scales with adapt -- the proposal scales of an adaptive ladder follow its temperatures")
+        if adapt is not None and self.swap_every == 0:
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered: swap_every = 0 with adapt -- an adaptive ladder tunes itself from its swap rounds")
+        self.adapt = adapt
+
+
+class LadderTable(list):
+    """ladder() of a tempered run: one row {rung, beta_median, beta_min, beta_max, rate} per rung -- the temperature over the ladders
+    and the swap rate of the pair (rung, rung + 1) (NaN for the last rung)"""
+
+    def __str__(self):
+        out = ["rung   beta median         min         max  swap rate"]
+        for w in self:
+            out.append("%4d %13.5g %11.5g %11.5g %10.3f" % (w["rung"], w["beta_median"], w["beta_min"], w["beta_max"], w["rate"]))
+        return "\n".join(out)
+
+    __repr__ = __str__
 
 
 class SwapTable(list):
-    """swap_rates() of a tempered run: one row {pair, beta_lo, beta_hi, attempts, swaps, rate} per pair of neighbouring rungs"""
+    """swap_rates() of a tempered run: one row {pair, beta_lo, beta_hi, attempts, swaps, rate} per pair of neighbouring rungs (an
+    adaptive run: the betas are the medians over the ladders)"""
 
     def __str__(self):
         out = ["pair     beta_r    beta_r+1    attempts       swaps    rate"]
@@ -1770,7 +1821,12 @@ class Run:
             cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
             tcfg = L.TemperedCfg(sampler.R, sampler.swap_every, sampler.betas.ctypes.data,
                                  None if sampler.scales is None else sampler.scales.ctypes.data)
-            L.check(lib.mhx_rwmh_create_tempered(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(self.h)))
+            if sampler.adapt is None:
+                L.check(lib.mhx_rwmh_create_tempered(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(self.h)))
+            else:
+                acfg = sampler.adapt.cfg()
+                L.check(lib.mhx_rwmh_create_tempered_adaptive(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(acfg),
+                                                              C.byref(self.h)))
             self.n = nchains
             self.kind = "rwmh"
         elif isinstance(sampler, MetropolisHastings):
@@ -2348,9 +2404,25 @@ class Run:
         L.check(L.lib().mhx_run_swap_stats(self.h, att, sw))
         return np.array(att[:], dtype=np.uint64), np.array(sw[:], dtype=np.uint64)
 
+    def betas(self):
+        """the current inverse temperature of every slot, [nladders][R] float64 (mhx_run_ladder_betas): an adaptive run's ladders as
+        of the end of the last sample call, a fixed ladder's table in every row"""
+        R = self.sampler.R if getattr(self, "tempered", False) else 1
+        out = np.empty(self.n, dtype=np.float64)
+        L.check(L.lib().mhx_run_ladder_betas(self.h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out.reshape(-1, R)
+
+    def ladder(self):
+        """a printable table: per rung the median, minimum and maximum beta over the ladders and the swap rate of pair (rung, rung + 1)"""
+        b = self.betas()
+        att, sw = self.swap_stats()
+        rate = [float(sw[r]) / float(att[r]) if att[r] else float("nan") for r in range(len(att))] + [float("nan")]
+        return LadderTable(dict(rung=r, beta_median=float(np.median(b[:, r])), beta_min=float(b[:, r].min()), beta_max=float(b[:, r].max()),
+                                rate=rate[r]) for r in range(b.shape[1]))
+
     def swap_rates(self):
         att, sw = self.swap_stats()
-        b = self.sampler.betas
+        b = self.sampler.betas if self.sampler.adapt is None else np.median(self.betas(), axis=0)
         return SwapTable(dict(pair=(r, r + 1), beta_lo=float(b[r]), beta_hi=float(b[r + 1]), attempts=int(att[r]), swaps=int(sw[r]),
                               rate=(float(sw[r]) / float(att[r]) if att[r] else float("nan"))) for r in range(len(att)))
 
@@ -2470,6 +2542,10 @@ def sample(model, sampler, N, nchains=1, *more, initial_params=None, discard_ini
         model = LogDensityModel(model)              # sample(problem, sampler, N): AbstractMCMC wraps what implements the interface
     if isinstance(sampler, Tempered):              # sample(model, Tempered(...), N, nladders): R device chains per ladder
         nchains = int(nchains) * sampler.R
+        if sampler.adapt is not None and discard_initial < sampler.adapt.steps:
+            raise L.ArgumentError(L.MHX_EINVAL, "sample: discard_initial = %d < adapt.steps = %d -- draws taken while the ladder moves are "
+                                  "not draws of the target: discard at least the adapting transitions (discard_initial >= adapt.steps)"
+                                  % (discard_initial, sampler.adapt.steps))
     run = Run(model, sampler, nchains=nchains, seed=seed, first_chain=first_chain, ctx=ctx, flags=flags,
               reduce_lanes=reduce_lanes, dtype=dtype, normal_gen=normal_gen)
     run.init(initial_params)

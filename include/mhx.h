@@ -525,7 +525,8 @@ typedef struct {
                                   symmetric flag and parameter map; lane per chain, compiled at run time, the same two forms,
                                   16 a tempered run (mhx_rwmh_create_tempered): ladders of temperatures in consecutive lanes, swaps
                                   across lanes inside the step kernel; the run-time specialised register form or the state-in-HBM
-                                  form (pre-built for the catalogue targets), the same chain */
+                                  form (pre-built for the catalogue targets), the same chain,
+                                  17 a tempered run whose ladders adapt (mhx_rwmh_create_tempered_adaptive): the same two forms */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
@@ -534,7 +535,7 @@ typedef struct {
                                   (0 = diagonal, 1 = bidiagonal: an AR(1) / Markov model, ...), -1 = none (dense form, other samplers) */
     int32_t tainted;           /* 1: a probe / fault-injection option of the tools build was set on the run's context -- the chains of
                                   such a run may be INVALID (timing probes skip work).  Always 0 from libmhx.so. */
-    int32_t register_form;     /* kernel variants 13, 14, 15 and 16: 1 = the run is stepped by the run-time specialised register form, 0 = by
+    int32_t register_form;     /* kernel variants 13 .. 17: 1 = the run is stepped by the run-time specialised register form, 0 = by
                                   the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
@@ -996,6 +997,32 @@ int mhx_run_swap_stats(mhx_run *run, uint64_t *attempts, uint64_t *swaps);
  * from columns r, r + R, r + 2R, ... of the sample tensor; it inherits seed and first_chain as a derived run does and every post-run
  * statistic reads it like any run.  MHX_EINVAL: r out of range; MHX_ESTATE: not a tempered run, or no sample tensor.  Blocking. */
 int mhx_run_rung(mhx_run *run, int32_t r, mhx_run **out);
+/* An adaptive ladder: every ladder tunes its own temperatures from its own swap rounds while the run warms
+ * up, inside the step kernel -- no second kernel, no trip to the host; there is no shared ladder and no reduction over ladders, so a
+ * shard is still the matching columns of the larger run and two calls are one.  The ladder is parametrised by rho[r], the log of the
+ * gap of pair (r, r + 1) in log beta: beta[r] = exp(-sum_{q < r} exp(rho[q])), the proposal scale of rung r is beta[r]^(-1/2), and
+ * after swap round s with s * swap_every <= adapt_steps every attempted pair moves
+ *     rho[r] += c * s^(-kappa) * (min(1, swap ratio) - target_rate),   clamped to [rho_min, rho_max]
+ * (the "Geometric" schedule of Miasojedow, Moulines and Vihola as MCMCTempering.jl implements it).  After adapt_steps transitions the
+ * ladder is frozen.  tcfg.beta is the ladder the run starts from (rho0 = log log (beta[r] / beta[r + 1]), clamped).  Draws taken while
+ * the ladder moves are not draws of the target: discard at least adapt_steps transitions.
+ *     adapt_steps  >= 0 transitions; 0: the ladder of rho0 for the whole run
+ *     a double field that is NaN takes its default: target_rate 0.234, c 1, kappa 0.6, rho_min -10, rho_max log(16 / (R - 1)).  (0 is
+ *     a value like any other -- c = 0 is the ladder that never moves -- so NaN is the one encoding of "default" for all five.)
+ * MHX_EINVAL with a message that names the rule for everything mhx_rwmh_create_tempered refuses, and for: swap_every == 0, tcfg.scale
+ * given (the scales follow the ladder), adapt_steps < 0, kappa outside (0.5, 1], c < 0, target_rate outside (0, 1), rho_min > rho_max,
+ * (R - 1) exp(rho_max) > 80 (the coldest beta would leave fp32's normal range).  The run is kernel variant 17; mhx_run_swap_stats and
+ * mhx_run_rung work on it; it refuses what a fixed ladder refuses (MHX_SAVE_MOMENTS, mhx_run_sample_to_host, checkpoints, mhx_group_attach). */
+typedef struct {
+    int32_t adapt_steps;
+    double target_rate, c, kappa, rho_min, rho_max;
+} mhx_ladder_adapt_cfg;
+int mhx_rwmh_create_tempered_adaptive(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_tempered_cfg *tcfg,
+                                      const mhx_ladder_adapt_cfg *acfg, mhx_run **out);
+/* beta[nchains]: slot c's current inverse temperature, widened exactly from the run's width (slot c is rung c mod R of ladder c div R).
+ * An adaptive run: as of the end of the last mhx_run_sample (after create or mhx_run_init: the ladder of rho0); a fixed ladder: its
+ * table.  MHX_ESTATE: not a tempered run.  Blocking. */
+int mhx_run_ladder_betas(mhx_run *run, double *beta);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process. Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`

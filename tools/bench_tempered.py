@@ -12,7 +12,17 @@ is compiled and loaded, the chains leave their start), then the configurations a
 of each is reported with its spread.  Each width runs in a child process of its own under a time limit; a width that fails ends the
 run.
 
-    bench_tempered.py [OUT.json]        default OUT: profiles/tempered_bench.json"""
+    bench_tempered.py [OUT.json]        default OUT: profiles/tempered_bench.json
+
+--adapt measures the adaptive ladder (kernel variant 17) at the same shape instead, in milliseconds of kernel time per step of all
+chains, the three configurations timed in turn as above:
+  (fixed)    the geometric ladder with swap_every = 1: (d) above
+  (adapting) the same start, LadderAdaptation over more transitions than the run makes: every swap round moves rho and derives the ladder
+  (frozen)   LadderAdaptation(0): the adaptive kernel on the ladder of rho0, which is (fixed)'s up to rounding, never adapting
+--lib PATH adds (fixed) measured on another build of the library (the parent commit's, say), in child processes of its own that
+alternate with children that time (fixed) alone on this build: the fixed ladder's code path must not have moved.
+
+    bench_tempered.py --adapt [--lib OTHER/libmhx.so] [OUT.json]        default OUT: profiles/tempered_adaptive_bench.json"""
 import json
 import os
 import subprocess
@@ -69,6 +79,83 @@ def measure(dt):
     return row
 
 
+def measure_adapt(dt, lib=None):
+    """lib None: the three configurations on this build; a path, or "-" for this build: (fixed) alone, the A/B children"""
+    import mhx
+    if lib and lib != "-":
+        mhx.use_library(lib)
+    s = float(np.float32(2.38 / D ** 0.5))
+    rw = mhx.RWMH(mhx.MvNormal(mhx.zeros(D), (s * s) * mhx.I))
+    ladder = mhx.geometric_betas(R, 0.05)
+    configs = [("fixed", mhx.Tempered(rw, ladder, swap_every=1))]
+    if not lib:
+        configs += [("adapting", mhx.Tempered(rw, ladder, swap_every=1, adapt=mhx.LadderAdaptation(1 << 20))),
+                    ("frozen", mhx.Tempered(rw, ladder, swap_every=1, adapt=mhx.LadderAdaptation(0)))]
+    model = mhx.DensityModel(mhx.IsoGaussian(D))
+    runs = {}
+    for name, spl in configs:
+        run = mhx.Run(model, spl, nchains=C, seed=1, reduce_lanes=1, dtype=dt)
+        run.init(np.zeros(D))
+        run.sample(STEPS, 50, 1, 0)
+        runs[name] = run
+    ms = {name: [] for name in runs}
+    for _ in range(REPEATS):
+        for name, run in runs.items():
+            run.sample(STEPS, 1, 1, 0)
+            st = run.stats()
+            ms[name].append(st["kernel_ms"] / (st["transitions"] / C))
+    row = {}
+    for name, run in runs.items():
+        st = run.stats()
+        v = np.array(ms[name])
+        att, swp = run.swap_stats()
+        row[name] = dict(ms_per_step=float(np.median(v)), min=float(v.min()), max=float(v.max()), kernel_variant=st["kernel_variant"],
+                         form=run.form_name(), swap_rate=float(swp.sum()) / float(att.sum()))
+        run.close()
+    return row
+
+
+def child(args):
+    done = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, stdout=subprocess.PIPE, text=True, timeout=STEP_LIMIT_S)
+    if done.returncode != 0:
+        print("bench_tempered: the step %s ended with status %d; nothing more is started" % (args, done.returncode), flush=True)
+        return None
+    return json.loads(done.stdout.strip().splitlines()[-1])
+
+
+def main_adapt(out, lib):
+    result = dict(dim=D, R=R, nchains=C, recorded_steps=STEPS, repeats=REPEATS, target="IsoGaussian",
+                  unit="milliseconds of kernel time per step of all chains")
+    for dt in ("f64", "f32"):
+        row = child(["--one-adapt", dt])
+        if row is None:
+            return 1
+        if lib:
+            # the other build and this one in turn, a child process each that times (fixed) ALONE -- the same process on both sides,
+            # not (fixed) between two other kernels on one of them: medians of the children's medians
+            other, this = [], []
+            for i in range(3):
+                a, b = child(["--one-adapt", dt, lib]), child(["--one-adapt", dt, "-"])
+                if a is None or b is None:
+                    return 1
+                other.append(a["fixed"]["ms_per_step"])
+                this.append(b["fixed"]["ms_per_step"])
+            row["fixed_other_build"] = dict(ms_per_step=float(np.median(other)), runs=other)
+            row["fixed_this_build"] = dict(ms_per_step=float(np.median(this)), runs=this)
+            row["fixed_this_over_other"] = float(np.median(this) / np.median(other))
+        row["adapting_over_fixed"] = row["adapting"]["ms_per_step"] / row["fixed"]["ms_per_step"]
+        row["frozen_over_fixed"] = row["frozen"]["ms_per_step"] / row["fixed"]["ms_per_step"]
+        # an adapting round per step: its time per chain-step, in nanoseconds of kernel time
+        row["adapting_round_ns_per_chain_step"] = (row["adapting"]["ms_per_step"] - row["frozen"]["ms_per_step"]) * 1e6 / C
+        result[dt] = row
+        print(json.dumps({dt: row}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    return 0
+
+
 def main(out):
     result = dict(dim=D, R=R, nchains=C, recorded_steps=STEPS, repeats=REPEATS, target="IsoGaussian", unit="chain-steps per second of kernel time")
     for dt in ("f64", "f32"):
@@ -89,4 +176,13 @@ if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--one":
         print(json.dumps(measure(sys.argv[2])), flush=True)
         sys.exit(0)
+    if len(sys.argv) > 2 and sys.argv[1] == "--one-adapt":
+        print(json.dumps(measure_adapt(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)), flush=True)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--adapt":
+        rest = sys.argv[2:]
+        lib = None
+        if rest and rest[0] == "--lib":
+            lib, rest = os.path.abspath(rest[1]), rest[2:]
+        sys.exit(main_adapt(rest[0] if rest else os.path.join(ROOT, "profiles", "tempered_adaptive_bench.json"), lib))
     sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "tempered_bench.json")))
