@@ -14,6 +14,14 @@ int mhx_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const m
     NEED_SAME(rwmh_create_tempered_adaptive, ctx, t, cfg, tcfg, acfg, out);
 }
 
+int mhx_rwmh_create_tempered_anchored(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tcfg,
+                                      const mhx_tempered_reference* ref, mhx_run** out)
+{
+    NEED_SAME(rwmh_create_tempered_anchored, ctx, t, cfg, tcfg, ref, out);
+}
+
+int mhx_run_evidence(mhx_run* r, double* out, int64_t* n_saved) { NEED_SAMPLER(run_evidence, r, out, n_saved); }
+
 int mhx_run_ladder_betas(mhx_run* r, double* beta) { NEED_SAMPLER(run_ladder_betas, r, beta); }
 
 int mhx_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps) { NEED_SAMPLER(run_swap_stats, r, attempts, swaps); }

@@ -30,6 +30,7 @@
 #include "mhx_rwmh_cond_kernels.h"
 #include "mhx_rwmh_composite_kernels.h"
 #include "mhx_rwmh_tempered_kernels.h"
+#include "mhx_evidence_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
 #include "mhx_mala_kernels.h"
@@ -855,6 +856,7 @@ enum kernel_form {
     KF_COMPOSITE = 15,      // ... and whose kind, symmetric flag and parameter map vary per block of components (a composite proposal)
     KF_TEMPERED = 16,       // parallel tempering of the plain random walk: specialised register form or state in HBM (mhx_api_tempered.inc)
     KF_TEMPERED_ADAPT = 17, // ... whose ladders tune their temperatures from their swaps while the run warms up: the same two forms
+    KF_TEMPERED_ANCHOR = 18, // ... whose rungs temper towards a normalised reference density, down to beta = 0: the same two forms
 };
 
 // One kernel of a run, ready to launch: everything the host needs for it, filled ONCE, in the branch of a create function that
@@ -950,6 +952,11 @@ struct mhx_run : mhx_handle_hdr {
     bool tmp_adapt = false;
     mhx_real* d_tadapt = nullptr;           // rho[n] | beta[n] | rho0[n] | gamma[adapt_steps / swap_every]
     mhx_tmp_adapt tmp_ad{};                 // the step kernel's adaptation block: pointers into d_tadapt and d_pvec, the constants
+    // KF_TEMPERED_ANCHOR: everything of KF_TEMPERED, and
+    bool tmp_anchor = false;
+    bool tmp_beta_end_zero = false;         // the ladder reaches the reference itself (mhx_run_evidence)
+    mhx_real* d_tanchor = nullptr;          // omb[R] | m[dim] | w[dim]
+    mhx_tmp_anchor tmp_an{};                // the step kernel's reference block: pointers into d_tanchor, lc
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -1026,7 +1033,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc, d_tadapt};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc, d_tadapt, d_tanchor};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (acc_total_pin) (void)hipHostFree(acc_total_pin);
     }
@@ -2131,6 +2138,7 @@ const char* api_run_form_name(const mhx_run* r)
     case KF_RAM_DEFER: return "ram_defer";
     case KF_TEMPERED: return r->fam_reg ? "tempered_reg" : "tempered_generic";
     case KF_TEMPERED_ADAPT: return r->fam_reg ? "tempered_adapt_reg" : "tempered_adapt_generic";
+    case KF_TEMPERED_ANCHOR: return r->fam_reg ? "tempered_anchored_reg" : "tempered_anchored_generic";
     case KF_FAMILY: return "family";
     case KF_COND: return "cond";
     case KF_COMPOSITE: return "composite";
@@ -2337,6 +2345,7 @@ static sweep_plan pointwise_sweep_plan(const draws_view& v, long ntiles)
 #include "mhx_api_acf.inc"
 #include "mhx_api_derive.inc"
 #include "mhx_api_tempered.inc"
+#include "mhx_api_evidence.inc"
 #include "mhx_api_pointwise.inc"
 #include "mhx_api_psis.inc"
 

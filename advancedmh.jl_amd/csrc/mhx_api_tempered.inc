@@ -17,6 +17,13 @@ k_tempered_adapt_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tpa
 {
     mhx_tmp_generic_body<MHX_TARGET_DYNAMIC, true>(a, tparams, nullptr, swapc, swap_every, R, &ad);
 }
+// ... of an anchored ladder (mhx_rwmh_create_tempered_anchored)
+__global__ void __launch_bounds__(256)
+k_tempered_anchored_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                            mhx_u32* __restrict__ swapc, const int swap_every, const int R, const mhx_tmp_anchor an)
+{
+    mhx_tmp_generic_body<MHX_TARGET_DYNAMIC, false, true>(a, tparams, tt, swapc, swap_every, R, nullptr, &an);
+}
 __global__ void __launch_bounds__(256)
 k_tempered_derive(const mhx_tmp_adapt ad, const int nchains, const int R) { mhx_tmp_derive_body(ad, nchains, R); }
 __global__ void __launch_bounds__(256)
@@ -37,8 +44,9 @@ static int tempered_reset_ladder(mhx_run* r)
 }
 
 // `ac` NULL: a fixed ladder (mhx_rwmh_create_tempered); else the ladder adapts (mhx_rwmh_create_tempered_adaptive, DESIGN.md section 3.17.1)
+// `ref`: a fixed ladder anchored at a reference density (mhx_rwmh_create_tempered_anchored, DESIGN.md section 3.17.2); never with `ac`
 static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc,
-                           const mhx_ladder_adapt_cfg* ac, mhx_run** out)
+                           const mhx_ladder_adapt_cfg* ac, const mhx_tempered_reference* ref, mhx_run** out)
 {
     if (!ctx || !t || !cfg || !tc || !out) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
     if (cfg->dim != t->dim) return mhx_fail(MHX_EINVAL, "%s: proposal dim %d != model dim %d", me, cfg->dim, t->dim);
@@ -70,6 +78,28 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
     const double* beta = (const double*)tc->beta;
     const double* scale = (const double*)tc->scale;
     if (!beta) return mhx_fail(MHX_EINVAL, "%s: beta is NULL", me);
+    // ---- an anchored ladder: the reference's tables in the run's width, m[d] | w[d], and lc
+    std::vector<mhx_real> ta;
+    mhx_real ref_lc = MHX_R(0.0);
+    if (ref) {
+        const double* rm = (const double*)ref->mean;
+        const double* rs = (const double*)ref->sd;
+        if (!rm || !rs) return mhx_fail(MHX_EINVAL, "%s: the reference's %s is NULL", me, rm ? "sd" : "mean");
+        ta.assign((size_t)R + 2 * (size_t)d, MHX_R(0.0));
+        double lc = 0.0;
+        for (int k = 0; k < d; ++k) {
+            if (!std::isfinite(rm[k])) return mhx_fail(MHX_EINVAL, "%s: reference mean[%d] = %g is not finite", me, k, rm[k]);
+            if (!std::isfinite(rs[k])) return mhx_fail(MHX_EINVAL, "%s: reference sd[%d] = %g is not finite", me, k, rs[k]);
+            if (!(rs[k] > 0.0)) return mhx_fail(MHX_EINVAL, "%s: reference sd[%d] = %g -- every standard deviation is positive (the reference is a proper density)", me, k, rs[k]);
+            ta[(size_t)R + k] = (mhx_real)rm[k];
+            ta[(size_t)R + d + k] = (mhx_real)(1.0 / rs[k]);                                     // one division in double, rounded once
+            if (!std::isfinite((double)ta[(size_t)R + d + k]) || !(ta[(size_t)R + d + k] > MHX_R(0.0)))
+                return mhx_fail(MHX_EINVAL, "%s: 1 / reference sd[%d] = %g leaves the run's width", me, k, 1.0 / rs[k]);
+            lc -= std::log(rs[k]);
+        }
+        lc -= 0.5 * (double)d * std::log(2.0 * 3.14159265358979323846);
+        ref_lc = (mhx_real)lc;
+    }
     // ---- an adaptive ladder: NaN in a field of the cfg = its default
     double a_target = 0.234, a_c = 1.0, a_kappa = 0.6, a_rmin = -10.0, a_rmax = std::log(16.0 / (double)(R - 1));
     if (ac) {
@@ -94,9 +124,16 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
     const bool iso = cfg->proposal_kind == MHX_PROP_ISO;
     std::vector<mhx_real> tt((size_t)2 * R + (size_t)R * (iso ? 1 : (size_t)d), MHX_R(0.0));
     if (beta[0] != 1.0) return mhx_fail(MHX_EINVAL, "%s: beta[0] = %g must be exactly 1 (rung 0 is the chain that is read)", me, beta[0]);
+    bool end_zero = false;
     for (int r = 0; r < R; ++r) {
         tt[(size_t)r] = (mhx_real)beta[r];
-        if (!(beta[r] > 0.0) || !(tt[(size_t)r] > MHX_R(0.0)) || !std::isfinite(beta[r]))
+        if (ref && beta[r] == 0.0) {                                // an anchored ladder may END at the reference itself
+            if (r != R - 1)
+                return mhx_fail(MHX_EINVAL, "%s: beta[%d] = 0 is not the last rung -- only the last inverse temperature of an anchored ladder may be 0", me, r);
+            if (!scale)
+                return mhx_fail(MHX_EINVAL, "%s: beta[%d] = 0 without scale[] -- the default proposal scale beta^(-1/2) has no value there: give scale[]", me, r);
+            end_zero = true;
+        } else if (!(beta[r] > 0.0) || !(tt[(size_t)r] > MHX_R(0.0)) || !std::isfinite(beta[r]))
             return mhx_fail(MHX_EINVAL, "%s: beta[%d] = %g -- every inverse temperature is positive (in the run's width too)", me, r, beta[r]);
         // (no swap rounds: equal temperatures are allowed, so that the cost of the frame can be timed against the plain run)
         if (r && (tc->swap_every > 0 ? !(tt[(size_t)r] < tt[(size_t)r - 1]) : !(tt[(size_t)r] <= tt[(size_t)r - 1])))
@@ -118,7 +155,7 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
     r->dim = d; r->n = cfg->nchains; r->seed = cfg->seed; r->first_id = cfg->first_chain;
     r->flags = cfg->flags;
     r->prop_kind = cfg->proposal_kind; r->prop_scale = (mhx_real)cfg->proposal_scale;          // (the initial draw is the plain run's)
-    r->variant = ac ? KF_TEMPERED_ADAPT : KF_TEMPERED;
+    r->variant = ac ? KF_TEMPERED_ADAPT : (ref ? KF_TEMPERED_ANCHOR : KF_TEMPERED);
     r->tmp_R = R; r->tmp_swap_every = tc->swap_every;
     HIP_TRY(hipMalloc(&r->d_pvec, (iso ? 1 : (size_t)d) * sizeof(mhx_real)));
     if (!iso) COPY_SYNC(ctx->stream, r->d_pvec, cfg_vec, (size_t)d * sizeof(mhx_real), hipMemcpyHostToDevice);
@@ -128,6 +165,17 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
     HIP_TRY(hipMemsetAsync(r->d_swapc, 0, 2 * (size_t)r->n * sizeof(uint32_t), ctx->stream));
     int rc = run_alloc_state(r.get());
     if (rc) return rc;
+    if (ref) {
+        for (int q = 0; q < R; ++q) ta[(size_t)q] = MHX_R(1.0) - tt[(size_t)q];                  // one subtraction of the rounded betas
+        HIP_TRY(hipMalloc(&r->d_tanchor, ta.size() * sizeof(mhx_real)));
+        COPY_SYNC(ctx->stream, r->d_tanchor, ta.data(), ta.size() * sizeof(mhx_real), hipMemcpyHostToDevice);
+        r->tmp_anchor = true;
+        r->tmp_beta_end_zero = end_zero;
+        r->tmp_an.omb = r->d_tanchor;
+        r->tmp_an.m = r->d_tanchor + R;
+        r->tmp_an.w = r->d_tanchor + R + d;
+        r->tmp_an.lc = ref_lc;
+    }
     if (ac) {
         // rho0[r] = log(log(beta[r] / beta[r + 1])) in double, rounded once, clamped in the width; gamma[s] = c s^(-kappa), s = 1 ..
         // adapt_steps / swap_every, one pow and one product in double, rounded once.  d_tadapt: rho[n] | beta[n] | rho0[n] | gamma[nrounds]
@@ -160,7 +208,7 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
     const int tk = t->kind;
     // the register form addresses a [dim+1][nchains] slab with 32-bit byte offsets and holds x and y in VGPRs
     const bool small = ((uint64_t)d + 1) * (uint64_t)r->n * (uint64_t)sizeof(mhx_real) < (1ull << 32);
-    if (!(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && small && d <= MHX_TEMPERED_REG_MAX_DIM &&
+    if (!(r->flags & (MHX_FLAG_GENERIC | MHX_FLAG_NO_JIT)) && small && (ref ? d <= MHX_TEMPERED_ANCHORED_REG_MAX_DIM : d <= MHX_TEMPERED_REG_MAX_DIM) &&
         !(tk == MHX_TARGET_CORR_GAUSS && d > (MHX_REAL64 ? 32 : 64)) && !(tk == MHX_TARGET_IID_NORMAL && t->nparams > 4096)) {
         jit_module* m = nullptr;
         const char* ut = opt(ctx, "REG_UNROLL");
@@ -169,16 +217,20 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
         std::vector<std::string> rdefs = {"MHX_JIT_TEMPERED_REG=1", "MHX_JIT_DIM=" + std::to_string(d), "MHX_JIT_TK=" + std::to_string(tk),
                                           "MHX_JIT_PK=" + std::to_string(r->prop_kind), "MHX_JIT_R=" + std::to_string(R)};
         if (ac) rdefs.push_back("MHX_JIT_ADAPT=1");                // (a fixed ladder's defines, and so its kernel key, are what they were)
+        if (ref) rdefs.push_back("MHX_JIT_ANCHOR=1");
         rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_tempered_kernels.h"),
                          rdefs, &m, xo);
         // kernel(args, tparams, table, swap counters, swap_every): a lane per chain, one wave per block
-        r->step = rec_shape("tempered register kernel", 64, 64, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every});
-        if (rc == MHX_OK) rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_reg" : "mhx_jit_tempered_reg");
+        // (an anchored ladder: the reference block after them)
+        if (ref) r->step = rec_shape("tempered register kernel", 64, 64, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_an});
+        else r->step = rec_shape("tempered register kernel", 64, 64, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every});
+        if (rc == MHX_OK) rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_reg" : (ref ? "mhx_jit_tempered_anchored_reg" : "mhx_jit_tempered_reg"));
         if (rc) return rc;
         r->fam_reg = true;                                  // (mhx_stats.register_form)
     }
     // ... else kernel(args, tparams, table, swap counters, swap_every, R): the state in HBM, whole ladders per 256-thread block
-    if (!r->fam_reg) r->step = rec_shape("tempered state-in-HBM kernel", 256, 256, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_R});
+    if (!r->fam_reg && ref) r->step = rec_shape("tempered state-in-HBM kernel", 256, 256, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_R, &r->tmp_an});
+    else if (!r->fam_reg) r->step = rec_shape("tempered state-in-HBM kernel", 256, 256, 0, {&r->k_tp, tab, &r->d_swapc, &r->tmp_swap_every, &r->tmp_R});
     if (tk == MHX_TARGET_USER) {
         jit_module* m = nullptr;
         if ((rc = jit_generic_rwmh(t, &m))) return rc;
@@ -186,10 +238,12 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
         if (!r->fam_reg) {
             std::vector<std::string> gdefs = {"MHX_JIT_TEMPERED_GENERIC=1", "MHX_JIT_TK=" + std::to_string(tk)};
             if (ac) gdefs.push_back("MHX_JIT_ADAPT=1");
+            if (ref) gdefs.push_back("MHX_JIT_ANCHOR=1");
             if ((rc = jit_compile(ctx, jit_source(t, "mhx_rwmh_tempered_kernels.h"), gdefs, &m))) return rc;
-            if ((rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_generic" : "mhx_jit_tempered_generic"))) return rc;
+            if ((rc = rec_bind(&r->step, m, ac ? "mhx_jit_tempered_adapt_generic" : (ref ? "mhx_jit_tempered_anchored_generic" : "mhx_jit_tempered_generic")))) return rc;
         }
-    } else if (!r->fam_reg && (rc = rec_bind(&r->step, ac ? (const void*)k_tempered_adapt_generic : (const void*)k_tempered_generic))) return rc;
+    } else if (!r->fam_reg && (rc = rec_bind(&r->step, ac ? (const void*)k_tempered_adapt_generic
+                                                          : (ref ? (const void*)k_tempered_anchored_generic : (const void*)k_tempered_generic)))) return rc;
     if (!r->fam_reg) HIP_TRY(hipMalloc(&r->d_ybuf, (size_t)d * (size_t)r->n * sizeof(mhx_real)));
     *out = r.release();
     return MHX_OK;
@@ -197,7 +251,15 @@ static int tempered_create(const char* me, mhx_ctx* ctx, const mhx_target* t, co
 
 int api_rwmh_create_tempered(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc, mhx_run** out)
 {
-    return tempered_create("mhx_rwmh_create_tempered", ctx, t, cfg, tc, nullptr, out);
+    return tempered_create("mhx_rwmh_create_tempered", ctx, t, cfg, tc, nullptr, nullptr, out);
+}
+
+int api_rwmh_create_tempered_anchored(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc,
+                                      const mhx_tempered_reference* ref, mhx_run** out)
+{
+    const char* me = "mhx_rwmh_create_tempered_anchored";
+    if (!ref) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
+    return tempered_create(me, ctx, t, cfg, tc, nullptr, ref, out);
 }
 
 int api_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg, const mhx_tempered_cfg* tc,
@@ -205,7 +267,7 @@ int api_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const m
 {
     const char* me = "mhx_rwmh_create_tempered_adaptive";
     if (!ac) return mhx_fail(MHX_EINVAL, "%s: NULL argument", me);
-    return tempered_create(me, ctx, t, cfg, tc, ac, out);
+    return tempered_create(me, ctx, t, cfg, tc, ac, nullptr, out);
 }
 
 // beta[n]: slot c's current temperature, widened exactly.  A fixed ladder: its table.

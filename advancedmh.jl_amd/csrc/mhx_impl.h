@@ -142,6 +142,10 @@ void mhx_jit_unlock();
     int api_rwmh_create_tempered_adaptive(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                 \
                                           const mhx_tempered_cfg* tcfg, const mhx_ladder_adapt_cfg* acfg,             \
                                           mhx_run** out);                                                             \
+    int api_rwmh_create_tempered_anchored(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                 \
+                                          const mhx_tempered_cfg* tcfg, const mhx_tempered_reference* ref,            \
+                                          mhx_run** out);                                                             \
+    int api_run_evidence(mhx_run* r, double* out, int64_t* n_saved);                                                  \
     int api_run_ladder_betas(mhx_run* r, double* beta);                                                               \
     int api_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps);                                          \
     int api_run_rung(mhx_run* src, int32_t rung, mhx_run** out);                                                      \

@@ -25,6 +25,9 @@
 // sig[R] (ISO) or sig[R][dim] (DIAG).  `swapc`: [2][nchains] u32, attempts then swaps of pair (r, r + 1), kept by the lower slot.
 // Both bodies have an ADAPT variant (a template bool; MHX_JIT_ADAPT for the run-time kernels) in which every ladder tunes its
 // temperatures from its own swap rounds: see mhx_tmp_adapt below.  With ADAPT false nothing of it is compiled in.
+// ... and an ANCHOR variant (a template bool; MHX_JIT_ANCHOR) in which rung r samples target^beta[r] * q^(1 - beta[r]) for a normalised
+// reference density q, so that beta = 0 is a legal last rung and the ladder carries the evidence: see mhx_tmp_anchor below.  With
+// ANCHOR false nothing of it is compiled in either.
 #pragma once
 #include "mhx_rwmh_kernels.h"
 
@@ -41,6 +44,53 @@ MHX_NS_BEGIN
 // size tried.  Above it the state-in-HBM form runs.  The adaptive variant (below) holds the limit too: it keeps no per-lane scales
 // (DIAG: 460 registers in fp64, 433 in fp32) and a few more reals of its own (ISO: 452 / 426); tests/test_tempered_adaptive_cpu.py.
 #define MHX_TEMPERED_REG_MAX_DIM (MHX_REAL64 ? 48 : 80)
+// ... and of the anchored variant (below), which carries lq and forms lqy beside the target's own value.  Measured the same way:
+// fp64 clean at 44 (DIAG: 496 registers; 460 at 40), scratch at 48 (DIAG, 84 bytes; ISO is clean there with 442); fp32 clean at 76
+// (DIAG: 501; 479 at 72), scratch at 80 (DIAG, 44 bytes; ISO is clean with 445).  tests/test_tempered_anchored_cpu.py compiles both.
+#define MHX_TEMPERED_ANCHORED_REG_MAX_DIM (MHX_REAL64 ? 44 : 76)
+
+// ---------------------------------------------------------------------------------------------
+// An anchored ladder: rung r samples target^beta[r] * q^(1 - beta[r]), q a diagonal Gaussian of known
+// normaliser, so the last rung may sit at beta = 0 (it samples q, restricted to the target's support) and the path from beta = 1 to 0
+// integrates to the log evidence (mhx_evidence_kernels.h).  Everything here is wave-uniform: a lane keeps of it only omb of its rung
+// and lq of its state.  Built on the host: w[k] = 1 / sd[k] and m[k], rounded once; lc = -sum log sd[k] - (d / 2) log 2 pi in double,
+// rounded once; omb[r] = 1 - beta[r] of the rounded betas.
+struct mhx_tmp_anchor {
+    const mhx_real* m;           // [dim] the reference's mean
+    const mhx_real* w;           // [dim] 1 / sd
+    const mhx_real* omb;         // [R] 1 - beta
+    mhx_real lc;                 // the log of the reference's normaliser
+};
+// log q(x): z = (x[k] - m[k]) * w[k], acc = fma(z, z, acc) for k ascending from 0, lq = fma(-0.5, acc, lc).  A pure function of the
+// state: the step kernels recompute it at the start of every launch, the evidence sweep per draw.  d: the loop's extent (a constant
+// where x is a register array).
+template <class X>
+MHX_DEV mhx_real mhx_tmp_logq(const X& x, const int d, const mhx_tmp_anchor& an)
+{
+    mhx_real acc = MHX_R(0.0);
+#pragma unroll
+    for (int k = 0; k < d; ++k) {
+        const mhx_real z = (x[k] - an.m[k]) * an.w[k];
+        acc = mhx_fma(z, z, acc);
+    }
+    return mhx_fma(MHX_R(-0.5), acc, an.lc);
+}
+// what a lane of an anchored ladder carries through a launch; nothing where the ladder is not anchored
+template <bool ANCHOR>
+struct mhx_tmp_lq {};
+template <>
+struct mhx_tmp_lq<true> {
+    mhx_real lq;                 // log q of the state
+    mhx_real lqy;                // ... of the candidate
+    mhx_real omb;                // 1 - beta of the lane's rung
+};
+// the log acceptance ratio from its target part `b` = beta * (lpy - lp): two products and one sum.  beta = 1: + 0, the plain chain's
+// bits; beta = 0 and a candidate outside the target's support: 0 * (-inf) = NaN, a reject.
+MHX_DEV mhx_real mhx_tmp_loga(const mhx_real b, const mhx_tmp_lq<false>&) { return b; }
+MHX_DEV mhx_real mhx_tmp_loga(const mhx_real b, const mhx_tmp_lq<true>& q) { return b + q.omb * (q.lqy - q.lq); }
+// what the swap round compares: lp, or u = lp - lq
+MHX_DEV mhx_real mhx_tmp_swap_u(const mhx_real lp, const mhx_tmp_lq<false>&) { return lp; }
+MHX_DEV mhx_real mhx_tmp_swap_u(const mhx_real lp, const mhx_tmp_lq<true>& q) { return lp - q.lq; }
 
 // the value of `v` in lane (lane ^ 1): a quad permutation [1, 0, 3, 2]
 MHX_DEV mhx_u32 mhx_tmp_xor1_u32(const mhx_u32 v)
@@ -96,6 +146,8 @@ MHX_DEV mhx_tmp_lane mhx_tmp_lane_of(const int c, const int R, const mhx_real* _
 
 // The decision of swap round `s` for this lane's pair: true in BOTH lanes of a pair that swaps, false elsewhere.  `plp` receives the
 // partner's lp, `logs` the log of the pair's swap ratio (the same value in both lanes).  attempts / swaps: the lower slot's counters.
+// An anchored ladder passes u = lp - lq for lp: the ratio is of u, and `plp` receives the partner's u (the same one subtraction of the
+// partner's own lp and lq, whichever lane makes it); the lanes that swap fetch lp and lq themselves afterwards.
 template <bool EVEN>
 MHX_DEV bool mhx_tmp_decide(const mhx_tmp_lane& t, const mhx_philox_key& ks, const mhx_u64 id, const mhx_u32 s, const mhx_real lp,
                             mhx_real& plp, mhx_u32& attempts, mhx_u32& swaps, mhx_real& logs)
@@ -201,10 +253,13 @@ MHX_DEV void mhx_tmp_adapt_round(mhx_tmp_lane& t, const mhx_tmp_adapt& ad, const
 // ---------------------------------------------------------------------------------------------
 // state in HBM, run-time dimension
 // ADAPT: an adaptive ladder -- `ad` in place of the table `tt` (each is NULL where the other is read)
-template <int TK, bool ADAPT = false>
+// ANCHOR: an anchored ladder -- the table and `an` (fixed ladders only)
+template <int TK, bool ADAPT = false, bool ANCHOR = false>
 MHX_DEV void mhx_tmp_generic_body(const mhx_rwmh_args& a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
-                                  mhx_u32* __restrict__ swapc, const int swap_every, const int R, const mhx_tmp_adapt* ad = nullptr)
+                                  mhx_u32* __restrict__ swapc, const int swap_every, const int R, const mhx_tmp_adapt* ad = nullptr,
+                                  const mhx_tmp_anchor* an = nullptr)
 {
+    static_assert(!(ADAPT && ANCHOR), "an anchored ladder is a fixed ladder");
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.nchains) return;                                     // (whole ladders leave together: nchains is a multiple of R)
     const mhx_u64 id = a.first_chain + (mhx_u64)c;
@@ -224,6 +279,14 @@ MHX_DEV void mhx_tmp_generic_body(const mhx_rwmh_args& a, const mhx_real* __rest
     }
 
     mhx_real lp = a.lp[c];
+    mhx_tmp_lq<ANCHOR> q;                                            // ANCHOR: log q of the state, recomputed (no state of its own is kept)
+    if constexpr (ANCHOR) {
+        mhx_strided_x xv;
+        xv.base = xs;
+        xv.ld = ld;
+        q.lq = mhx_tmp_logq(xv, d, *an);
+        q.omb = an->omb[t.r];
+    }
     mhx_u32 nacc = a.acc_count[c];
     mhx_u32 wave_acc = 0;
     bool last = a.last_acc[c] != 0;
@@ -261,9 +324,11 @@ MHX_DEV void mhx_tmp_generic_body(const mhx_rwmh_args& a, const mhx_real* __rest
         yv.ld = ld;
         const mhx_real lpy = mhx_target_eval<TK>(a.target_kind, yv, d, tparams, a.ntparams, a.tconst);
         const mhx_real logu = mhx_accept_logu(ks, id_lo, id_hi, step, ac);
-        const mhx_real loga = t.beta * (lpy - lp);
+        if constexpr (ANCHOR) q.lqy = mhx_tmp_logq(yv, d, *an);
+        const mhx_real loga = mhx_tmp_loga(t.beta * (lpy - lp), q);
         const bool acc = logu < loga;                    // strict; NaN compares false => reject
         lp = acc ? lpy : lp;
+        if constexpr (ANCHOR) q.lq = acc ? q.lqy : q.lq;
         nacc += acc ? 1u : 0u;
         last = acc;
         wave_acc += (mhx_u32)__popcll(__ballot(acc));
@@ -274,22 +339,32 @@ MHX_DEV void mhx_tmp_generic_body(const mhx_rwmh_args& a, const mhx_real* __rest
             const mhx_u32 s = sround++;
             mhx_real plp, logs;
             if ((s & 1u) == 0u) {
-                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, lp, plp, attempts, swaps, logs);
+                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, mhx_tmp_swap_u(lp, q), plp, attempts, swaps, logs);
                 if (__ballot(sw) != 0ull) {
                     for (int k = 0; k < d; ++k) {
                         const mhx_real mine = xs[(long)k * ld];
                         const mhx_real theirs = mhx_tmp_partner<true>(mine, t.paddr_odd);
                         if (sw) xs[(long)k * ld] = theirs;
                     }
+                    if constexpr (ANCHOR) {             // (plp is the partner's u)
+                        plp = mhx_tmp_partner<true>(lp, t.paddr_odd);
+                        const mhx_real plq = mhx_tmp_partner<true>(q.lq, t.paddr_odd);
+                        q.lq = sw ? plq : q.lq;
+                    }
                     lp = sw ? plp : lp;
                 }
             } else {
-                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, lp, plp, attempts, swaps, logs);
+                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, mhx_tmp_swap_u(lp, q), plp, attempts, swaps, logs);
                 if (__ballot(sw) != 0ull) {
                     for (int k = 0; k < d; ++k) {
                         const mhx_real mine = xs[(long)k * ld];
                         const mhx_real theirs = mhx_tmp_partner<false>(mine, t.paddr_odd);
                         if (sw) xs[(long)k * ld] = theirs;
+                    }
+                    if constexpr (ANCHOR) {             // (plp is the partner's u)
+                        plp = mhx_tmp_partner<false>(lp, t.paddr_odd);
+                        const mhx_real plq = mhx_tmp_partner<false>(q.lq, t.paddr_odd);
+                        q.lq = sw ? plq : q.lq;
                     }
                     lp = sw ? plp : lp;
                 }
@@ -346,10 +421,12 @@ MHX_DEV void mhx_tmp_rung_body(const mhx_real* __restrict__ src, mhx_real* __res
 // ---------------------------------------------------------------------------------------------
 // state in registers; dimension, target, proposal kind and ladder size compile-time constants
 #ifdef MHX_JIT_TEMPERED_REG
-template <int D, int TK, int PK, int R, bool ADAPT = false>
+template <int D, int TK, int PK, int R, bool ADAPT = false, bool ANCHOR = false>
 MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
-                              mhx_u32* __restrict__ swapc, const int swap_every, const mhx_tmp_adapt* ad = nullptr)
+                              mhx_u32* __restrict__ swapc, const int swap_every, const mhx_tmp_adapt* ad = nullptr,
+                              const mhx_tmp_anchor* an = nullptr)
 {
+    static_assert(!(ADAPT && ANCHOR), "an anchored ladder is a fixed ladder");
     static_assert(R >= 2 && R <= 64 && (R & (R - 1)) == 0, "a ladder is a power of two of lanes of one wave");
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.nchains) return;                                     // (whole ladders leave together: nchains is a multiple of R)
@@ -372,6 +449,11 @@ MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = mhx_ld_off(a.x + (long)k * ld, cu);
     mhx_real lp = a.lp[c];
+    mhx_tmp_lq<ANCHOR> q;                                            // ANCHOR: log q of the state, recomputed (no state of its own is kept)
+    if constexpr (ANCHOR) {
+        q.lq = mhx_tmp_logq(x, D, *an);
+        q.omb = an->omb[t.r];
+    }
     mhx_u32 nacc = a.acc_count[c];
     mhx_u32 wave_acc = 0;
     bool last = a.last_acc[c] != 0;
@@ -407,7 +489,8 @@ MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict
         }
         const mhx_real lpy = mhx_target_eval<TK>(TK, y, D, tparams, a.ntparams, a.tconst);
         const mhx_real logu = mhx_accept_logu(ks, id_lo, id_hi, step, ac);
-        const mhx_real loga = t.beta * (lpy - lp);
+        if constexpr (ANCHOR) q.lqy = mhx_tmp_logq(y, D, *an);
+        const mhx_real loga = mhx_tmp_loga(t.beta * (lpy - lp), q);
         const bool acc = logu < loga;                    // strict; NaN compares false => reject
         // (fp64: a move under the execute mask, fp32: a select -- see mhx_rwmh_reg_body)
         if (MHX_REAL64) {
@@ -420,6 +503,7 @@ MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict
             for (int k = 0; k < D; ++k) x[k] = acc ? y[k] : x[k];
         }
         lp = acc ? lpy : lp;
+        if constexpr (ANCHOR) q.lq = acc ? q.lqy : q.lq;
         nacc += acc ? 1u : 0u;
         last = acc;
         wave_acc += (mhx_u32)__popcll(__ballot(acc));
@@ -429,20 +513,28 @@ MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict
             // the exchange runs under the execute mask of the lanes that swap -- both lanes of a pair, by construction -- and in place:
             // y is dead here, but not even it is needed
             if ((s & 1u) == 0u) {
-                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, lp, plp, attempts, swaps, logs);
+                const bool sw = mhx_tmp_decide<true>(t, ks, id, s, mhx_tmp_swap_u(lp, q), plp, attempts, swaps, logs);
                 if (__ballot(sw) != 0ull) {
                     if (sw) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) x[k] = mhx_tmp_partner<true>(x[k], t.paddr_odd);
+                        if constexpr (ANCHOR) {         // (plp is the partner's u)
+                            plp = mhx_tmp_partner<true>(lp, t.paddr_odd);
+                            q.lq = mhx_tmp_partner<true>(q.lq, t.paddr_odd);
+                        }
                         lp = plp;
                     }
                 }
             } else if (R > 2) {                          // (R = 2: the odd rounds have no pair)
-                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, lp, plp, attempts, swaps, logs);
+                const bool sw = mhx_tmp_decide<false>(t, ks, id, s, mhx_tmp_swap_u(lp, q), plp, attempts, swaps, logs);
                 if (__ballot(sw) != 0ull) {
                     if (sw) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) x[k] = mhx_tmp_partner<false>(x[k], t.paddr_odd);
+                        if constexpr (ANCHOR) {         // (plp is the partner's u)
+                            plp = mhx_tmp_partner<false>(lp, t.paddr_odd);
+                            q.lq = mhx_tmp_partner<false>(q.lq, t.paddr_odd);
+                        }
                         lp = plp;
                     }
                 }
@@ -482,7 +574,14 @@ MHX_DEV void mhx_tmp_reg_body(const mhx_rwmh_args& a, const mhx_real* __restrict
         atomicAdd(a.acc_total, (mhx_u64)wave_acc);
 }
 
-#ifdef MHX_JIT_ADAPT
+#if defined(MHX_JIT_ANCHOR)
+extern "C" __global__ void __launch_bounds__(64)
+mhx_jit_tempered_anchored_reg(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                              mhx_u32* __restrict__ swapc, const int swap_every, const mhx_tmp_anchor an)
+{
+    mhx_tmp_reg_body<MHX_JIT_DIM, MHX_JIT_TK, MHX_JIT_PK, MHX_JIT_R, false, true>(a, tparams, tt, swapc, swap_every, nullptr, &an);
+}
+#elif defined(MHX_JIT_ADAPT)
 extern "C" __global__ void __launch_bounds__(64)
 mhx_jit_tempered_adapt_reg(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_tmp_adapt ad,
                            mhx_u32* __restrict__ swapc, const int swap_every)
@@ -498,7 +597,14 @@ mhx_jit_tempered_reg(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams
 }
 #endif
 #endif
-#if defined(MHX_JIT_TEMPERED_GENERIC) && defined(MHX_JIT_ADAPT)
+#if defined(MHX_JIT_TEMPERED_GENERIC) && defined(MHX_JIT_ANCHOR)
+extern "C" __global__ void __launch_bounds__(256)
+mhx_jit_tempered_anchored_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_real* __restrict__ tt,
+                                  mhx_u32* __restrict__ swapc, const int swap_every, const int R, const mhx_tmp_anchor an)
+{
+    mhx_tmp_generic_body<MHX_JIT_TK, false, true>(a, tparams, tt, swapc, swap_every, R, nullptr, &an);
+}
+#elif defined(MHX_JIT_TEMPERED_GENERIC) && defined(MHX_JIT_ADAPT)
 extern "C" __global__ void __launch_bounds__(256)
 mhx_jit_tempered_adapt_generic(const mhx_rwmh_args a, const mhx_real* __restrict__ tparams, const mhx_tmp_adapt ad,
                                mhx_u32* __restrict__ swapc, const int swap_every, const int R)

@@ -65,6 +65,11 @@ class LadderAdaptCfg(C.Structure):
                 ("rho_min", C.c_double), ("rho_max", C.c_double)]
 
 
+class TemperedReference(C.Structure):
+    """mhx_tempered_reference: the diagonal Gaussian an anchored ladder tempers towards; mean and sd point at dim doubles"""
+    _fields_ = [("mean", C.c_void_p), ("sd", C.c_void_p)]
+
+
 class ProposalComponent(C.Structure):
     """mhx_proposal_component: one univariate component of a proposal, parameters as in Distributions.jl"""
     _fields_ = [("family", C.c_int32), ("reserved", C.c_int32), ("p0", C.c_double), ("p1", C.c_double)]
@@ -146,7 +151,7 @@ EXPORTS = [
     "mhx_run_autocovariance", "mhx_ctx_autocovariance", "mhx_group_autocovariance",
     "mhx_run_derive", "mhx_ctx_derive", "mhx_run_predict", "mhx_ctx_predict", "mhx_run_pointwise", "mhx_ctx_pointwise",
     "mhx_run_psis", "mhx_ctx_psis", "mhx_rwmh_create_tempered", "mhx_run_swap_stats", "mhx_run_rung",
-    "mhx_rwmh_create_tempered_adaptive", "mhx_run_ladder_betas",
+    "mhx_rwmh_create_tempered_adaptive", "mhx_run_ladder_betas", "mhx_rwmh_create_tempered_anchored", "mhx_run_evidence",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -317,6 +322,9 @@ def lib():
         if hasattr(L, "mhx_run_ladder_betas"):            # (an older build bound by use_library for an A/B run has neither)
             L.mhx_rwmh_create_tempered_adaptive.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), C.POINTER(LadderAdaptCfg), pvp]
             L.mhx_run_ladder_betas.argtypes = [vp, dp]
+        if hasattr(L, "mhx_run_evidence"):
+            L.mhx_rwmh_create_tempered_anchored.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), C.POINTER(TemperedReference), pvp]
+            L.mhx_run_evidence.argtypes = [vp, dp, i64p]
         _lib = _loaded[_lib_path] = L
     return _lib
 

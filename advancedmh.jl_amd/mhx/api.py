@@ -944,6 +944,17 @@ def geometric_betas(R, beta_min):
     return b
 
 
+def power_betas(R, p=3.0):
+    """The usual ladder of thermodynamic integration: beta_r = ((R - 1 - r) / (R - 1))^p, from beta_0 exactly 1 to beta_{R-1} exactly 0,
+    dense near 0 where E_beta[u] changes fastest.  For an anchored ladder (Tempered(..., reference=...)); give `scales` with it."""
+    R = int(R)
+    if R < 2 or not (float(p) > 0.0 and math.isfinite(float(p))):
+        raise L.ArgumentError(L.MHX_EINVAL, "power_betas: R >= 2 rungs and a finite p > 0")
+    b = np.array([((R - 1.0 - r) / (R - 1.0)) ** float(p) for r in range(R)], dtype=np.float64)
+    b[0], b[-1] = 1.0, 0.0
+    return b
+
+
 class LadderAdaptation:
     """LadderAdaptation(steps, target_rate=0.234, c=1.0, kappa=0.6, rho_min=None, rho_max=None) -- how the ladders of a Tempered
     sampler tune their temperatures during the first `steps` transitions (mhx_ladder_adapt_cfg): after swap
@@ -973,15 +984,18 @@ class LadderAdaptation:
 
 
 class Tempered:
-    """Tempered(sampler, betas, swap_every=1, scales=None, adapt=None) -- parallel tempering (replica exchange) around a random-walk
+    """Tempered(sampler, betas, swap_every=1, scales=None, adapt=None, reference=None) -- parallel tempering (replica exchange) around a random-walk
     sampler, what MCMCTempering.jl wraps around AdvancedMH's samplers and emcee shipped as PTSampler.  `sampler`: an RWMH over an
     isotropic or diagonal zero-mean MvNormal.  `betas`: the ladder, betas[0] == 1, strictly decreasing, a power of two of rungs (2..64).
     Rung r samples target^betas[r] with the proposal scaled by scales[r] (default betas[r]^(-1/2)); after every swap_every-th transition
     neighbouring rungs may exchange their states.  `adapt`: a LadderAdaptation -- `betas` is then where every ladder starts and each
-    tunes its own temperatures from its own swaps (no `scales`: they follow the ladder).
+    tunes its own temperatures from its own swaps (no `scales`: they follow the ladder).  `reference`: an MvNormal(mean, diagonal
+    variances) q -- the ladder is ANCHORED: rung r samples target^beta q^(1 - beta), the last beta may be
+    exactly 0 (then `scales` must be given) and `chain.tempered.evidence()` is the log marginal likelihood.  At beta = 0 the rung samples
+    q restricted to the target's support.  Fixed ladders only.
     `sample(model, Tempered(...), N, nladders)` returns the nladders cold chains."""
 
-    def __init__(self, sampler, betas, swap_every=1, scales=None, adapt=None):
+    def __init__(self, sampler, betas, swap_every=1, scales=None, adapt=None, reference=None):
         if not isinstance(sampler, MetropolisHastings) or not isinstance(sampler.proposal, RandomWalkProposal) or \
                 not isinstance(sampler.proposal.proposal, MvNormal):
             raise L.ArgumentError(L.MHX_EINVAL, "Tempered wraps an RWMH sampler over an isotropic or diagonal MvNormal")
@@ -1001,6 +1015,97 @@ class Tempered:
         if adapt is not None and self.swap_every == 0:
             raise L.ArgumentError(L.MHX_EINVAL, "Tempered: swap_every = 0 with adapt -- an adaptive ladder tunes itself from its swap rounds")
         self.adapt = adapt
+        self.reference = reference
+        self.ref_mean = self.ref_sd = None
+        if reference is not None:
+            if adapt is not None:
+                raise L.ArgumentError(L.MHX_EINVAL, "Tempered: reference with adapt -- an adaptive ladder moves in log beta, which cannot reach "
+                                      "0: an anchored ladder is a fixed ladder")
+            if not isinstance(reference, MvNormal) or reference.kind == L.PROP_DENSE:
+                raise L.ArgumentError(L.MHX_EINVAL, "Tempered: reference must be an MvNormal with an isotropic or a diagonal covariance (a dense "
+                                      "reference is not supported)")
+            self.ref_mean = np.ascontiguousarray(reference.mean, dtype=np.float64).ravel()
+            self.ref_sd = np.full(reference.dim, reference.scale, dtype=np.float64) if reference.kind == L.PROP_ISO else \
+                np.ascontiguousarray(reference.vec, dtype=np.float64).ravel()
+            if not (np.isfinite(self.ref_mean).all() and np.isfinite(self.ref_sd).all() and (self.ref_sd > 0).all()):
+                raise L.ArgumentError(L.MHX_EINVAL, "Tempered: the reference needs a finite mean and finite positive variances")
+        zero = np.flatnonzero(self.betas == 0.0)
+        if zero.size and reference is not None:
+            if zero[0] != self.R - 1:
+                raise L.ArgumentError(L.MHX_EINVAL, "Tempered: betas[%d] = 0 is not the last rung -- only the last inverse temperature of an "
+                                      "anchored ladder may be 0" % zero[0])
+            if self.scales is None:
+                raise L.ArgumentError(L.MHX_EINVAL, "Tempered: betas[%d] = 0 without scales -- the default proposal scale beta^(-1/2) has no "
+                                      "value there: give scales" % zero[0])
+
+
+class EvidenceResult(dict):
+    """what Run.evidence returns: dict(rungs, log_z_ti, log_z_ti_coarse, log_z_ss, log_z_ss_backward, se_ti, se_ss, se_ss_backward, bad,
+    nladders, n_saved) that prints.  rungs: one row {rung, beta, n, mean_u, var_u} per rung, u = log target - log reference."""
+
+    def __str__(self):
+        out = ["log Z   stepping stone %.5f (se %.5f)   backward %.5f (se %.5f)" % (self["log_z_ss"], self["se_ss"], self["log_z_ss_backward"],
+                                                                                   self["se_ss_backward"]),
+               "        thermodynamic integration %.5f (se %.5f)   every other rung %.5f" % (self["log_z_ti"], self["se_ti"],
+                                                                                           self["log_z_ti_coarse"]),
+               "        %d ladders, %d saved draws per chain, %d draws left out" % (self["nladders"], self["n_saved"], self["bad"]),
+               "rung        beta         n        mean u         var u"]
+        for w in self["rungs"]:
+            out.append("%4d %11.5g %9d %13.5f %13.5f" % (w["rung"], w["beta"], w["n"], w["mean_u"], w["var_u"]))
+        return "\n".join(out)
+
+    __repr__ = __str__
+
+
+def _lse_pool(mx, se):
+    """log sum exp of chains given as (max, sum exp(. - max)) pairs"""
+    m = float(np.max(mx))
+    if not math.isfinite(m):
+        return m if m < 0 else math.nan
+    return m + math.log(float(np.sum(se * np.exp(mx - m))))
+
+
+def evidence_from_table(table, betas, n_saved):
+    """The log evidence from the per-chain table [nladders * R][8] of mhx_run_evidence (bad, shift, s1, s2, max_f, sumexp_f, max_b,
+    sumexp_b), the ladder's betas [R] as the run holds them and the draws per chain, all in float64 on the host:
+    log_z_ti  the trapezoid over beta of the rung means of u;  log_z_ti_coarse  the same rule on rungs 0, 2, 4, .. and the last (NaN for
+    R = 2): their difference is the discretisation error's size;  log_z_ss = sum_r log mean exp(dbeta[r] u) over rung r + 1;
+    log_z_ss_backward = -sum_r log mean exp(-dbeta[r] u) over rung r;  se_*: the standard deviation of the per-ladder estimates over
+    sqrt(nladders) (NaN with one ladder)."""
+    betas = np.asarray(betas, dtype=np.float64).ravel()
+    R = betas.size
+    t = np.asarray(table, dtype=np.float64).reshape(-1, R, 8)
+    nl = t.shape[0]
+    with np.errstate(all="ignore"):
+        n = float(n_saved) - t[:, :, 0]                              # [nl][R] draws that count
+        mean_c = t[:, :, 1] + t[:, :, 2] / n                         # per chain
+        m2_c = t[:, :, 3] - t[:, :, 2] * t[:, :, 2] / n
+        ntot = n.sum(axis=0)
+        mean = (n * mean_c).sum(axis=0) / ntot
+        var = (m2_c.sum(axis=0) + (n * (mean_c - mean) ** 2).sum(axis=0)) / (ntot - 1.0)
+
+        def trapezoid(m, idx):
+            idx = np.asarray(idx)
+            return ((betas[idx[:-1]] - betas[idx[1:]]) * 0.5 * (m[..., idx[:-1]] + m[..., idx[1:]])).sum(axis=-1)
+        full = np.arange(R)
+        coarse = np.concatenate([np.arange(0, R - 1, 2), [R - 1]])
+        lf = t[:, :, 4] + np.log(t[:, :, 5] / n)                     # per chain: log mean exp(dbeta[r - 1] u)
+        lb = t[:, :, 6] + np.log(t[:, :, 7] / n)
+        ss_l, ssb_l, ti_l = lf[:, 1:].sum(axis=1), -lb[:, :-1].sum(axis=1), trapezoid(mean_c, full)
+        ss = sum(_lse_pool(t[:, r, 4], t[:, r, 5]) - math.log(ntot[r]) for r in range(1, R))
+        ssb = -sum(_lse_pool(t[:, r, 6], t[:, r, 7]) - math.log(ntot[r]) for r in range(R - 1))
+
+        def se(v):
+            return float(np.std(v, ddof=1) / math.sqrt(nl)) if nl > 1 else math.nan
+        return EvidenceResult(rungs=[dict(rung=r, beta=float(betas[r]), n=int(ntot[r]), mean_u=float(mean[r]), var_u=float(var[r])) for r in range(R)],
+                              log_z_ti=float(trapezoid(mean, full)), log_z_ti_coarse=float(trapezoid(mean, coarse)) if R > 2 else math.nan,
+                              log_z_ss=float(ss), log_z_ss_backward=float(ssb), se_ti=se(ti_l), se_ss=se(ss_l), se_ss_backward=se(ssb_l),
+                              bad=int(t[:, :, 0].sum()), nladders=int(nl), n_saved=int(n_saved))
+
+
+def bayes_factor(a, b):
+    """log Bayes factor of two EvidenceResults, model a over model b: the difference of their log_z_ss and the combined standard error"""
+    return dict(log_bf=a["log_z_ss"] - b["log_z_ss"], se=math.hypot(a["se_ss"], b["se_ss"]))
 
 
 class LadderTable(list):
@@ -1821,7 +1926,12 @@ class Run:
             cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
             tcfg = L.TemperedCfg(sampler.R, sampler.swap_every, sampler.betas.ctypes.data,
                                  None if sampler.scales is None else sampler.scales.ctypes.data)
-            if sampler.adapt is None:
+            if sampler.reference is not None:
+                self._keep += [sampler.ref_mean, sampler.ref_sd]
+                ref = L.TemperedReference(sampler.ref_mean.ctypes.data, sampler.ref_sd.ctypes.data)
+                L.check(lib.mhx_rwmh_create_tempered_anchored(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(ref),
+                                                              C.byref(self.h)))
+            elif sampler.adapt is None:
                 L.check(lib.mhx_rwmh_create_tempered(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(tcfg), C.byref(self.h)))
             else:
                 acfg = sampler.adapt.cfg()
@@ -2425,6 +2535,20 @@ class Run:
         b = self.sampler.betas if self.sampler.adapt is None else np.median(self.betas(), axis=0)
         return SwapTable(dict(pair=(r, r + 1), beta_lo=float(b[r]), beta_hi=float(b[r + 1]), attempts=int(att[r]), swaps=int(sw[r]),
                               rate=(float(sw[r]) / float(att[r]) if att[r] else float("nan"))) for r in range(len(att)))
+
+    def evidence_table(self):
+        """(table [nchains][8] float64, n_saved) of mhx_run_evidence: per chain bad, shift, s1, s2, max_f, sumexp_f, max_b, sumexp_b of
+        u = lp - lq over its saved draws"""
+        out = np.empty((self.n, 8), dtype=np.float64)
+        n_saved = C.c_int64()
+        L.check(L.lib().mhx_run_evidence(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n_saved)))
+        return out, int(n_saved.value)
+
+    def evidence(self):
+        """the log marginal likelihood of an anchored tempered run whose ladder ends at beta = 0 (Tempered(..., reference=...)): an
+        EvidenceResult -- thermodynamic integration and both stepping-stone estimates with their standard errors between ladders"""
+        table, n_saved = self.evidence_table()
+        return evidence_from_table(table, self.betas()[0], n_saved)
 
     def rung(self, r):
         """rung r of every ladder as a snapshot run (mhx_run_rung): [n_saved][dim + 1][nladders] on the device, read by every post-run

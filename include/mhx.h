@@ -526,7 +526,9 @@ typedef struct {
                                   16 a tempered run (mhx_rwmh_create_tempered): ladders of temperatures in consecutive lanes, swaps
                                   across lanes inside the step kernel; the run-time specialised register form or the state-in-HBM
                                   form (pre-built for the catalogue targets), the same chain,
-                                  17 a tempered run whose ladders adapt (mhx_rwmh_create_tempered_adaptive): the same two forms */
+                                  17 a tempered run whose ladders adapt (mhx_rwmh_create_tempered_adaptive): the same two forms,
+                                  18 a tempered run anchored at a reference density (mhx_rwmh_create_tempered_anchored): the same
+                                  two forms */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
@@ -535,7 +537,7 @@ typedef struct {
                                   (0 = diagonal, 1 = bidiagonal: an AR(1) / Markov model, ...), -1 = none (dense form, other samplers) */
     int32_t tainted;           /* 1: a probe / fault-injection option of the tools build was set on the run's context -- the chains of
                                   such a run may be INVALID (timing probes skip work).  Always 0 from libmhx.so. */
-    int32_t register_form;     /* kernel variants 13 .. 17: 1 = the run is stepped by the run-time specialised register form, 0 = by
+    int32_t register_form;     /* kernel variants 13 .. 18: 1 = the run is stepped by the run-time specialised register form, 0 = by
                                   the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
@@ -1023,6 +1025,39 @@ int mhx_rwmh_create_tempered_adaptive(mhx_ctx *ctx, const mhx_target *t, const m
  * An adaptive run: as of the end of the last mhx_run_sample (after create or mhx_run_init: the ladder of rho0); a fixed ladder: its
  * table.  MHX_ESTATE: not a tempered run.  Blocking. */
 int mhx_run_ladder_betas(mhx_run *run, double *beta);
+/* An anchored ladder: rung r samples target^beta[r] * q^(1 - beta[r]) where q is a normalised reference
+ * density, a diagonal Gaussian N(mean[k], sd[k]^2) given as doubles (every sd > 0).  This is the power posterior when q is the prior
+ * and the generalised stepping stone otherwise.  beta[0] == 1 and the ladder is strictly decreasing as before, but the LAST beta may
+ * be exactly 0 (only the last): that rung samples q, and the path from beta = 1 to beta = 0 integrates to the log evidence,
+ *     log Z = integral_0^1 E_beta[log target - log q] d beta            (mhx_run_evidence below).
+ * With a beta of 0 tcfg.scale must be given: the default beta^(-1/2) has no value there.  Fixed ladders only.
+ *     transition   log a = beta (lp(y) - lp(x)) + (1 - beta) (lq(y) - lq(x)); with beta = 1 this has the bits of the plain chain's
+ *     swap round   log s = dbeta ((lp - lq)[r + 1] - (lp - lq)[r]); a swap exchanges x, lp and lq
+ *     recorded     row dim of the sample tensor stays the UNTEMPERED log target(x)
+ * SUPPORT: at beta = 0 a candidate outside the target's support has lp = -inf, 0 * (-inf) = NaN, and is rejected: the hot rung samples
+ * q RESTRICTED to the support of the target, and the evidence is then relative to q's mass on that support -- choose q inside it, or
+ * account for the missing mass.  (A chain that STARTS outside the support stays where it is on a beta = 0 rung until a swap moves it.)
+ * MHX_EINVAL with a message that names the rule for everything mhx_rwmh_create_tempered refuses, and for: a NULL or non-finite mean or
+ * sd, an sd <= 0, a zero beta that is not the last, a zero beta without tcfg.scale.  The run is kernel variant 18 (its register form is
+ * built for dim <= 44 in fp64, 76 in fp32); mhx_run_swap_stats, mhx_run_rung and mhx_run_ladder_betas work on it; it refuses what a
+ * fixed ladder refuses. */
+typedef struct {
+    const void *mean;          /* [dim] doubles */
+    const void *sd;            /* [dim] doubles, each > 0 */
+} mhx_tempered_reference;
+int mhx_rwmh_create_tempered_anchored(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg, const mhx_tempered_cfg *tcfg,
+                                      const mhx_tempered_reference *ref, mhx_run **out);
+/* What the log evidence of an anchored run is made of: out[nchains][8], per chain c (rung c mod R of ladder c div R, whose temperature
+ * never changes) over that chain's saved draws, u = lp - lq(x) formed in the run's width as the step kernel forms it, then fp64:
+ *     [0] bad        draws whose u is NaN or +-inf: counted and left out of every sum
+ *     [1] shift      the chain's first saved u, 0 where that is not finite
+ *     [2] s1         sum (u - shift)               [3] s2  sum (u - shift)^2
+ *     [4] max_f, [5] sumexp_f   max and sum exp(. - max) of dbeta[r - 1] u, rungs r >= 1: the stepping-stone weight towards the colder rung
+ *     [6] max_b, [7] sumexp_b   ... of -dbeta[r] u, rungs r <= R - 2: the backward weight          (an unused pair: -inf, 0)
+ * *n_saved (may be NULL): the draws per chain.  From these: thermodynamic integration is the trapezoid of the rung means of u over
+ * beta; the stepping-stone estimate is sum_r log mean exp(dbeta[r] u) over rung r + 1.  One sweep of the tensor, no atomics: two calls
+ * give the same bits.  MHX_ESTATE: not an anchored run, no sample tensor, or the ladder's last beta is not 0.  Blocking. */
+int mhx_run_evidence(mhx_run *run, double *out, int64_t *n_saved);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process. Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`

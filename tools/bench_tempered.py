@@ -22,7 +22,14 @@ chains, the three configurations timed in turn as above:
 --lib PATH adds (fixed) measured on another build of the library (the parent commit's, say), in child processes of its own that
 alternate with children that time (fixed) alone on this build: the fixed ladder's code path must not have moved.
 
-    bench_tempered.py --adapt [--lib OTHER/libmhx.so] [OUT.json]        default OUT: profiles/tempered_adaptive_bench.json"""
+    bench_tempered.py --adapt [--lib OTHER/libmhx.so] [OUT.json]        default OUT: profiles/tempered_adaptive_bench.json
+
+--anchor measures the anchored ladder (kernel variant 18) at the same shape, in the same unit, (fixed) and (anchored) timed in turn:
+  (fixed)    the geometric ladder with swap_every = 1: (d) above
+  (anchored) the same ladder and scales with a reference density N(0.25, 1.5^2 I): lq beside the target in every transition and swap
+--lib PATH adds (fixed) measured on another build of the library (the parent commit's) in a child process of its own.
+
+    bench_tempered.py --anchor [--lib OTHER/libmhx.so] [OUT.json]       default OUT: profiles/tempered_anchored_bench.json"""
 import json
 import os
 import subprocess
@@ -115,6 +122,65 @@ def measure_adapt(dt, lib=None):
     return row
 
 
+def measure_anchor(dt, lib=None):
+    """lib None: (fixed) and (anchored) on this build; a path: (fixed) alone on that build"""
+    import mhx
+    if lib:
+        mhx.use_library(lib)
+    s = float(np.float32(2.38 / D ** 0.5))
+    rw = mhx.RWMH(mhx.MvNormal(mhx.zeros(D), (s * s) * mhx.I))
+    ladder = mhx.geometric_betas(R, 0.05)
+    configs = [("fixed", mhx.Tempered(rw, ladder, swap_every=1))]
+    if not lib:
+        configs.append(("anchored", mhx.Tempered(rw, ladder, swap_every=1, reference=mhx.MvNormal(np.full(D, 0.25), 2.25 * mhx.I))))
+    model = mhx.DensityModel(mhx.IsoGaussian(D))
+    runs = {}
+    for name, spl in configs:
+        run = mhx.Run(model, spl, nchains=C, seed=1, reduce_lanes=1, dtype=dt)
+        run.init(np.zeros(D))
+        run.sample(STEPS, 50, 1, 0)
+        runs[name] = run
+    ms = {name: [] for name in runs}
+    for _ in range(REPEATS):
+        for name, run in runs.items():
+            run.sample(STEPS, 1, 1, 0)
+            st = run.stats()
+            ms[name].append(st["kernel_ms"] / (st["transitions"] / C))
+    row = {}
+    for name, run in runs.items():
+        st = run.stats()
+        v = np.array(ms[name])
+        att, swp = run.swap_stats()
+        row[name] = dict(ms_per_step=float(np.median(v)), min=float(v.min()), max=float(v.max()), kernel_variant=st["kernel_variant"],
+                         form=run.form_name(), swap_rate=float(swp.sum()) / float(att.sum()))
+        run.close()
+    return row
+
+
+def main_anchor(out, lib):
+    result = dict(dim=D, R=R, nchains=C, recorded_steps=STEPS, repeats=REPEATS, target="IsoGaussian",
+                  unit="milliseconds of kernel time per step of all chains")
+    for dt in ("f64", "f32"):
+        row = child(["--one-anchor", dt])
+        if row is None:
+            return 1
+        row["anchored_over_fixed"] = row["anchored"]["ms_per_step"] / row["fixed"]["ms_per_step"]
+        if lib:
+            other = child(["--one-anchor", dt, lib])
+            if other is None:
+                return 1
+            row["fixed_other_build"] = other["fixed"]
+            row["anchored_over_fixed_other_build"] = row["anchored"]["ms_per_step"] / other["fixed"]["ms_per_step"]
+            row["fixed_this_over_other"] = row["fixed"]["ms_per_step"] / other["fixed"]["ms_per_step"]
+        result[dt] = row
+        print(json.dumps({dt: row}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    return 0
+
+
 def child(args):
     done = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, stdout=subprocess.PIPE, text=True, timeout=STEP_LIMIT_S)
     if done.returncode != 0:
@@ -179,6 +245,15 @@ if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--one-adapt":
         print(json.dumps(measure_adapt(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)), flush=True)
         sys.exit(0)
+    if len(sys.argv) > 2 and sys.argv[1] == "--one-anchor":
+        print(json.dumps(measure_anchor(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)), flush=True)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "--anchor":
+        rest = sys.argv[2:]
+        lib = None
+        if rest and rest[0] == "--lib":
+            lib, rest = os.path.abspath(rest[1]), rest[2:]
+        sys.exit(main_anchor(rest[0] if rest else os.path.join(ROOT, "profiles", "tempered_anchored_bench.json"), lib))
     if len(sys.argv) > 1 and sys.argv[1] == "--adapt":
         rest = sys.argv[2:]
         lib = None
