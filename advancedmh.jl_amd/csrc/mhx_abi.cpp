@@ -344,3 +344,4 @@ extern "C" int mhx_emcee_exchange_unpack(mhx_run* r, int half, int rank, int wor
 
 #include "mhx_abi_pointwise.inc"
 #include "mhx_abi_tempered.inc"
+#include "mhx_abi_adaptive.inc"

@@ -30,6 +30,7 @@
 #include "mhx_rwmh_cond_kernels.h"
 #include "mhx_rwmh_composite_kernels.h"
 #include "mhx_rwmh_tempered_kernels.h"
+#include "mhx_rwmh_adaptive_kernels.h"
 #include "mhx_evidence_kernels.h"
 #include "mhx_emcee_kernels.h"
 #include "mhx_ram_kernels.h"
@@ -511,12 +512,13 @@ static int jit_compile(mhx_ctx* ctx, const std::string& source, const std::vecto
                              k_src_mhx_rwmh_dense_kernels_h, k_src_mhx_rwmh_mfma_kernels_h,
                              k_src_mhx_mala_mfma_kernels_h, k_src_mhx_emcee_mfma_kernels_h, k_src_mhx_rwmh_family_kernels_h,
                              k_src_mhx_rwmh_cond_kernels_h, k_src_mhx_rwmh_composite_kernels_h, k_src_mhx_derive_kernels_h,
-                             k_src_mhx_pointwise_kernels_h, k_src_mhx_psis_kernels_h, k_src_mhx_rwmh_tempered_kernels_h};
+                             k_src_mhx_pointwise_kernels_h, k_src_mhx_psis_kernels_h, k_src_mhx_rwmh_tempered_kernels_h,
+                             k_src_mhx_rwmh_adaptive_kernels_h};
     const char* hdr_name[] = {"mhx_zig_table.h", "mhx_device_math.h", "mhx_targets.h", "mhx_rwmh_kernels.h",
                               "mhx_emcee_kernels.h", "mhx_ram_kernels.h", "mhx_mala_kernels.h",
                               "mhx_rwmh_dense_kernels.h", "mhx_rwmh_mfma_kernels.h", "mhx_mala_mfma_kernels.h", "mhx_emcee_mfma_kernels.h",
                               "mhx_rwmh_family_kernels.h", "mhx_rwmh_cond_kernels.h", "mhx_rwmh_composite_kernels.h", "mhx_derive_kernels.h",
-                              "mhx_pointwise_kernels.h", "mhx_psis_kernels.h", "mhx_rwmh_tempered_kernels.h"};
+                              "mhx_pointwise_kernels.h", "mhx_psis_kernels.h", "mhx_rwmh_tempered_kernels.h", "mhx_rwmh_adaptive_kernels.h"};
     const int nhdr = (int)(sizeof hdr_src / sizeof hdr_src[0]);
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize",
                                      MHX_REAL64 ? "-DMHX_REAL64=1" : "-DMHX_REAL64=0", "-DMHX_XW_LINE=" + std::to_string(MHX_XW_LINE)};
@@ -857,6 +859,8 @@ enum kernel_form {
     KF_TEMPERED = 16,       // parallel tempering of the plain random walk: specialised register form or state in HBM (mhx_api_tempered.inc)
     KF_TEMPERED_ADAPT = 17, // ... whose ladders tune their temperatures from their swaps while the run warms up: the same two forms
     KF_TEMPERED_ANCHOR = 18, // ... whose rungs temper towards a normalised reference density, down to beta = 0: the same two forms
+    KF_ADAPTIVE = 19,       // the plain random walk whose chains tune their own proposal while the run warms up, then freeze it: two
+                            // phases, each the specialised register form or state in HBM (mhx_api_adaptive.inc)
 };
 
 // One kernel of a run, ready to launch: everything the host needs for it, filled ONCE, in the branch of a create function that
@@ -957,6 +961,15 @@ struct mhx_run : mhx_handle_hdr {
     bool tmp_beta_end_zero = false;         // the ladder reaches the reference itself (mhx_run_evidence)
     mhx_real* d_tanchor = nullptr;          // omb[R] | m[dim] | w[dim]
     mhx_tmp_anchor tmp_an{};                // the step kernel's reference block: pointers into d_tanchor, lc
+    // KF_ADAPTIVE (mhx_api_adaptive.inc): `step` is the adapting phase's kernel, `step_frozen` the frozen phase's
+    bool adp = false;
+    uint64_t adp_steps = 0;                 // transitions 1 .. adp_steps adapt
+    int adp_shape = 0;                      // the per-coordinate standard deviations adapt too
+    int adp_perk = 0;                       // eff has a row per coordinate (DIAG or shape), else one row
+    bool adp_reg = false, adp_frozen_reg = false;   // the phase is stepped by its register form
+    mhx_real* d_adp = nullptr;              // lam[n] | eff[n or dim n] | (shape) m, v, sig [dim n] each | gamma[adp_steps] | s, vlo, vhi [dim] each
+    uint32_t* d_acc_freeze = nullptr;       // [n] the accept counters as they stood after transition adp_steps
+    mhx_adp adp_a{};                        // the adapting kernels' block: pointers into d_adp, the constants
     // mala
     mhx_real mala_sigma = MHX_R(1.0);
     mhx_real *d_gx = nullptr, *d_gy = nullptr, *d_z = nullptr;
@@ -1009,6 +1022,7 @@ struct mhx_run : mhx_handle_hdr {
     const mhx_real* k_tp = nullptr;      // target->dparams, as a kernel argument (run_alloc_state)
     launch_rec step;                     // the step kernel (an ensemble: the half-step, or the sequential sweep)
     launch_rec step_k8;                  // KF_WAVE: the K = 8 build of the wave-per-chain kernel
+    launch_rec step_frozen;              // KF_ADAPTIVE: the frozen phase's kernel (transitions after adp_steps)
     launch_rec step_mom;                 // KF_COOP / KF_COOP_JIT: the running-moments twin (pre-built, or built by the first MHX_SAVE_MOMENTS call)
     launch_rec sweep;                    // an ensemble: the stretch move as ONE launch per sweep (mhx_emcee_coop_sweep_body); state double-buffered
     launch_rec persist;                  // ... a small one as one persistent block (mhx_emcee_persist_body): a whole call per launch
@@ -1033,7 +1047,7 @@ struct mhx_run : mhx_handle_hdr {
     {
         void* ptrs[] = {d_pvec, d_S, d_Ssel, d_status, d_dmin, d_dmax, d_eta, d_x, d_lp, d_ybuf,
                         d_acc, d_last, d_acc_total, d_samples, d_accepted, d_mom_mean, d_mom_m2, d_gx, d_gy, d_z, d_pmean, d_qx, d_xw, d_loga, d_mfma_img, d_rec_loga,
-                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc, d_tadapt, d_tanchor};
+                        d_watch_chains, d_watch, d_xw2, d_lp2, d_defer, d_fam, d_cond_data, d_cond_p, d_cond_bad, d_cmp_tab, d_ttab, d_swapc, d_tadapt, d_tanchor, d_adp, d_acc_freeze};
         for (void* p : ptrs) if (p) (void)hipFree(p);
         if (acc_total_pin) (void)hipHostFree(acc_total_pin);
     }
@@ -1670,6 +1684,8 @@ static int rwmh_canonical_zero(mhx_run* r)
 }
 
 static int tempered_reset_ladder(mhx_run* r);                       // (mhx_api_tempered.inc)
+static int adaptive_reset(mhx_run* r);                              // (mhx_api_adaptive.inc)
+static int adaptive_seam(mhx_run* r);
 
 static int rwmh_init(mhx_run* r, const mhx_real* init)
 {
@@ -1703,6 +1719,7 @@ static int rwmh_init(mhx_run* r, const mhx_real* init)
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (r->adp) return adaptive_reset(r);                            // an adaptive run: lam = 0, eff = s, m = the first state
     return rwmh_whiten(r);
 }
 
@@ -1725,7 +1742,10 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
     mhx_ctx* ctx = r->ctx;
     uint64_t done = 0;
     while (done < nsteps) {
-        const uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
+        uint64_t chunk = std::min<uint64_t>(nsteps - done, MHX_MAX_STEPS_PER_LAUNCH);
+        // an adaptive run: a launch is of one phase, the schedule is split at the seam
+        const bool adapting = r->adp && r->tau < r->adp_steps;
+        if (adapting) chunk = std::min<uint64_t>(chunk, r->adp_steps - r->tau);
         mhx_rwmh_args a = rwmh_args(r);
         a.step0 = (uint32_t)(r->tau + 1);
         a.nsteps = (int)chunk;
@@ -1735,7 +1755,8 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         // the record: the running-moments twin, the K = 8 build of the wave-per-chain kernel (candidates per round: by the last call's
         // acceptance, or option WAVE_K), else the run's step kernel
         const launch_rec& k = r->moments_mode && r->step_mom ? r->step_mom
-                            : (r->step_k8 && opt_int(ctx, "WAVE_K", r->wave_k) == 8 ? r->step_k8 : r->step);
+                            : (r->step_k8 && opt_int(ctx, "WAVE_K", r->wave_k) == 8 ? r->step_k8
+                            : (r->adp && !adapting ? r->step_frozen : r->step));
         int rc = launch(k, ctx->stream, r->n, 1, &a);
         if (rc) return rc;
         HIP_TRY(hipGetLastError());
@@ -1743,6 +1764,7 @@ static int rwmh_advance(mhx_run* r, uint64_t nsteps, uint32_t save_next, int sav
         save_cursor_skip(r, chunk, thinning, &save_next, &save_slot);
         r->tau += chunk;
         done += chunk;
+        if (adapting && r->tau == r->adp_steps && (rc = adaptive_seam(r))) return rc;
     }
     return MHX_OK;
 }
@@ -1842,6 +1864,8 @@ int api_run_sample(mhx_run* r, const mhx_schedule* s, int save_samples)
         // running moments instead of a sample tensor
         if (r->tmp_R)
             return mhx_fail(MHX_ESTATE, "mhx_run_sample: running moments (MHX_SAVE_MOMENTS) are not kept by a tempered run: record samples");
+        if (r->adp)
+            return mhx_fail(MHX_ESTATE, "mhx_run_sample: running moments (MHX_SAVE_MOMENTS) are not kept by an adaptive run: record samples");
         if (r->kind == RUN_RWMH && r->variant == KF_COMPOSITE)
             return mhx_fail(MHX_EINVAL, "running moments (MHX_SAVE_MOMENTS) are not kept by a run with a composite proposal "
                                     "(kernel variant 15): record samples");
@@ -2045,6 +2069,7 @@ int api_run_state_size(mhx_run* r, size_t* bytes)
 {
     if (!r || !bytes) return mhx_fail(MHX_EINVAL, "mhx_run_state_size: NULL argument");
     if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_state_size: a tempered run has no checkpoint / resume");
+    if (r->adp) return mhx_fail(MHX_ESTATE, "mhx_run_state_size: an adaptive run has no checkpoint / resume");
     size_t total = sizeof(ckpt_header);
     for (const auto& p : ckpt_parts(r)) total += p.bytes;
     *bytes = total;
@@ -2054,6 +2079,7 @@ int api_run_save_state(mhx_run* r, void* blob, size_t bytes)
 {
     if (!r || !blob) return mhx_fail(MHX_EINVAL, "mhx_run_save_state: NULL argument");
     if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_save_state: a tempered run has no checkpoint / resume");
+    if (r->adp) return mhx_fail(MHX_ESTATE, "mhx_run_save_state: an adaptive run has no checkpoint / resume");
     if (!r->initialised) return mhx_fail(MHX_ESTATE, "mhx_run_save_state: run is not initialised");
     size_t need = 0;
     api_run_state_size(r, &need);
@@ -2076,6 +2102,7 @@ int api_run_load_state(mhx_run* r, const void* blob, size_t bytes)
 {
     if (!r || !blob) return mhx_fail(MHX_EINVAL, "mhx_run_load_state: NULL argument");
     if (r->tmp_R) return mhx_fail(MHX_ESTATE, "mhx_run_load_state: a tempered run has no checkpoint / resume");
+    if (r->adp) return mhx_fail(MHX_ESTATE, "mhx_run_load_state: an adaptive run has no checkpoint / resume");
     size_t need = 0;
     api_run_state_size(r, &need);
     ckpt_header h;
@@ -2113,7 +2140,7 @@ int api_run_stats(mhx_run* r, mhx_stats* out)
     if (!r || !out) return mhx_fail(MHX_EINVAL, "mhx_run_stats: NULL argument");
     *out = r->stats;
     out->tainted = r->ctx->tainted ? 1 : 0;
-    out->register_form = r->fam_reg ? 1 : 0;
+    out->register_form = (r->adp ? (r->tau < r->adp_steps ? r->adp_reg : r->adp_frozen_reg) : r->fam_reg) ? 1 : 0;
     return MHX_OK;
 }
 
@@ -2139,6 +2166,9 @@ const char* api_run_form_name(const mhx_run* r)
     case KF_TEMPERED: return r->fam_reg ? "tempered_reg" : "tempered_generic";
     case KF_TEMPERED_ADAPT: return r->fam_reg ? "tempered_adapt_reg" : "tempered_adapt_generic";
     case KF_TEMPERED_ANCHOR: return r->fam_reg ? "tempered_anchored_reg" : "tempered_anchored_generic";
+    case KF_ADAPTIVE:           // the form of the phase the next transition belongs to
+        if (r->tau < r->adp_steps) return r->adp_reg ? "adaptive_reg" : "adaptive_generic";
+        return r->adp_frozen_reg ? "adaptive_frozen_reg" : "adaptive_frozen_generic";
     case KF_FAMILY: return "family";
     case KF_COND: return "cond";
     case KF_COMPOSITE: return "composite";
@@ -2345,6 +2375,7 @@ static sweep_plan pointwise_sweep_plan(const draws_view& v, long ntiles)
 #include "mhx_api_acf.inc"
 #include "mhx_api_derive.inc"
 #include "mhx_api_tempered.inc"
+#include "mhx_api_adaptive.inc"
 #include "mhx_api_evidence.inc"
 #include "mhx_api_pointwise.inc"
 #include "mhx_api_psis.inc"

@@ -228,6 +228,9 @@ int api_run_sample_to_host(mhx_run* r, const mhx_schedule* s, mhx_real* host_sam
     if (r->tmp_R)
         return mhx_fail(MHX_ESTATE, "mhx_run_sample_to_host: a tempered run is not streamed to the host -- the accept-compacted return path takes a "
                                     "rejected transition for a repeat of the row above, and a swap breaks that: mhx_run_sample, then mhx_run_rung");
+    if (r->adp)
+        return mhx_fail(MHX_ESTATE, "mhx_run_sample_to_host: an adaptive run is not streamed to the host (the accept-compacted return path is left "
+                                    "out): mhx_run_sample, then mhx_run_get_samples");
     if (!host_samples) return mhx_fail(MHX_EINVAL, "mhx_run_sample_to_host: samples is NULL (use mhx_run_sample to keep nothing)");
     if (s->n_samples < 1 || s->thinning < 1 || s->discard_initial < 0 || s->num_warmup < 0)
         return mhx_fail(MHX_EINVAL, "mhx_run_sample_to_host: bad schedule (N=%d discard=%d thinning=%d warmup=%d slab=%d)",

@@ -213,6 +213,8 @@ extern "C" int mhx_group_attach(mhx_group* g, mhx_run* const* runs)
         if (!runs[i]) return mhx_fail(MHX_EINVAL, "mhx_group_attach: run %d is NULL", i);
         if (!strncmp(mhx_run_form_name(runs[i]), "tempered", 8))
             return mhx_fail(MHX_ESTATE, "mhx_group_attach: run %d is a tempered run, which a group does not drive (no Group twin of the swap statistics and the rung snapshot)", i);
+        if (!strncmp(mhx_run_form_name(runs[i]), "adaptive", 8))
+            return mhx_fail(MHX_ESTATE, "mhx_group_attach: run %d is an adaptive run, which a group does not drive (no Group twin of the proposal state)", i);
         int32_t d = 0, c = 0;
         const int rc = mhx_run_shape(runs[i], &d, &c);
         if (rc) return rc;

@@ -149,6 +149,9 @@ void mhx_jit_unlock();
     int api_run_ladder_betas(mhx_run* r, double* beta);                                                               \
     int api_run_swap_stats(mhx_run* r, uint64_t* attempts, uint64_t* swaps);                                          \
     int api_run_rung(mhx_run* src, int32_t rung, mhx_run** out);                                                      \
+    int api_rwmh_create_adaptive(mhx_ctx* ctx, const mhx_target* t, const mhx_rwmh_cfg* cfg,                          \
+                                 const mhx_proposal_adapt_cfg* acfg, mhx_run** out);                                  \
+    int api_run_proposal_state(mhx_run* r, double* lam, double* sd, double* mean, uint32_t* acc_at_freeze);           \
     int api_emcee_half_step(mhx_run* r, int half, int begin, int count);                                               \
     int api_emcee_end_sweep(mhx_run* r);                                                                               \
     int api_emcee_device_state(mhx_run* r, REAL** xw, int32_t* pitch, REAL** lp, uint32_t** acc_count,                 \

@@ -10,7 +10,7 @@ from .api import (I, Banana, Cauchy, Chains, ComponentProposal, CompositeProposa
                   HipPointwise, PointwiseSums, PointwiseTable, merge_pointwise, pointwise_table, waic_from_table, dic_from_table,
                   PsisResult, LooTable, LooResult, CompareTable, loo_table, loo_from_table, compare, psis_tail_length, khat_threshold,
                   SymmetricRandomWalkProposal, SymmetricStaticProposal, TDist, Transition, Uniform, bundle_samples,
-                  Tempered, LadderAdaptation, SwapTable, LadderTable, geometric_betas, power_betas, EvidenceResult, evidence_from_table,
+                  Tempered, LadderAdaptation, ProposalAdaptation, AdaptationTable, SwapTable, LadderTable, geometric_betas, power_betas, EvidenceResult, evidence_from_table,
                   bayes_factor, logdensity, pack_lower, sample, unpack_lower, zeros)
 from . import trace
 

@@ -59,6 +59,12 @@ class TemperedCfg(C.Structure):
     _fields_ = [("R", C.c_int32), ("swap_every", C.c_int32), ("beta", C.c_void_p), ("scale", C.c_void_p)]
 
 
+class ProposalAdaptCfg(C.Structure):
+    """mhx_proposal_adapt_cfg: how the chains of an adaptive random walk tune their proposal; a NaN double takes its default"""
+    _fields_ = [("adapt_steps", C.c_int32), ("shape", C.c_int32), ("target_rate", C.c_double), ("c", C.c_double), ("kappa", C.c_double),
+                ("lam_min", C.c_double), ("lam_max", C.c_double)]
+
+
 class LadderAdaptCfg(C.Structure):
     """mhx_ladder_adapt_cfg: how the ladders of a tempered run adapt; a NaN double takes its default"""
     _fields_ = [("adapt_steps", C.c_int32), ("target_rate", C.c_double), ("c", C.c_double), ("kappa", C.c_double),
@@ -152,6 +158,7 @@ EXPORTS = [
     "mhx_run_derive", "mhx_ctx_derive", "mhx_run_predict", "mhx_ctx_predict", "mhx_run_pointwise", "mhx_ctx_pointwise",
     "mhx_run_psis", "mhx_ctx_psis", "mhx_rwmh_create_tempered", "mhx_run_swap_stats", "mhx_run_rung",
     "mhx_rwmh_create_tempered_adaptive", "mhx_run_ladder_betas", "mhx_rwmh_create_tempered_anchored", "mhx_run_evidence",
+    "mhx_rwmh_create_adaptive", "mhx_run_proposal_state",
 ]
 
 MHX_F32, MHX_F64 = 0, 1
@@ -325,6 +332,9 @@ def lib():
         if hasattr(L, "mhx_run_evidence"):
             L.mhx_rwmh_create_tempered_anchored.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(TemperedCfg), C.POINTER(TemperedReference), pvp]
             L.mhx_run_evidence.argtypes = [vp, dp, i64p]
+        if hasattr(L, "mhx_run_proposal_state"):          # (the parent build of an A/B run has neither)
+            L.mhx_rwmh_create_adaptive.argtypes = [vp, vp, C.POINTER(RwmhCfg), C.POINTER(ProposalAdaptCfg), pvp]
+            L.mhx_run_proposal_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_uint32)]
         _lib = _loaded[_lib_path] = L
     return _lib
 

@@ -863,8 +863,22 @@ class MetropolisHastings:
     of ONE kind (all random-walk or all static; Normal or any other device family); its keys name the parameters
     (src/AdvancedMH.jl:96-104)."""
 
-    def __init__(self, proposal):
+    def __init__(self, proposal, adapt=None):
+        """adapt: a ProposalAdaptation -- every chain tunes its own proposal during the first adapt.steps transitions
+        (mhx_rwmh_create_adaptive); only for a zero-mean isotropic or diagonal MvNormal random walk."""
         self.param_names = None
+        self.adapt = None
+        if adapt is not None:
+            if not isinstance(adapt, ProposalAdaptation):
+                raise L.ArgumentError(L.MHX_EINVAL, "MetropolisHastings: adapt must be a ProposalAdaptation or None")
+            self.__init__(proposal)
+            mv = self.proposal.proposal
+            if not isinstance(self.proposal, RandomWalkProposal) or not isinstance(mv, MvNormal) or \
+                    mv.kind not in (L.PROP_ISO, L.PROP_DIAG) or np.any(mv.mean != 0):
+                raise L.ArgumentError(L.MHX_EINVAL, "MetropolisHastings: adapt is for a random walk over a zero-mean isotropic or diagonal "
+                                      "MvNormal (dense, drifting, static, family, function and composite proposals do not adapt)")
+            self.adapt = adapt
+            return
         if isinstance(proposal, (list, tuple, NamedProposals)):
             # the reference's Array{Proposal} / NamedTuple{Proposal} in full (src/proposal.jl:128-175): entries that are all scalar,
             # constant and of one kind fold exactly as the mapping form below does; anything else is a composite run
@@ -928,9 +942,55 @@ def StaticMH(d):
     return MetropolisHastings(StaticProposal(d))
 
 
-def RWMH(d):
-    """RWMH(d) / RWMH(d::Int) -- src/mh-core.jl:50-51."""
-    return MetropolisHastings(RandomWalkProposal(d))
+def RWMH(d, adapt=None):
+    """RWMH(d) / RWMH(d::Int) -- src/mh-core.jl:50-51.  adapt: a ProposalAdaptation (see MetropolisHastings)."""
+    return MetropolisHastings(RandomWalkProposal(d), adapt=adapt)
+
+
+class ProposalAdaptation:
+    """ProposalAdaptation(steps, target_rate=0.234, c=1.0, kappa=0.6, shape=False, lam_min=None, lam_max=None) -- how the chains of an
+    RWMH sampler tune their own proposal during the first `steps` transitions (mhx_proposal_adapt_cfg): after
+    transition t the chain's log-scale moves by min(1, c * t^(-kappa)) * (min(1, accept ratio) - target_rate), clamped to
+    [lam_min, lam_max] (None: the library's defaults, -20 and 20); shape=True: the per-coordinate standard deviations follow the
+    chain's own running variance as well.  Afterwards the proposal is frozen and the chain is a plain random walk."""
+
+    def __init__(self, steps, target_rate=0.234, c=1.0, kappa=0.6, shape=False, lam_min=None, lam_max=None):
+        self.steps, self.target_rate, self.c, self.kappa = int(steps), float(target_rate), float(c), float(kappa)
+        self.shape = bool(shape)
+        self.lam_min = None if lam_min is None else float(lam_min)
+        self.lam_max = None if lam_max is None else float(lam_max)
+        if self.steps < 0:
+            raise L.ArgumentError(L.MHX_EINVAL, "ProposalAdaptation: steps = %d must not be negative" % self.steps)
+        if not (0.5 < self.kappa <= 1.0):
+            raise L.ArgumentError(L.MHX_EINVAL, "ProposalAdaptation: kappa = %g outside (0.5, 1]" % self.kappa)
+        if not (self.c >= 0.0 and np.isfinite(self.c)):
+            raise L.ArgumentError(L.MHX_EINVAL, "ProposalAdaptation: c = %g must be finite and not negative" % self.c)
+        if not (0.0 < self.target_rate < 1.0):
+            raise L.ArgumentError(L.MHX_EINVAL, "ProposalAdaptation: target_rate = %g outside (0, 1)" % self.target_rate)
+        if self.lam_min is not None and self.lam_max is not None and not (self.lam_min <= self.lam_max):
+            raise L.ArgumentError(L.MHX_EINVAL, "ProposalAdaptation: lam_min = %g > lam_max = %g" % (self.lam_min, self.lam_max))
+
+    def cfg(self):
+        nan = float("nan")
+        return L.ProposalAdaptCfg(self.steps, 1 if self.shape else 0, self.target_rate, self.c, self.kappa,
+                                  nan if self.lam_min is None else self.lam_min, nan if self.lam_max is None else self.lam_max)
+
+
+class AdaptationTable(list):
+    """chain.adaptation of an adaptive run: one row {parameter, sd_median, sd_min, sd_max} per parameter -- the frozen proposal's
+    standard deviations over the chains -- with `lam_median`, the median log-scale, and `accept_rate`, the pooled acceptance rate of
+    the frozen phase (NaN: no frozen transition yet), as attributes"""
+    lam_median = float("nan")
+    accept_rate = float("nan")
+
+    def __str__(self):
+        out = ["parameter         sd median         min         max"]
+        for w in self:
+            out.append("%-12s %14.5g %11.5g %11.5g" % (w["parameter"], w["sd_median"], w["sd_min"], w["sd_max"]))
+        out.append("median log-scale %.4f, acceptance rate of the frozen phase %.3f" % (self.lam_median, self.accept_rate))
+        return "\n".join(out)
+
+    __repr__ = __str__
 
 
 def geometric_betas(R, beta_min):
@@ -999,6 +1059,8 @@ class Tempered:
         if not isinstance(sampler, MetropolisHastings) or not isinstance(sampler.proposal, RandomWalkProposal) or \
                 not isinstance(sampler.proposal.proposal, MvNormal):
             raise L.ArgumentError(L.MHX_EINVAL, "Tempered wraps an RWMH sampler over an isotropic or diagonal MvNormal")
+        if getattr(sampler, "adapt", None) is not None:
+            raise L.ArgumentError(L.MHX_EINVAL, "Tempered: the wrapped sampler adapts its proposal (ProposalAdaptation), which a tempered run does not")
         self.sampler = sampler
         self.proposal = sampler.proposal                     # (what Run.init looks at)
         self.param_names = sampler.param_names
@@ -1915,6 +1977,7 @@ class Run:
         d = model.dim
         self._keep = []
         self.tempered = isinstance(sampler, Tempered)
+        self.adaptive = False
         if self.tempered:
             # a ladder of R rungs per "chain" asked for: nchains device chains in all, whole ladders (mhx_rwmh_create_tempered)
             mv = sampler.proposal.proposal
@@ -1978,7 +2041,12 @@ class Run:
                 mean = f32(mv.mean) if np.any(mv.mean != 0) else None
                 self._keep += [vec, mean]
                 cfg = L.RwmhCfg(d, nchains, seed, first_chain, mv.kind, mv.scale, L.fptr(vec), flags, L.fptr(mean), reduce_lanes)
-                L.check(lib.mhx_rwmh_create(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(self.h)))
+                if getattr(sampler, "adapt", None) is not None:
+                    acfg = sampler.adapt.cfg()
+                    L.check(lib.mhx_rwmh_create_adaptive(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(acfg), C.byref(self.h)))
+                    self.adaptive = True
+                else:
+                    L.check(lib.mhx_rwmh_create(self.ctx.h, model.handle(self.ctx), C.byref(cfg), C.byref(self.h)))
             self.n = nchains
             self.kind = "rwmh"
         elif isinstance(sampler, Ensemble):
@@ -2559,6 +2627,32 @@ class Run:
         out.n = self.n // self.sampler.R
         return out
 
+    # -- an adaptive run (RWMH(..., adapt=ProposalAdaptation(...))): every chain's own proposal
+    def proposal_state(self):
+        """dict(lam [nchains], sd [dim][nchains], mean [dim][nchains] (NaN without shape), acc_at_freeze [nchains] uint32) as of the end
+        of the last sample call, float64 widened exactly from the run's width (mhx_run_proposal_state)"""
+        n, d = self.n, self.dim
+        lam, sd, mean = np.empty(n, dtype=np.float64), np.empty((d, n), dtype=np.float64), np.empty((d, n), dtype=np.float64)
+        acc = np.empty(n, dtype=np.uint32)
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().mhx_run_proposal_state(self.h, lam.ctypes.data_as(dp), sd.ctypes.data_as(dp), mean.ctypes.data_as(dp),
+                                               acc.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return dict(lam=lam, sd=sd, mean=mean, acc_at_freeze=acc)
+
+    def adaptation(self, names=None):
+        """the AdaptationTable of an adaptive run: median / min / max of sd over the chains per parameter, the median lam and the pooled
+        acceptance rate of the transitions after the proposal froze"""
+        ps = self.proposal_state()
+        names = names or ["param_%d" % (k + 1) for k in range(self.dim)]
+        t = AdaptationTable(dict(parameter=str(names[k]), sd_median=float(np.median(ps["sd"][k])), sd_min=float(ps["sd"][k].min()),
+                                 sd_max=float(ps["sd"][k].max())) for k in range(self.dim))
+        t.lam_median = float(np.median(ps["lam"]))
+        frozen = getattr(self, "_transitions", 0) - self.sampler.adapt.steps
+        if frozen > 0:
+            cnt = self.state()[2].astype(np.int64) - ps["acc_at_freeze"].astype(np.int64)
+            t.accept_rate = float(cnt.sum()) / (float(frozen) * self.n)
+        return t
+
     def accept_rates(self):
         """Metropolis-Hastings acceptance rate of every temperature since init: accepted proposals of the rung's slots over their
         transitions, [R]"""
@@ -2670,11 +2764,22 @@ def sample(model, sampler, N, nchains=1, *more, initial_params=None, discard_ini
             raise L.ArgumentError(L.MHX_EINVAL, "sample: discard_initial = %d < adapt.steps = %d -- draws taken while the ladder moves are "
                                   "not draws of the target: discard at least the adapting transitions (discard_initial >= adapt.steps)"
                                   % (discard_initial, sampler.adapt.steps))
+    adapt = getattr(sampler, "adapt", None) if isinstance(sampler, MetropolisHastings) else None
+    if adapt is not None and discard_initial < adapt.steps:
+        raise L.ArgumentError(L.MHX_EINVAL, "sample: discard_initial = %d < adapt.steps = %d -- draws taken while the proposal moves are "
+                              "not draws of the target: discard at least the adapting transitions (discard_initial >= adapt.steps)"
+                              % (discard_initial, adapt.steps))
     run = Run(model, sampler, nchains=nchains, seed=seed, first_chain=first_chain, ctx=ctx, flags=flags,
               reduce_lanes=reduce_lanes, dtype=dtype, normal_gen=normal_gen)
     run.init(initial_params)
     cold = None
-    if run.tempered:
+    if run.adaptive:
+        # the draws stay on the device (the accept-compacted return path is left out for this form) and come back in one copy
+        if callback is not None:
+            raise L.ArgumentError(L.MHX_EINVAL, "sample: an adaptive run takes no callback")
+        run.sample(N, discard_initial, thinning, num_warmup)
+        value, acc = run.samples()
+    elif run.tempered:
         # the draws stay on the device (the accept-compacted return path does not know swaps): the cold rung is gathered there and
         # only it comes back
         if callback is not None:
@@ -2721,6 +2826,8 @@ def sample(model, sampler, N, nchains=1, *more, initial_params=None, discard_ini
         chain = Chains(value, names, discard_initial + 1, thinning, accepted=acc, stats=run.stats(), state=cold if cold is not None else run)
         if cold is not None:
             chain.tempered = run                                    # the full run: swap_rates(), rung(r), accept_rates()
+        if run.adaptive:
+            chain.adaptation = run.adaptation(names[:-1])           # what every chain's proposal froze at
         return chain
     if chain_type is np.ndarray:
         return value

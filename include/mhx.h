@@ -528,7 +528,9 @@ typedef struct {
                                   form (pre-built for the catalogue targets), the same chain,
                                   17 a tempered run whose ladders adapt (mhx_rwmh_create_tempered_adaptive): the same two forms,
                                   18 a tempered run anchored at a reference density (mhx_rwmh_create_tempered_anchored): the same
-                                  two forms */
+                                  two forms,
+                                  19 an adaptive random walk (mhx_rwmh_create_adaptive): an adapting and a frozen phase, each with
+                                  the same two forms */
     int32_t launches;
     int32_t reduce_lanes;      /* lanes per chain in effect (1 unless a cooperative kernel runs) */
     int32_t dtype;             /* mhx_dtype of the run's context */
@@ -537,8 +539,9 @@ typedef struct {
                                   (0 = diagonal, 1 = bidiagonal: an AR(1) / Markov model, ...), -1 = none (dense form, other samplers) */
     int32_t tainted;           /* 1: a probe / fault-injection option of the tools build was set on the run's context -- the chains of
                                   such a run may be INVALID (timing probes skip work).  Always 0 from libmhx.so. */
-    int32_t register_form;     /* kernel variants 13 .. 18: 1 = the run is stepped by the run-time specialised register form, 0 = by
-                                  the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant */
+    int32_t register_form;     /* kernel variants 13 .. 19: 1 = the run is stepped by the run-time specialised register form, 0 = by
+                                  the state-in-HBM form (MHX_FLAG_GENERIC or a shape outside the register rule); 0 for every other variant.
+                                  Variant 19: of the phase the run's next transition belongs to */
 } mhx_stats;
 int mhx_run_stats(mhx_run *run, mhx_stats *out);
 /* The name of the run's kernel form -- kernel_variant spelled out ("generic", "reg", "coop", "coop_jit", "wave", ...) -- with the body
@@ -1058,6 +1061,38 @@ int mhx_rwmh_create_tempered_anchored(mhx_ctx *ctx, const mhx_target *t, const m
  * beta; the stepping-stone estimate is sum_r log mean exp(dbeta[r] u) over rung r + 1.  One sweep of the tensor, no atomics: two calls
  * give the same bits.  MHX_ESTATE: not an anchored run, no sample tensor, or the ladder's last beta is not 0.  Blocking. */
 int mhx_run_evidence(mhx_run *run, double *out, int64_t *n_saved);
+
+/* ---------------------------------------------------------------------------------------------
+ * Adaptive random-walk Metropolis (Andrieu & Thoms 2008, Algorithm 4 with a diagonal covariance): during the
+ * first adapt_steps transitions every chain tunes its OWN proposal inside the step kernel -- a log-scale lam driven towards the
+ * acceptance rate target_rate,
+ *     lam += min(1, c t^(-kappa)) * (min(1, accept ratio) - target_rate),   clamped to [lam_min, lam_max]
+ * and, with shape != 0, a running mean and variance per coordinate whose square root replaces the configured standard deviation; the
+ * proposal's standard deviations are sd[k] = sig[k] * exp(lam).  Afterwards nothing adapts: sd is a constant of the chain and the run
+ * is a plain random walk with a diagonal proposal, at the plain lane-per-chain kernels' rate.  Everything is per chain -- no reduction
+ * over chains -- and indexed by the global step, so a shard is still the matching columns of the larger run and two calls are one.
+ * Draws taken while the proposal moves are not draws of the target: discard at least adapt_steps transitions.
+ *     cfg          an ISO or a DIAG proposal with zero mean: where every chain starts from (lam = 0)
+ *     adapt_steps  >= 0 transitions; 0: the plain run
+ *     shape        0: the scale alone, else the per-coordinate standard deviations too
+ *     a double field that is NaN takes its default: target_rate 0.234, c 1, kappa 0.6, lam_min -20, lam_max 20 (0 is a value)
+ * MHX_EINVAL with a message that names the rule: a DENSE proposal, a proposal mean, MHX_FLAG_STATIC_PROPOSAL, MHX_FLAG_ZIGGURAT,
+ * reduce_lanes > 1, MHX_FLAG_NO_JIT with a user target, adapt_steps < 0, kappa outside (0.5, 1], c < 0, target_rate outside (0, 1),
+ * lam_min > lam_max, and (shape) a configured s[k] whose s[k]^2 2^-40 is not normal or whose s[k]^2 2^40 is not finite in the run's
+ * width (the clamps of the adapted variance).  The run is kernel variant 19; mhx_run_init / mhx_run_sample drive it; it refuses with
+ * MHX_ESTATE what the tempered runs refuse (MHX_SAVE_MOMENTS, mhx_run_sample_to_host, checkpoints, mhx_group_attach). */
+typedef struct {
+    int32_t adapt_steps;
+    int32_t shape;
+    double target_rate, c, kappa, lam_min, lam_max;
+} mhx_proposal_adapt_cfg;
+int mhx_rwmh_create_adaptive(mhx_ctx *ctx, const mhx_target *t, const mhx_rwmh_cfg *cfg,
+                             const mhx_proposal_adapt_cfg *acfg, mhx_run **out);
+/* The proposal of every chain as of the end of the last mhx_run_sample (after mhx_run_init: the configured one), widened exactly from
+ * the run's width: lam[nchains], sd[dim][nchains] (the standard deviations the proposal uses), mean[dim][nchains] (may be NULL; NaN
+ * without shape), acc_at_freeze[nchains] (may be NULL): the accept counters as they stood after transition adapt_steps, 0 while the
+ * run still adapts.  MHX_ESTATE: not an adaptive run.  Blocking. */
+int mhx_run_proposal_state(mhx_run *run, double *lam, double *sd, double *mean, uint32_t *acc_at_freeze);
 
 /* ---------------------------------------------------------------------------------------------
  * Many chains over many GPUs as ONE call from ONE process. Replaces `sample(model, sampler, MCMCThreads(), N, nchains)`
